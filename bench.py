@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """Benchmark of the flow + egomotion-warp + frame-difference hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1080p|4k|640]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1080p|4k|640] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps,
+write the last step's outputs if --dump-outputs is given, print the JSON line.  Every other leg
+(the unpipelined rate, 4K, RANSAC, the warp+diff and LK rooflines, the oracle check of the last
+step, the CPU baselines, the node's live chain) runs only with --full; their fields are null
+without it.
 
 A *step* = one pass of the whole reference path (gray+pad, pyramids, Scharr, pyramidal LK,
 first-4 perspective fit, back-warp + absdiff + threshold) over a batch of B synthetic frame
@@ -12,7 +18,7 @@ GPU (LOCAL_RANK) with its own seeds: no data-path collective; torch.distributed 
 only for the barrier and the max-over-ranks timing.  value = pixels of frame 2 processed by
 all ranks / max-over-ranks wall time, in Mpixels/s (weak scaling).
 
-Also reported, for the north-star kernel (fused warp+diff, rows A8-A10) on 4K pairs with the
+Also reported with --full, for the north-star kernel (fused warp+diff, rows A8-A10) on 4K pairs with the
 generator's true homography: achieved algorithmic HBM GB/s vs the 8 TB/s peak ("roofline"),
 and the CPU oracle (C restatement of the reference path) timed on this host ("cpu_baseline").
 """
@@ -193,6 +199,62 @@ def check_outputs(uniq, outs, B, w, h, ps, threads):
                 compared="next_pts bits, status, Vec4d bits, H bits, mask, num_vectors vs oracle/ (untimed)")
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # --dump-outputs: all files of a run together stay under 64 MB
+DUMP_SEED = 20141105
+
+
+def dump_outputs(dirname: str, arrays: dict, rank: int = 0, world: int = 1) -> dict:
+    """--dump-outputs: write each output array of the last timed step as DIR/<name>.npy (rank r > 0:
+    DIR/<name>_rank<r>.npy).  float64 outputs stay float64, every other type becomes float32 (exact
+    for the u8 / i32 / f32 values written here).  The budget is dealt smallest array first; an array
+    that does not fit its share is written as a fixed sample: the elements at sorted indices drawn
+    once from default_rng(DUMP_SEED) over its flat size, so the same elements in every run and every
+    build.  Returns {name: [elements written, elements in all]}."""
+    os.makedirs(dirname, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES // max(world, 1), {}
+    order = sorted(arrays, key=lambda k: arrays[k].size * (8 if arrays[k].dtype == np.float64 else 4))
+    for i, name in enumerate(order):
+        a = arrays[name]
+        dt = np.float64 if a.dtype == np.float64 else np.float32
+        cap = left // (len(order) - i) // np.dtype(dt).itemsize
+        flat = a.reshape(-1)
+        if flat.size > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, size=cap))
+            out = flat[idx].astype(dt)
+        else:
+            out = a.astype(dt)
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if rank else "") + ".npy"), out)
+        left -= out.nbytes
+        written[name] = [int(out.size), int(flat.size)]
+    return written
+
+
+TIMED_SLOTS = 256   # stage events the library keeps between enable_timing and readout (mdx_api.cpp kSlots)
+
+
+def run_timed(D: Dist, ctx, step, k: int):
+    """k steps on the clock, in runs of at most TIMED_SLOTS: each run is bracketed by barriers and
+    device syncs (the device sync also reports an LK hand-off timeout as an error) with the stage
+    events on, and the stage sums are read between runs, off the clock.  Up to TIMED_SLOTS steps
+    that is one run.  Returns (this rank's wall seconds over the runs, summed stage_ms dict)."""
+    el, st, left = 0.0, {}, k
+    while left > 0:
+        m = min(left, TIMED_SLOTS)
+        ctx.enable_timing(True)
+        D.barrier()
+        ctx.device_sync()
+        t = time.perf_counter()
+        for _ in range(m):
+            step()
+        ctx.device_sync()
+        D.barrier()
+        el += time.perf_counter() - t
+        for name, v in ctx.stage_ms().items():
+            st[name] = st.get(name, 0) + v
+        left -= m
+    return el, st
+
+
 REHEARSE = False   # --rehearse: ranks beyond the visible devices may share device 0
 
 
@@ -344,6 +406,9 @@ def main_c4(args, D: Dist, threads: int):
                                                  cands=K * 96, mask=w * h, num=4).items()}
         c.h2d(d["i1"], a)
         c.h2d(d["i2"], b)
+        if args.dump_outputs:                                    # entries of other ranks' bands stay 0 in the dump
+            for k, sz in dict(np=n * 8, st=n, mask=w * h, num=4).items():
+                c.h2d(d[k], np.zeros(sz, np.uint8))
         bufs.append(d)
     rows = [rowtile.band_rows(h, K, k) for k in range(K)]
     pad = bytes(96)
@@ -399,6 +464,14 @@ def main_c4(args, D: Dist, threads: int):
     el_max = D.max(el)
     num = np.empty(1, np.int32)
     ctxs[0].d2h(num, bufs[0]["num"])
+    dumped = None
+    if args.dump_outputs:
+        # the last step's frame 0 (every in-flight frame is the same pair): this rank's bands' rows
+        # and points of the full-frame arrays, the rest 0
+        o = dict(next_pts=np.empty((n, 2), np.float32), status=np.empty(n, np.uint8), mask=np.empty((h, w), np.uint8))
+        for k, src in (("next_pts", "np"), ("status", "st"), ("mask", "mask")):
+            ctxs[0].d2h(o[k], bufs[0][src])
+        dumped = dump_outputs(args.dump_outputs, dict(o, num_vectors=num), D.rank, D.world)
     # one band alone per in-flight frame (K bands on K GPUs: each GPU's share), timed here for the
     # rehearsal case: F frames of band mine[0], amortised per frame
     band_ms = None
@@ -444,6 +517,7 @@ def main_c4(args, D: Dist, threads: int):
         "one_band_ms": round(band_ms, 3) if band_ms else None,
         "num_vectors": int(num[0]),
         "lk_fallbacks": [c.lk_fallbacks() for c in ctxs],
+        "dumped_outputs": dumped,
         "roofline": None,
         "cpu_baseline": None,
     }
@@ -564,7 +638,19 @@ def main():
     ap.add_argument("--probe-ranks", action="store_true", help="launch plumbing only: ranks report over gloo, no GPU")
     ap.add_argument("--no-pipelining", action="store_true", help="time the main leg with call pipelining off")
     ap.add_argument("--no-parity", action="store_true", help="skip the untimed oracle check of the last step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure (unpipelined rate, 4K, RANSAC, rooflines, "
+                         "oracle check, CPU baselines, live chain); the --no-* options then leave legs out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32 / float64, "
+                         "under 64 MB in all; a larger array as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only_roofline and not args.full:
+        ap.error("--only-roofline runs a leg of --full: pass --full with it")
+    if args.only_roofline and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline step's outputs, which --only-roofline does not run")
     global REHEARSE
     REHEARSE = args.rehearse
 
@@ -625,26 +711,31 @@ def main():
         step()
     ctx.device_sync()
 
-    ctx.enable_timing(True)
-    el = timed(full_steps)
+    el, st = run_timed(D, ctx, step, full_steps)
     px_rate, el_max = throughput(D, float(full_steps * B * w * h), el)
     value = px_rate / 1e6
     px_all = px_rate * el_max
-    st = ctx.stage_ms()
     calls = max(st["calls"], 1)
     stages = {k: round(v / calls, 4) for k, v in st.items() if k != "calls"}
-    # the last timed step's outputs, checked against the oracle after every timed leg (untimed)
+    # the last timed step's outputs: written by --dump-outputs, and with --full checked against the
+    # oracle after every timed leg (untimed); a plain run reads back num_vectors alone
+    want_parity = args.full and not args.only_roofline and not args.no_parity
     outs = {k: np.empty(shape, dt) for k, shape, dt in (("np", (B, n, 2), np.float32), ("st", (B, n), np.uint8),
                                                          ("vec", (B, n, 4), np.float64),
                                                          ("mask", (B, h, w), np.uint8), ("H", (B, 9), np.float64),
-                                                         ("num", (B,), np.int32))}
+                                                         ("num", (B,), np.int32))
+            if k == "num" or want_parity or args.dump_outputs}
     for k, arr in outs.items():
         ctx.d2h(arr, dout[k])
     num = outs["num"]
     fallbacks = ctx.lk_fallbacks()
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, dict(next_pts=outs["np"], status=outs["st"], vectors=outs["vec"],
+                                                      mask=outs["mask"], H=outs["H"], num_vectors=num), D.rank, D.world)
     # the same steps with call pipelining off (the line's value_unpipelined)
     value_unpiped = None
-    if pipe and not args.only_roofline:
+    if args.full and pipe and not args.only_roofline:
         ctx.set_params(call_pipelining=0)
         step()
         el_u = timed(full_steps)
@@ -656,7 +747,7 @@ def main():
 
     # ---- the whole path at 4K (config C2; the metric names 1080p & 4K): 8 pairs per step
     full4k = None
-    if not args.no_4k and not args.only_roofline and args.config == "1080p":
+    if args.full and not args.no_4k and not args.only_roofline and args.config == "1080p":
         kw, kh = CONFIGS["4k"]
         KB = 8
         k1, k2, _, _ = make_batch(kw, kh, KB, min(4, KB), SEED0 + 500 + 1000 * D.rank, threads)
@@ -695,7 +786,7 @@ def main():
     # ---- MDX_FIT_RANSAC (not in the reference; parity with it N/A): the headline step with the
     # deterministic RANSAC fit instead of first-4, so the warp runs on a real, projective fit
     ransac = None
-    if not args.no_ransac and not args.only_roofline and args.config == "1080p":
+    if args.full and not args.no_ransac and not args.only_roofline and args.config == "1080p":
         rkw = dict(pixel_step=ps, min_vector_size=1.0, call_pipelining=pipe, fit_mode=mdx.FIT_RANSAC)
         qg1, qg2, _, quniq = make_batch(w, h, B, unique, SEED0 + 1000 * D.rank, threads)
         qctx = open_ctx(D, w, h, B, **rkw)
@@ -711,15 +802,8 @@ def main():
         for _ in range(max(1, args.warmup)):
             stepq()
         qctx.device_sync()
-        qctx.enable_timing(True)
-        D.barrier()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            stepq()
-        qctx.device_sync()
-        D.barrier()
-        rateq, elq = throughput(D, float(args.steps * B * w * h), time.perf_counter() - t0)
-        qs = qctx.stage_ms()
+        elq_local, qs = run_timed(D, qctx, stepq, args.steps)
+        rateq, elq = throughput(D, float(args.steps * B * w * h), elq_local)
         qst = {k: round(v / max(qs["calls"], 1), 4) for k, v in qs.items() if k in ("classify_fit", "warp_diff")}
         qH = np.empty((B, 9))
         qctx.d2h(qH, qo["H"])
@@ -749,7 +833,7 @@ def main():
 
     # ---- north-star kernel: fused warp+diff at 4K with the generator's true H
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         rw, rh = CONFIGS[args.roofline_config]
         RB = args.roofline_batch
         r1, r2, Hr, _ = make_batch(rw, rh, RB, min(4, RB), SEED0 + 77 + 1000 * D.rank, threads)
@@ -763,6 +847,7 @@ def main():
         # 180-190 -> 141 us over its first ~120 launches on the same inputs, the copy probe flat at
         # 121 us: profiles/r05_warp_transient.txt), so each leg is timed after roofline_warmup launches
         rwarm = max(2, args.warmup, args.roofline_warmup)
+        rsteps = min(args.steps, TIMED_SLOTS)   # timed launches per leg: --steps, as far as the stage events reach
         cold_ms = None
         if args.roofline_h != "projective":
             # the cold burst, reported beside the warmed figure: the first --steps launches after
@@ -770,7 +855,7 @@ def main():
             rctx.device_sync()
             time.sleep(max(0.0, args.cold_idle))
             rctx.enable_timing(True)
-            for _ in range(args.steps):
+            for _ in range(rsteps):
                 rctx.warp_diff_dev(RB, e1, e2, rw, rh, rw, rw * rh, eH, eM)
             rctx.device_sync()
             cs0 = rctx.stage_ms()
@@ -780,7 +865,7 @@ def main():
                 rctx.warp_diff_dev(RB, e1, e2, rw, rh, rw, rw * rh, eH, eM)
             rctx.device_sync()
             rctx.enable_timing(True)
-            for _ in range(args.steps):
+            for _ in range(rsteps):
                 rctx.warp_diff_dev(RB, e1, e2, rw, rh, rw, rw * rh, eH, eM)
             rctx.device_sync()
             rs = rctx.stage_ms()
@@ -793,7 +878,7 @@ def main():
             rctx.probe_stream3_dev(RB * rw * rh, e1, e2, eM)
         rctx.device_sync()
         rctx.enable_timing(True)
-        for _ in range(args.steps):
+        for _ in range(rsteps):
             rctx.probe_stream3_dev(RB * rw * rh, e1, e2, eM)
         rctx.device_sync()
         cs = rctx.stage_ms()
@@ -810,7 +895,7 @@ def main():
                 rctx.warp_diff_dev(RB, e1, e2, rw, rh, rw, rw * rh, eH, eM)
             rctx.device_sync()
             rctx.enable_timing(True)
-            for _ in range(args.steps):
+            for _ in range(rsteps):
                 rctx.warp_diff_dev(RB, e1, e2, rw, rh, rw, rw * rh, eH, eM)
             rctx.device_sync()
             ps_ = rctx.stage_ms()
@@ -834,10 +919,10 @@ def main():
                     frac=round(achieved / HBM_PEAK_GBS, 4) if achieved else None, traffic=traffic, kernel="k_warp_diff",
                     workload=f"{rw}x{rh} gray, {RB} pairs per launch, true H (affine), 3 B/px algorithmic",
                     avg_launch_us=round(launch_ms * 1e3, 2) if launch_ms else None,
-                    timed_launches=args.steps, warmup_launches=rwarm,
+                    timed_launches=rsteps, warmup_launches=rwarm,
                     cold_burst=(dict(avg_launch_us=round(cold_ms * 1e3, 2),
                                      frac=round(alg_bytes / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                     what=f"the first {args.steps} launches after {args.cold_idle:g} s idle, before "
+                                     what=f"the first {rsteps} launches after {args.cold_idle:g} s idle, before "
                                           f"the warmup (clock / power transient: profiles/r06_warp_burst.txt)")
                                 if cold_ms else None),
                     algorithmic_bytes_per_launch=int(alg_bytes),
@@ -855,24 +940,24 @@ def main():
         del r1, r2
 
     parity = None
-    if not args.only_roofline and not args.no_parity:
+    if want_parity:
         parity = check_outputs(uniq, outs, B, w, h, ps, host_cores()["available"])
     cpu = cpu1 = cpu_scalar = None
-    if D.world == 1 and not args.no_cpu:
+    if args.full and D.world == 1 and not args.no_cpu:
         hc = host_cores()
         cpu = cpu_baseline(uniq, w, h, args.cpu_seconds, hc["available"])   # every CPU this job may use, SSE2
         cpu.update(nproc=hc["nproc"], cgroup_cpu_quota=hc["cgroup_cpu_quota"])
         cpu1 = cpu_baseline(uniq, w, h, args.cpu_seconds / 2, 1)          # one core, SSE2
         cpu_scalar = cpu_baseline(uniq, w, h, args.cpu_seconds / 2, hc["available"], simd=False)
     live = None
-    if D.world == 1 and not args.no_live and not args.only_roofline:
+    if args.full and D.world == 1 and not args.no_live and not args.only_roofline:
         live = live_leg(D.local_rank, w, h, threads, with_cpu=not args.no_cpu)
 
     lk_share = stages["lk"] / stages["total"] if stages["total"] > 0 else None
     # VALU roofline of the dominant stage (LK): algorithmic wave-instructions of the
     # step's B pairs over the LK stage's HIP-event time, against the chip's VALU issue rate
     lk_roof = None
-    if not args.only_roofline and not args.no_lk_roofline and stages.get("lk", 0) > 0:
+    if args.full and not args.only_roofline and not args.no_lk_roofline and stages.get("lk", 0) > 0:
         wk = lk_work(ctx.device, w, h, ps, uniq)
         alg_wave = wk["valu_lane_instr_per_pair"] * B / 64.0
         ach = alg_wave / (stages["lk"] * 1e-3)
@@ -925,6 +1010,8 @@ def main():
                             "roofline": lk_roof},
         "num_vectors_pair0": int(num[0]),
         "lk_fallbacks": fallbacks,
+        "full": bool(args.full),
+        "dumped_outputs": dumped,
         "full_path_4k": full4k,
         "full_path_ransac": ransac,
         "live_path": live,

@@ -7,14 +7,14 @@ out=gpurun_out/r03; mkdir -p $out
 export TMPDIR=/tmp
 step() { echo "== $1"; }
 step profile
-bash scripts/profile.sh r03 --no-cpu > $out/profile.log 2>&1 || exit 1
+bash scripts/profile.sh r03 --full --no-cpu > $out/profile.log 2>&1 || exit 1
 step pmc_lk
 bash scripts/pmc_lk.sh > $out/pmc_lk.log 2>&1 || exit 1
 step pmc_step
 BENCH_ARGS="--steps 2 --warmup 1 --no-cpu --no-roofline --no-live --no-4k --no-lk-roofline" \
     bash scripts/pmc_sets.sh step "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_step.log 2>&1 || exit 1
 step pmc_warp
-BENCH_ARGS="--only-roofline --steps 3 --warmup 1 --no-cpu" \
+BENCH_ARGS="--full --only-roofline --steps 3 --warmup 1 --no-cpu" \
     bash scripts/pmc_sets.sh warp "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_warp.log 2>&1 || exit 1
 step c4
 timeout -k 10 200 python3 bench.py --workload c4 --config 8k --bands 8 --inflight 2 --steps 10 --warmup 3 \

@@ -10,9 +10,10 @@ for v in default "$@"; do
     rt=$?; echo "$v: warp tests rc=$rt $(tail -1 gpurun_out/warp_tests_$v.log)"
     [ $rt -le 1 ] || exit $rt
     [ $rt -eq 0 ] || rc=1
-    timeout -k 10 200 python bench.py --only-roofline --steps 20 --warmup 3 --no-cpu > gpurun_out/roof_$v.json 2> gpurun_out/roof_$v.err
+    log=${LOG_DIR:-logs}; mkdir -p $log
+    timeout -k 10 200 python bench.py --full --only-roofline --steps 20 --warmup 3 --no-cpu > $log/roof_$v.json 2> $log/roof_$v.err
     rc2=$?
-    python3 -c "import json; d=json.load(open('gpurun_out/roof_$v.json')); print('$v', d['roofline']['avg_launch_us'], d['roofline']['frac'])" || echo "$v rc=$rc2"
+    python3 -c "import json; d=json.load(open('$log/roof_$v.json')); print('$v', d['roofline']['avg_launch_us'], d['roofline']['frac'])" || echo "$v rc=$rc2"
     [ $rc2 -le 1 ] || exit $rc2
 done
 exit $rc

@@ -7,7 +7,7 @@ rc=$?; echo "warp tests rc=$rc"; tail -3 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
 for rep in 1 2; do
   for impl in ${IMPLS:-1 2}; do
-    MDX_WARP=$impl timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-cpu --no-live --no-4k --only-roofline \
+    MDX_WARP=$impl timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-cpu --no-live --no-4k --full --only-roofline \
         > $out/r${rep}_$impl.json 2> $out/r${rep}_$impl.err
     rc=$?
     python3 -c "import json; d=json.load(open('$out/r${rep}_$impl.json')); r=d['roofline']; print('impl $impl', r['avg_launch_us'], r['frac'])" || { echo "impl $impl rc=$rc"; exit 1; }

@@ -10,7 +10,7 @@ for impl in ${IMPLS:-1 2}; do
     for set in "$S1" "$S2" "$S3"; do
         i=$((i+1))
         MDX_WARP=$impl timeout -s KILL 90 rocprofv3 --pmc $set --kernel-trace -d $out/p$i -o run --output-format csv \
-            -- python3 bench.py --only-roofline --steps 3 --warmup 1 --no-cpu > $out/p$i.json 2> $out/p$i.err
+            -- python3 bench.py --full --only-roofline --steps 3 --warmup 1 --no-cpu > $out/p$i.json 2> $out/p$i.err
         rc=$?; echo "$impl pass $i rc=$rc"
         [ $rc -le 1 ] || break
     done

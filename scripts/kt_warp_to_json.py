@@ -1,4 +1,4 @@
-"""Turn a rocprofv3 --kernel-trace run of `bench.py --only-roofline` into profiles/warp_kernel_trace.json:
+"""Turn a rocprofv3 --kernel-trace run of `bench.py --full --only-roofline` into profiles/warp_kernel_trace.json:
 the average kernel-record duration of the roofline leg's launches (k_warp_prep + k_warp_diff) and of
 the copy-ceiling probe (k_stream3), and the fractions of the 8 TB/s peak they give for the 3 B/px
 algorithmic bytes.

@@ -1,7 +1,7 @@
 """Per-step LK counters from scripts/pmc_lk.sh's passes.
 Usage: python scripts/pmc_lk_to_json.py <dir> [steps covered by the run | auto]
-auto (default): the steps are counted as the 1080p x 32 k_warp_diff launches (one per step; the bench
-also runs its value_unpipelined steps under the profiler)."""
+auto (default): the steps are counted as the 1080p x 32 k_warp_diff launches (one per step; with --full
+the bench also runs its value_unpipelined steps under the profiler)."""
 import csv
 import glob
 import json

@@ -1,4 +1,4 @@
-"""Turn a scripts/pmc_sets.sh run (FETCH_SIZE / WRITE_SIZE passes over `bench.py --only-roofline`)
+"""Turn a scripts/pmc_sets.sh run (FETCH_SIZE / WRITE_SIZE passes over `bench.py --full --only-roofline`)
 into profiles/pmc_warp_diff.json, the per-launch HBM traffic bench.py reports as roofline.traffic.
 
 gfx950 correction (MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports half the bytes of a wide

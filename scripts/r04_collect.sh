@@ -14,9 +14,9 @@ if [ "$part" = a ]; then
     timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
         > $out/pytest_gpu.log 2>&1 || exit 1
     step bench
-    timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || exit 1
+    timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || exit 1
     step profile
-    bash scripts/profile.sh r04 --no-cpu > $out/profile.log 2>&1 || exit 1
+    bash scripts/profile.sh r04 --full --no-cpu > $out/profile.log 2>&1 || exit 1
 else
     step pmc_lk
     bash scripts/pmc_lk.sh > $out/pmc_lk.log 2>&1 || exit 1
@@ -25,14 +25,14 @@ else
     MDX_LK_FLOW=0 BENCH_ARGS="--steps 2 --warmup 1 --no-cpu --no-roofline --no-live --no-4k --no-lk-roofline" \
         bash scripts/pmc_sets.sh step "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_step.log 2>&1 || exit 1
     step pmc_warp
-    BENCH_ARGS="--only-roofline --steps 3 --warmup 1 --no-cpu" \
+    BENCH_ARGS="--full --only-roofline --steps 3 --warmup 1 --no-cpu" \
         bash scripts/pmc_sets.sh warp "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_warp.log 2>&1 || exit 1
     step pmc_warp_counters
     bash scripts/pmc_warp.sh gpurun_out/pmc_warpc > $out/pmc_warpc.log 2>&1 || exit 1
     step warp_kt
     mkdir -p $out/warp_kt
     timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/warp_kt -o run --output-format csv -- python3 bench.py \
-        --only-roofline --steps 20 --warmup 3 --no-cpu > $out/warp_kt/p1.json 2> $out/warp_kt/p1.err || exit 1
+        --full --only-roofline --steps 20 --warmup 3 --no-cpu > $out/warp_kt/p1.json 2> $out/warp_kt/p1.err || exit 1
     step lk_tail
     MDX_LK_DEBUG=1 timeout -k 10 200 python3 scripts/lk_tail.py > $out/lk_tail.txt 2> $out/lk_tail.err || exit 1
     step live_kt

@@ -8,7 +8,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
         v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=${spec#*:}
         tag=$(echo "$spec" | tr ':=,' '___')
         if [ "$v" = head ]; then unset MDX_LIB_PATH; else export MDX_LIB_PATH=$PWD/motion_detection_amd/lib_var/$v/libmdx.so; fi
-        env ${envs//,/ } timeout -k 10 120 python3 bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu --no-live --no-4k \
+        env ${envs//,/ } timeout -k 10 120 python3 bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu --no-live --no-4k \
             --no-roofline --no-lk-roofline --no-ransac ${BENCH_EXTRA} > gpurun_out/ab/$tag.$r.json 2> gpurun_out/ab/$tag.$r.err
         rc=$?
         [ $rc -eq 0 ] || { echo "$spec rc=$rc"; tail -3 gpurun_out/ab/$tag.$r.err; exit $rc; }

@@ -10,24 +10,24 @@ out=gpurun_out/r06; mkdir -p $out
 export TMPDIR=/tmp
 step() { echo "== $1 $(date +%T)"; }
 if [ "$part" = w ]; then   # the warp evidence alone (also in part b)
-    BENCH_ARGS="--only-roofline --roofline-h affine --steps 3 --warmup 1 --roofline-warmup 2 --no-cpu" \
+    BENCH_ARGS="--full --only-roofline --roofline-h affine --steps 3 --warmup 1 --roofline-warmup 2 --no-cpu" \
         bash scripts/pmc_sets.sh warp "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_warp.log 2>&1 || exit 1
     mkdir -p $out/warp_kt $out/warp_kt_proj
     timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/warp_kt -o run --output-format csv -- python3 bench.py \
-        --only-roofline --roofline-h affine --steps 20 --warmup 3 --no-cpu > $out/warp_kt/p1.json 2> $out/warp_kt/p1.err || exit 1
+        --full --only-roofline --roofline-h affine --steps 20 --warmup 3 --no-cpu > $out/warp_kt/p1.json 2> $out/warp_kt/p1.err || exit 1
     timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/warp_kt_proj -o run --output-format csv -- python3 bench.py \
-        --only-roofline --roofline-h projective --steps 20 --warmup 3 --no-cpu > $out/warp_kt_proj/p1.json \
+        --full --only-roofline --roofline-h projective --steps 20 --warmup 3 --no-cpu > $out/warp_kt_proj/p1.json \
         2> $out/warp_kt_proj/p1.err || exit 1
 elif [ "$part" = a ]; then
     step pytest_gpu
     timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
         > $out/pytest_gpu.log 2>&1 || exit 1
     step bench
-    timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || exit 1
+    timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || exit 1
     step smoke
     timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.txt 2>&1 || exit 1
     step profile
-    bash scripts/profile.sh r06 --no-cpu > $out/profile.log 2>&1 || exit 1
+    bash scripts/profile.sh r06 --full --no-cpu > $out/profile.log 2>&1 || exit 1
 else
     step pmc_lk
     bash scripts/pmc_lk.sh > $out/pmc_lk.log 2>&1 || exit 1
@@ -37,17 +37,17 @@ else
     BENCH_ARGS="--steps 2 --warmup 1 --no-cpu --no-roofline --no-live --no-4k --no-ransac --no-lk-roofline" \
         bash scripts/pmc_sets.sh step "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_step.log 2>&1 || exit 1
     step pmc_warp
-    BENCH_ARGS="--only-roofline --roofline-h affine --steps 3 --warmup 1 --roofline-warmup 2 --no-cpu" \
+    BENCH_ARGS="--full --only-roofline --roofline-h affine --steps 3 --warmup 1 --roofline-warmup 2 --no-cpu" \
         bash scripts/pmc_sets.sh warp "FETCH_SIZE" "WRITE_SIZE" > $out/pmc_warp.log 2>&1 || exit 1
     step pmc_warp_counters
     bash scripts/pmc_warp.sh gpurun_out/pmc_warpc > $out/pmc_warpc.log 2>&1 || exit 1
     step warp_kt
     mkdir -p $out/warp_kt
     timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/warp_kt -o run --output-format csv -- python3 bench.py \
-        --only-roofline --roofline-h affine --steps 20 --warmup 3 --no-cpu > $out/warp_kt/p1.json 2> $out/warp_kt/p1.err || exit 1
+        --full --only-roofline --roofline-h affine --steps 20 --warmup 3 --no-cpu > $out/warp_kt/p1.json 2> $out/warp_kt/p1.err || exit 1
     mkdir -p $out/warp_kt_proj
     timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/warp_kt_proj -o run --output-format csv -- python3 bench.py \
-        --only-roofline --roofline-h projective --steps 20 --warmup 3 --no-cpu > $out/warp_kt_proj/p1.json \
+        --full --only-roofline --roofline-h projective --steps 20 --warmup 3 --no-cpu > $out/warp_kt_proj/p1.json \
         2> $out/warp_kt_proj/p1.err || exit 1
     step lk_levels
     mkdir -p $out/seq

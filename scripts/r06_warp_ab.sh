@@ -7,7 +7,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
         v=${spec%%:*}; envs=""; [ "$spec" != "$v" ] && envs=${spec#*:}
         tag=$(echo "$spec" | tr ':=,' '___')
         if [ "$v" = head ]; then unset MDX_LIB_PATH; else export MDX_LIB_PATH=$PWD/motion_detection_amd/lib_var/$v/libmdx.so; fi
-        env ${envs//,/ } timeout -k 10 120 python3 bench.py --only-roofline --roofline-h ${ROOF_H:-affine} --steps 20 \
+        env ${envs//,/ } timeout -k 10 120 python3 bench.py --full --only-roofline --roofline-h ${ROOF_H:-affine} --steps 20 \
             --warmup 3 --no-cpu > gpurun_out/wab/$tag.$r.json 2> gpurun_out/wab/$tag.$r.err
         rc=$?
         [ $rc -eq 0 ] || { echo "$spec rc=$rc"; tail -3 gpurun_out/wab/$tag.$r.err; exit $rc; }

@@ -11,7 +11,7 @@ mkdir -p gpurun_out/wpmc
 for v in head "$@"; do
     if [ "$v" = head ]; then unset MDX_LIB_PATH; else export MDX_LIB_PATH=$PWD/motion_detection_amd/lib_var/$v/libmdx.so; fi
     timeout -s KILL 90 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS --kernel-trace -d gpurun_out/wpmc/$v -o run \
-        --output-format csv -- python3 bench.py --only-roofline --roofline-h affine --steps 3 --warmup 1 --roofline-warmup 2 \
+        --output-format csv -- python3 bench.py --full --only-roofline --roofline-h affine --steps 3 --warmup 1 --roofline-warmup 2 \
         --no-cpu > gpurun_out/wpmc/$v.json 2> gpurun_out/wpmc/$v.err || exit 1
 done
 echo done
