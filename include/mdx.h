@@ -24,13 +24,15 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 4    /* 2: mdx_params.call_pipelining, mdx_input_ready.
+#define MDX_ABI_VERSION 5    /* 2: mdx_params.call_pipelining, mdx_input_ready.
                                 3: mdx_lk_fallbacks; mdx_params grew ransac_iters, ransac_thresh and
                                    ransac_seed (16 more bytes: a caller built against ABI 2 passes a
                                    shorter struct); mdx_sync / mdx_device_sync return MDX_OK after an
                                    LK hand-off that gave up and was recomputed (ABI 2: MDX_EHIP).
                                 4: mdx_abi_version and mdx_params_size: check both at start-up --
-                                   a mismatch means the header and the library differ. */
+                                   a mismatch means the header and the library differ.
+                                5: mdx_debug_warp_paths (a new entry, as 3 and 4 were: nothing existing
+                                   changes, but a caller's header and library must be the same age). */
 
 /* Return codes */
 #define MDX_OK           0
@@ -350,6 +352,14 @@ int mdx_debug_copy(mdx_ctx* ctx, int which, void* dst, size_t bytes);
 /* Test hook: d_out[i] = 32 / d_in[i] through the projective warp's FP64 division (device buffers,
  * queued on the context stream); equal to IEEE division for |d_in[i]| in [2^-100, 2^100]. */
 int mdx_debug_div32(mdx_ctx* ctx, const double* d_in, double* d_out, int n);
+/* Test hook: which rows of k_warp_diff each tile of the context's last warp launch ran (any entry
+ * that produces a mask; the call must have returned MDX_OK).  Waits for the context's stream, then
+ * reads back the per-tile records and fits the kernel itself read and applies the kernel's own
+ * branch conditions.  out[pair * tiles + tile], tiles = ceil(w / 128) * ceil(rows / 64), tile column
+ * fastest: 0 general (per pixel), 1 fixed point, 2 affine FP64, 3 projective, -1 a pair without a
+ * fit.  Writes at most cap codes (out may be NULL when cap is 0) and returns the launch's number of
+ * (pair, tile) records, or a negative error. */
+int mdx_debug_warp_paths(mdx_ctx* ctx, int32_t* out, int cap);
 
 /* Measurement probe, no reference counterpart: the memory ceiling of k_warp_diff's access mix.
  * d_mask[i] = |d_a[i] - d_b[i]| > thresh ? 255 : 0 over n bytes (n a multiple of 16, pointers

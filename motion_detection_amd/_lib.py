@@ -38,9 +38,9 @@ EXPORTED = [
     "mdx_srand", "mdx_rand", "mdx_fit_subspace", "mdx_device_pci", "mdx_build_info",
     "mdx_ring_push", "mdx_ring_trajectory", "mdx_ring_reset", "mdx_input_ready",
     "mdx_host_alloc", "mdx_host_free", "mdx_probe_stream3_dev", "mdx_lk_fallbacks",
-    "mdx_debug_div32", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
+    "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
 ]
-ABI_VERSION = 4   # include/mdx.h MDX_ABI_VERSION
+ABI_VERSION = 5   # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_internal.h", "mdx_api.cpp", "mdx_kernels.hip", "mdx_lk.hip", "mdx_warp.hip",
@@ -165,6 +165,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "mdx_debug_div32"):
         L.mdx_debug_div32.argtypes = [vp, vp, vp, C.c_int]
         L.mdx_debug_div32.restype = C.c_int
+    if hasattr(L, "mdx_debug_warp_paths"):
+        L.mdx_debug_warp_paths.argtypes = [vp, vp, C.c_int]
+        L.mdx_debug_warp_paths.restype = C.c_int
     if hasattr(L, "mdx_lk_fallbacks"):
         L.mdx_lk_fallbacks.argtypes = [vp, C.POINTER(C.c_longlong)]
         L.mdx_lk_fallbacks.restype = C.c_int

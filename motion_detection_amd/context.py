@@ -253,6 +253,15 @@ class Context:
         return self._check(lib().mdx_warp_diff_dev(self._h, batch, C.c_void_p(d_gray1), C.c_void_p(d_gray2), w, h,
                                                    stride, frame_stride, C.c_void_p(d_H), C.c_void_p(d_mask)))
 
+    def debug_warp_paths(self) -> np.ndarray:
+        """Test hook (include/mdx.h mdx_debug_warp_paths): the k_warp_diff row path of every (pair,
+        tile) of this context's last warp launch, after a sync, as a flat int32 array (pair-major,
+        tile column fastest): 0 general, 1 fixed point, 2 affine FP64, 3 projective, -1 no fit."""
+        n = self._check(lib().mdx_debug_warp_paths(self._h, None, 0))
+        out = np.empty(n, np.int32)
+        self._check(lib().mdx_debug_warp_paths(self._h, _ptr(out), n))
+        return out
+
     def probe_stream3_dev(self, n: int, d_a: int, d_b: int, d_mask: int, thresh: int = 190) -> int:
         """Memory-ceiling probe of k_warp_diff's 3 B/px access mix (include/mdx.h)."""
         return self._check(lib().mdx_probe_stream3_dev(self._h, n, C.c_void_p(d_a), C.c_void_p(d_b),

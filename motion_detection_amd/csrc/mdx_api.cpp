@@ -82,6 +82,7 @@ struct mdx_ctx {
     DevBuf straj, sdata, sq, scnt, scols, sres, sout, sbest;      // subspace RANSAC
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
     DevBuf wscr;                             // k_warp_prep's per-pair / per-tile tables
+    WarpLaunch last_warp;                    // the last launch_warp_diff (mdx_debug_warp_paths)
     DevBuf rsc;                              // MDX_FIT_RANSAC scratch (list, hypotheses, counts)
     std::vector<int> ring_order;             // held slots, oldest first
     int ring_cap = 0, ring_w = 0, ring_h = 0, ring_ml = -1;
@@ -958,7 +959,7 @@ static int run_pipeline(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint
         const size_t wsb = warp_scratch_bytes(batch, w, h);
         if ((rc = ensure(c, c->wscr, wsb)) != MDX_OK) return rc;
         HIP_OR_RETURN(c, launch_warp_diff(s, batch, g1, g.img_bytes, L0.pitch, g2, g.img_bytes, L0.pitch, w, h, fits,
-                                          d_mask, (long long)w * h, P.thresh, c->wscr.p, wsb));
+                                          d_mask, (long long)w * h, P.thresh, c->wscr.p, wsb, 0, -1, &c->last_warp));
     }
     if (d_H || d_num) HIP_OR_RETURN(c, launch_export_fit(s, batch, fits, d_H, d_num));
     if (pipe) HIP_OR_RETURN(c, hipEventRecord(c->pyr_free[half], s));
@@ -1468,7 +1469,7 @@ extern "C" int mdx_warp_diff_dev(mdx_ctx* c, int batch, const uint8_t* d_gray1, 
     if ((rc = ensure(c, c->wscr, wsb)) != MDX_OK) return rc;
     HIP_OR_RETURN(c, launch_warp_diff(s, batch, d_gray1, (long long)frame_stride, stride, d_gray2,
                                       (long long)frame_stride, stride, w, h, fits, d_mask, (long long)w * h,
-                                      c->prm.thresh, c->wscr.p, wsb));
+                                      c->prm.thresh, c->wscr.p, wsb, 0, -1, &c->last_warp));
     mark(c, 6);
     return MDX_OK;
 }
@@ -1538,7 +1539,8 @@ extern "C" int mdx_band_fit_warp_dev(mdx_ctx* c, int nrec, const mdx_band_cand* 
     const size_t wsb = warp_scratch_bytes(1, w, y1 - y0);
     if (const int erc = ensure(c, c->wscr, wsb); erc != MDX_OK) return erc;
     HIP_OR_RETURN(c, launch_warp_diff(s, 1, g1, g.img_bytes, L0.pitch, g2, g.img_bytes, L0.pitch, w, h, fits, d_mask_band,
-                                      (long long)w * (y1 - y0), c->prm.thresh, c->wscr.p, wsb, y0, y1));
+                                      (long long)w * (y1 - y0), c->prm.thresh, c->wscr.p, wsb, y0, y1,
+                                      &c->last_warp));
     if (d_H || d_num_vectors) HIP_OR_RETURN(c, launch_export_fit(s, 1, fits, d_H, d_num_vectors));
     // the band's pyramids have been read: the pipelined call two calls on may overwrite them
     if (c->prm.call_pipelining) HIP_OR_RETURN(c, hipEventRecord(c->pyr_free[c->band_half], s));
@@ -1579,6 +1581,16 @@ extern "C" int mdx_debug_div32(mdx_ctx* c, const double* d_in, double* d_out, in
     HIP_OR_RETURN(c, hipSetDevice(c->device));
     HIP_OR_RETURN(c, launch_div32(c->stream, d_in, d_out, n));
     return MDX_OK;
+}
+
+extern "C" int mdx_debug_warp_paths(mdx_ctx* c, int32_t* out, int cap)
+{
+    if (!c || cap < 0 || (cap > 0 && !out)) return MDX_EINVAL;
+    const WarpLaunch& L = c->last_warp;
+    if (L.batch <= 0) return set_err(c, MDX_EINVAL, "mdx_debug_warp_paths: no warp launch on this context yet");
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    HIP_OR_RETURN(c, debug_warp_paths(c->stream, L, out, cap));
+    return L.batch * L.ntiles;
 }
 
 extern "C" void* mdx_host_alloc(size_t bytes)

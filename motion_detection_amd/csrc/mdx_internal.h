@@ -283,10 +283,22 @@ hipError_t launch_set_fit_external(hipStream_t s, int batch, const double* H_ext
 // scratch: warp_scratch_bytes(batch, w, rows of the band) of device memory for the per-pair and
 // per-tile tables of k_warp_prep (the launch's own; reused by the next launch on the stream)
 size_t warp_scratch_bytes(int batch, int w, int rows);
+// What a launch_warp_diff handed k_warp_diff, kept by the context for the path report
+// (mdx_debug_warp_paths): the workgroup-uniform fast-path inputs and the device tables.
+struct WarpLaunch {
+    int batch = 0, ntiles = 0;   // pairs, tiles per pair (tile column fastest); batch 0: no launch yet
+    int bw0 = 0, vec_ok = 0;
+    const PairFit* fits = nullptr;
+    const void* tinfo = nullptr;   // TileInfo[batch][ntiles] inside the launch's scratch
+};
 hipError_t launch_warp_diff(hipStream_t s, int batch, const uint8_t* g1, long long g1_stride, int g1_pitch,
                             const uint8_t* g2, long long g2_stride, int g2_pitch, int w, int h,
                             const PairFit* fits, uint8_t* mask, long long mask_stride, int thresh, void* scratch,
-                            size_t scratch_bytes, int row0 = 0, int row1 = -1);
+                            size_t scratch_bytes, int row0 = 0, int row1 = -1, WarpLaunch* rec = nullptr);
+// Test hook: the row path of every (pair, tile) of launch L, from the TileInfo records and fits its
+// k_warp_diff read; out[pair * ntiles + tile] = 0 general, 1 fixed point, 2 affine FP64,
+// 3 projective, -1 pair without a fit.  Waits for the stream.  At most cap codes are written.
+hipError_t debug_warp_paths(hipStream_t s, const WarpLaunch& L, int32_t* out, int cap);
 hipError_t launch_div32(hipStream_t s, const double* in, double* out, int n);   // test hook
 hipError_t launch_stream3(hipStream_t s, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* o, int thresh);
 hipError_t launch_export_fit(hipStream_t s, int batch, const PairFit* fits, double* H, int* num_vectors);

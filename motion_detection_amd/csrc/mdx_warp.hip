@@ -38,8 +38,9 @@
 //     into the four 0x00/0xff mask bytes.
 //   * gray2 loads / mask stores go through buffer descriptors: lanes past the right edge get an
 //     out-of-range offset and rows past the band fall outside the mask descriptor, so the row
-//     loop is branch-free.  ~17 VALU per pixel (4 of them FP64), vs ~23 for the 64x128-tile
-//     design before it (rocprofv3 SQ_INSTS_VALU).
+//     loop is branch-free.  60 VALU per row of four pixels in the ISA of the fixed-point rows
+//     (the FP64 rows here were ~17 per pixel, 4 of them FP64, vs ~23 for the
+//     64x128-tile design before it: rocprofv3 SQ_INSTS_VALU).
 // Projective M (M6 or M7 != 0, e.g. every non-degenerate first-4 fit) takes the same tiles: the
 // tile's footprint is the bounding box of its reference blocks' corner images (the homography maps
 // the tile to a convex quadrilateral when W keeps one sign over it) widened by one pixel for the
@@ -50,6 +51,8 @@
 #include "mdx_internal.h"
 
 #include <limits.h>
+
+#include <vector>
 
 namespace mdx {
 
@@ -108,6 +111,33 @@ struct TileInfo {
     int sxa, sya;      // staged origin (sxa multiple of 16)
     int sw, sh;        // staged width (bytes), height (rows)
 };
+
+// Which rows a tile runs, written once for k_warp_diff and for the path report (debug_warp_paths):
+// general unless the launch allows the fast path (dword-aligned rows, reference blocks of 64: uniform
+// per launch) and the tile's TileInfo does; then fixed point when 32/M8 is a power of two
+// ((X0 + M0*x1) * Wd exact), else the affine FP64 rows, else (M6 or M7 != 0) the projective rows.
+enum { kPathGeneral = 0, kPathFixed = 1, kPathAffine = 2, kPathProjective = 3 };
+__host__ __device__ __forceinline__ bool warp_is_affine(const double* M)
+{
+    return (M[6] == 0.0) && (M[7] == 0.0);
+}
+__host__ __device__ __forceinline__ bool warp_try_fast(int bw0, int vec_ok)
+{
+    return bw0 == kBW && vec_ok;
+}
+__host__ __device__ __forceinline__ bool warp_is_pow2(bool affine, double Wd)
+{
+    return affine && Wd != 0.0 && (__builtin_bit_cast(long long, Wd) & 0x000fffffffffffffLL) == 0;
+}
+__host__ __device__ __forceinline__ bool warp_tile_fast(bool try_fast, int tile_fast)
+{
+    return try_fast && tile_fast;
+}
+// the order in which k_warp_diff tests them at its two branches (general; then pow2, affine, else)
+__host__ __device__ __forceinline__ int warp_path(bool fast, bool affine, bool pow2)
+{
+    return !fast ? kPathGeneral : pow2 ? kPathFixed : affine ? kPathAffine : kPathProjective;
+}
 
 // Bounds of the tile's taps, from the reference arithmetic at the corners of its (one or two)
 // reference blocks, one corner per lane of an aligned group of 8 (lane = its index in the group;
@@ -666,10 +696,10 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
         return;
     }
     const uint8_t* src = g1 + (long long)pair * g1_stride;
-    const bool affine = (M[6] == 0.0) && (M[7] == 0.0);
+    const bool affine = warp_is_affine(M);
     // fast path only over dword-aligned rows with reference blocks of 64 (uniform per workgroup)
-    const bool try_fast = bw0 == kBW && vec_ok;
-    if (!try_fast || !t.fast) {
+    const bool try_fast = warp_try_fast(bw0, vec_ok);
+    if (!warp_tile_fast(try_fast, t.fast)) {
         // ---- general path: per pixel, global gathers
         const int nx = max(0, min(4, w - xs));
         for (int r = r0; r < kTH && y0 + r < row1; r += 8) {
@@ -684,7 +714,7 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
     // ---- fast path
     const double Wd = t.wd;
     // 32/M8 a power of two -> (X0 + M0*x1) * Wd is exact: the fixed-point rows (warp_rows_fx)
-    const bool pow2 = affine && Wd != 0.0 && (__double_as_longlong(Wd) & 0x000fffffffffffffLL) == 0;
+    const bool pow2 = warp_is_pow2(affine, Wd);
     if (affine && !pow2 && tid < 32) {
         s_tab[2 * tid] = (uint32_t)(32 - tid) | ((uint32_t)tid << 16);
         s_tab[2 * tid + 1] = (uint32_t)(64 * (32 - tid)) | ((uint32_t)(64 * tid) << 16);
@@ -844,8 +874,9 @@ size_t warp_scratch_bytes(int batch, int w, int rows)
 hipError_t launch_warp_diff(hipStream_t s, int batch, const uint8_t* g1, long long g1_stride, int g1_pitch,
                             const uint8_t* g2, long long g2_stride, int g2_pitch, int w, int h, const PairFit* fits,
                             uint8_t* mask, long long mask_stride, int thresh, void* scratch, size_t scratch_bytes,
-                            int row0, int row1)
+                            int row0, int row1, WarpLaunch* rec)
 {
+    if (rec) *rec = WarpLaunch();
     if (row1 < 0) row1 = h;
     if (row0 < 0 || row1 > h || row0 >= row1) return hipErrorInvalidValue;
     if (!scratch || scratch_bytes < warp_scratch_bytes(batch, w, row1 - row0)) return hipErrorInvalidValue;
@@ -863,7 +894,40 @@ hipError_t launch_warp_diff(hipStream_t s, int batch, const uint8_t* g1, long lo
     hipLaunchKernelGGL(k_warp_diff, grid, dim3(256), 0, s, g1, g1_stride, g1_pitch, g2, g2_stride, g2_pitch, w, h, bw0,
                        fits, mask, mask_stride, thresh, vec_ok, row0, row1, tinfo, prep, udiv_magic_of((uint32_t)ntiles),
                        udiv_magic_of(grid.x));
+    if (rec) {
+        rec->batch = batch;
+        rec->ntiles = ntiles;
+        rec->bw0 = bw0;
+        rec->vec_ok = vec_ok;
+        rec->fits = fits;
+        rec->tinfo = tinfo;
+    }
     return hipGetLastError();
+}
+
+// Test hook (mdx_debug_warp_paths): the launch's TileInfo records and fits, copied back once the
+// stream has drained, through the kernel's own branch conditions.
+hipError_t debug_warp_paths(hipStream_t s, const WarpLaunch& L, int32_t* out, int cap)
+{
+    const size_t n = (size_t)L.batch * L.ntiles;
+    std::vector<TileInfo> ti(n);
+    std::vector<PairFit> fits(L.batch);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(ti.data(), L.tinfo, n * sizeof(TileInfo), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(fits.data(), L.fits, fits.size() * sizeof(PairFit), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    const bool try_fast = warp_try_fast(L.bw0, L.vec_ok);
+    for (size_t i = 0; i < n && i < (size_t)cap; i++) {
+        const PairFit& f = fits[i / L.ntiles];
+        if (f.fit_status != 0) {       // no fit: the tile's TileInfo was not written, its mask is all zero
+            out[i] = -1;
+            continue;
+        }
+        const TileInfo& t = ti[i];
+        const bool affine = warp_is_affine(f.Hinv);
+        out[i] = warp_path(warp_tile_fast(try_fast, t.fast), affine, warp_is_pow2(affine, t.wd));
+    }
+    return hipSuccess;
 }
 
 // Test hook (mdx_debug_div32): div32 over n values.

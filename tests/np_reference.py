@@ -374,9 +374,9 @@ def invert3x3(M):
     return np.array(t).reshape(3, 3)
 
 
-def warp_perspective(src: np.ndarray, Minv: np.ndarray) -> np.ndarray:
-    """warpPerspective with an already-inverted matrix (block origin xb, FP64, 1/32 px)."""
-    h, w = src.shape
+def warp_coords(w: int, h: int, Minv: np.ndarray):
+    """The (h, w) int64 1/32-px source coordinates X, Y warpPerspective rounds for every destination
+    pixel (block origin xb, FP64, clamped to int)."""
     M = np.asarray(Minv, dtype=np.float64).ravel()
     bh0 = min(16, h)
     bw0 = min(1024 // bh0, w)
@@ -390,10 +390,20 @@ def warp_perspective(src: np.ndarray, Minv: np.ndarray) -> np.ndarray:
     Wd = W0 + M[6] * x1
     with np.errstate(divide="ignore"):
         Wd = np.where(Wd != 0, 32.0 / np.where(Wd != 0, Wd, 1.0), 0.0)
-    fX = np.clip((X0 + M[0] * x1) * Wd, -2.0**31, 2.0**31 - 1)
-    fY = np.clip((Y0 + M[3] * x1) * Wd, -2.0**31, 2.0**31 - 1)
-    X = np.rint(fX).astype(np.int64)
-    Y = np.rint(fY).astype(np.int64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        fX = np.clip((X0 + M[0] * x1) * Wd, -2.0**31, 2.0**31 - 1)
+        fY = np.clip((Y0 + M[3] * x1) * Wd, -2.0**31, 2.0**31 - 1)
+    return np.rint(fX).astype(np.int64), np.rint(fY).astype(np.int64)
+
+
+def warp_perspective(src: np.ndarray, Minv: np.ndarray, offset=(0, 0)) -> np.ndarray:
+    """warpPerspective with an already-inverted matrix (block origin xb, FP64, 1/32 px).  offset
+    (ex, ey) is added to every pixel's rounded X, Y: a deliberately wrong warp, for measuring how
+    sensitive a check of the warp is (tests/test_warp_probe.py); (0, 0) is the reference."""
+    h, w = src.shape
+    X, Y = warp_coords(w, h, Minv)
+    X = X + int(offset[0])
+    Y = Y + int(offset[1])
     sx = np.clip(X >> 5, -32768, 32767)
     sy = np.clip(Y >> 5, -32768, 32767)
     fx, fy = X & 31, Y & 31

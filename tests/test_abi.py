@@ -90,6 +90,7 @@ def test_null_context_is_einval(mdx):
     p = buf.ctypes.data_as(C.c_void_p)
     assert L.mdx_flow_warp_diff(None, p, p, 4, 4, 4, 0, None, None, None, None, None, None, None) == _lib.MDX_EINVAL
     assert L.mdx_warp_diff_dev(None, 1, p, p, 4, 4, 4, 16, p, p) == _lib.MDX_EINVAL
+    assert L.mdx_debug_warp_paths(None, None, 0) == _lib.MDX_EINVAL
 
 
 def test_create_rejects_bad_params(mdx):
