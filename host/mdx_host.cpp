@@ -169,7 +169,11 @@ void MotionDetectionNode::run_live(int nimg, FrameResult* r)
     publish(kTopicFlowMarkers, flow_image(last_rgb_, r->vector_image, ps, p_.min_vector_size));   // (not :101-103's arrows)
     r->outlier_points.clear();
     r->subspace_columns.clear();
-    if (r->trajectories.empty() || !p_.egomotion) return;       // :296-318 / :357-389 (clustering: out of scope)
+    r->num_clusters = 0;
+    r->cluster_labels.clear();
+    r->kept_clusters.clear();
+    r->rectangles.clear();
+    if (r->trajectories.empty() || !p_.egomotion) return;       // :296-318 / :357-389 (getClusters: out of scope)
     const int nt = (int)r->trajectories.size(), d = 4 * p_.num_motions;
     std::vector<float> flat((size_t)nt * nimg * 2);
     for (int i = 0; i < nt; i++) std::memcpy(&flat[(size_t)i * nimg * 2], r->trajectories[i].data(), (size_t)nimg * 8);
@@ -182,6 +186,20 @@ void MotionDetectionNode::run_live(int nimg, FrameResult* r)
     r->outlier_points.assign(outl.begin(), outl.begin() + 2 * nout);
     for (int c : cols)
         if (c >= 0) r->subspace_columns.push_back(c);
+    if (!(p_.distance_threshold > 0)) return;
+    // clusterEuclidean(outlier_points, distance_threshold) (:355) and each kept cluster's
+    // boundingRect (optical_flow_visualizer.cpp:230-236); a kept cluster has more than 5 points
+    const int max_kept = nout / 6;
+    int nkept = 0;
+    r->cluster_labels.assign(nout, 0);
+    r->kept_clusters.assign(max_kept, 0);
+    r->rectangles.assign((size_t)4 * max_kept, 0);
+    const int crc = mdx_cluster_euclidean(ctx_, r->outlier_points.data(), nout, p_.distance_threshold, 5,
+                                          r->cluster_labels.data(), &r->num_clusters, r->kept_clusters.data(),
+                                          r->rectangles.data(), max_kept, &nkept);
+    if (crc < 0) throw std::runtime_error(std::string("mdx_cluster_euclidean: ") + mdx_last_error(ctx_));
+    r->kept_clusters.resize(nkept);
+    r->rectangles.resize((size_t)4 * nkept);
 }
 
 Image mask_image(const std::vector<uint8_t>& mask, int w, int h)

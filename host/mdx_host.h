@@ -4,8 +4,8 @@
 // it subscribes sensor_msgs/Image on ~input_image (:63), keeps a ring of the last
 // trajectory_size frames (:237-261), converts them with cv_bridge::toCvCopy(msg, "rgb8") (:271) and
 // runs either runOpticalFlow (:76-92, the pair path with the motion mask -- compiled but only
-// reachable from commented-out code) or runOpticalFlowTrajectory + fitSubspace (:94-110, :341-348,
-// the live path), then publishes RGB8 images (publishImage, :217-223).  This header restates that
+// reachable from commented-out code) or runOpticalFlowTrajectory + fitSubspace + clusterEuclidean
+// (:94-110, :341-355, the live path), then publishes RGB8 images (publishImage, :217-223).  This header restates that
 // caller without ROS or OpenCV: messages are plain structs, publishing is a callback, and every
 // per-pixel step goes through libmdx.so.  No Python anywhere on this path.
 #ifndef MDX_HOST_H_
@@ -53,6 +53,10 @@ struct Params {
     bool live_path = true;
     uint32_t seed = 1;             // the reference seeds rand() with time(NULL) (outlier_detector.cpp:17)
     int subspace_precision = MDX_SUBSPACE_F64;   // or MDX_SUBSPACE_F32 (the reference's float shape)
+    // clusterEuclidean's threshold (node.cpp:320-321, :355; no default there, the launch files set
+    // it).  0: the clustering stage is off
+    double distance_threshold = 0;
+    bool log_contours = false;     // node.cpp:39: log each kept cluster's rectangle (mdx_node: motion.log)
 };
 
 // One processed frame's outputs (what the node hands to its publishers / logs).
@@ -71,6 +75,11 @@ struct FrameResult {
     std::vector<std::vector<float>> trajectories;   // complete ones, (x, y) * traj_size each
     std::vector<float> outlier_points;              // fitSubspace's outlier_points, (x, y) each
     std::vector<int> subspace_columns;              // indices (into trajectories) of the winning sample
+    // clusterEuclidean on outlier_points (:355), when egomotion and distance_threshold > 0
+    int num_clusters = 0;                           // all clusters, kept or not
+    std::vector<int32_t> cluster_labels;            // per outlier point: its cluster among all, creation order
+    std::vector<int32_t> kept_clusters;             // ids of the clusters with more than 5 points
+    std::vector<int32_t> rectangles;                // x, y, w, h of each kept cluster's boundingRect
 };
 
 using Publisher = std::function<void(const std::string& topic, const Image& msg)>;

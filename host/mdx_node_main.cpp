@@ -4,6 +4,8 @@
 //   mdx_node <frames.bin> <outdir> [pixel_step=10] [min_vector_size=1.0] [skip_frames=1]
 //            [num_motions=2] [egomotion=1] [live_path=1] [sigma=0.5] [seed=1] [device=0]
 //            [subspace_precision=0]   (0 double, 1 the reference's float arithmetic shape)
+//            [distance_threshold=0]   (clusterEuclidean's threshold; 0: no clustering)
+//            [log_contours=0]
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -15,12 +17,19 @@
 //                                 i32 ncols, i32 columns[ncols]
 //   flow_<k>_h, flow_<k>_f        writeFlow of the node's vector image (optical_flow_calculator.cpp:509)
 //   traj_<k>                      writeTrajectories (live path, :543)
-// (The reference's MotionLogger logs the live branch's cluster rectangles, node.cpp:431-434; the
-// clustering is out of scope, so no motion.log is written.)
+//   clusters_<k>.bin              live path with egomotion and distance_threshold > 0: i32 num_all,
+//                                 num_kept; i32 labels[nout]; i32 kept[num_kept]; i32 rects[num_kept][4]
+//                                 (x, y, width, height)
+//   motion.log                    log_contours=1: created at start; MotionLogger::writeBoundingBox of
+//                                 every kept cluster's rectangle (node.cpp:431-434), "frame, id, tl.x,
+//                                 tl.y, br.x, br.y" with frame = the node's global_frame_count_ during
+//                                 that callback and id the index among the kept clusters.  (writeContour,
+//                                 :426-429, needs the convex hulls, which are out of scope.)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -89,6 +98,8 @@ int main(int argc, char** argv)
         p.sigma = std::atof(get("sigma", "0.5").c_str());
         p.seed = (uint32_t)std::strtoul(get("seed", "1").c_str(), nullptr, 10);
         p.subspace_precision = std::atoi(get("subspace_precision", "0").c_str());
+        p.distance_threshold = std::atof(get("distance_threshold", "0").c_str());
+        p.log_contours = std::atoi(get("log_contours", "0").c_str()) != 0;
         const int device = std::atoi(get("device", "0").c_str());
         const std::string out = argv[2];
         const std::vector<Image> frames = read_frames(argv[1]);
@@ -99,6 +110,9 @@ int main(int argc, char** argv)
             write_bytes(out + "/pub_" + std::to_string(k) + "_" + topic + ".rgb8", im.data.data(), im.data.size());
         };
         MotionDetectionNode node(p, device, (int)frames[0].width, (int)frames[0].height, pub);
+        std::unique_ptr<MotionLogger> ml;
+        if (p.log_contours) ml.reset(new MotionLogger(out + "/motion.log"));
+        const bool clustering = p.live_path && p.egomotion && p.distance_threshold > 0;
         for (size_t fi = 0; fi < frames.size(); fi++) {
             FrameResult r;
             if (!node.image_callback(frames[fi], &r)) continue;
@@ -119,6 +133,21 @@ int main(int argc, char** argv)
                 put(&nc, 4);
                 put(r.subspace_columns.data(), r.subspace_columns.size() * 4);
                 write_trajectories(r.trajectories, out + "/traj_" + std::to_string(k));
+            }
+            if (clustering) {
+                const int32_t chdr[2] = {r.num_clusters, (int32_t)r.kept_clusters.size()};
+                std::vector<uint8_t> cb((const uint8_t*)chdr, (const uint8_t*)chdr + sizeof(chdr));
+                auto cput = [&](const void* q, size_t n) { cb.insert(cb.end(), (const uint8_t*)q, (const uint8_t*)q + n); };
+                cput(r.cluster_labels.data(), r.cluster_labels.size() * 4);
+                cput(r.kept_clusters.data(), r.kept_clusters.size() * 4);
+                cput(r.rectangles.data(), r.rectangles.size() * 4);
+                write_bytes(out + "/clusters_" + std::to_string(k) + ".bin", cb.data(), cb.size());
+                // the callback's global_frame_count_ (node.cpp:433), before its closing increment (:454)
+                const int frame = (int)node.global_frame_count() - 1;
+                if (ml)
+                    for (size_t i = 0; i < r.kept_clusters.size(); i++)
+                        ml->write_bounding_box(r.rectangles[4 * i], r.rectangles[4 * i + 1], r.rectangles[4 * i + 2],
+                                               r.rectangles[4 * i + 3], frame, (int)i);
             }
             write_bytes(out + "/res_" + std::to_string(k) + ".bin", buf.data(), buf.size());
             write_flow(r.vector_image, r.w, r.h, p.pixel_step, out + "/flow_" + std::to_string(k));

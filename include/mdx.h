@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 5    /* 2: mdx_params.call_pipelining, mdx_input_ready.
+#define MDX_ABI_VERSION 6    /* 2: mdx_params.call_pipelining, mdx_input_ready.
                                 3: mdx_lk_fallbacks; mdx_params grew ransac_iters, ransac_thresh and
                                    ransac_seed (16 more bytes: a caller built against ABI 2 passes a
                                    shorter struct); mdx_sync / mdx_device_sync return MDX_OK after an
@@ -32,7 +32,8 @@ extern "C" {
                                 4: mdx_abi_version and mdx_params_size: check both at start-up --
                                    a mismatch means the header and the library differ.
                                 5: mdx_debug_warp_paths (a new entry, as 3 and 4 were: nothing existing
-                                   changes, but a caller's header and library must be the same age). */
+                                   changes, but a caller's header and library must be the same age).
+                                6: mdx_cluster_euclidean (a new entry; mdx_params is unchanged, 80 bytes). */
 
 /* Return codes */
 #define MDX_OK           0
@@ -322,6 +323,38 @@ int  mdx_rand(mdx_rand_state* st);
 int  mdx_fit_subspace(mdx_ctx* ctx, const float* traj, int ntraj, int traj_len, int num_motions, double sigma,
                       mdx_rand_state* rng, int* columns, uint8_t* is_outlier, double* residuals,
                       float* outlier_points, int* n_outliers);
+
+/*
+ * Greedy Euclidean clustering and bounding rectangles: replaces FlowClusterer::clusterEuclidean
+ * (common/src/flow_clusterer.cpp:231-269), which the node runs on fitSubspace's outlier_points
+ * (motion_detection_node.cpp:355), and boundingRect of each kept cluster
+ * (optical_flow_visualizer.cpp:230-236).  Restated from the source; unpinned against a real build
+ * (no OpenCV 2.4 to compare with): copyTo's converting path and boundingRect in particular.
+ *   Points are visited in input order.  Point i joins the cluster whose nearest member is nearest
+ *   (strict <: the earliest-created cluster on a tie) when that distance d < distance_threshold
+ *   (double compare; d = sqrt((double)s), s = dx*dx + dy*dy in float, each operation rounded,
+ *   point_cluster.cpp:63-66), else it starts a new cluster.  Clusters never merge.  Kept clusters:
+ *   size > min_size (:263).  Rectangle: the members converted with cvRound (round half to even),
+ *   then (xmin, ymin, xmax - xmin + 1, ymax - ymin + 1); coordinates beyond +-2^30 give unspecified
+ *   rectangles.
+ *   points [npoints][2] float host, input order.
+ * Outputs (any may be NULL):
+ *   labels   [npoints] index of the point's cluster among ALL clusters, creation order
+ *   num_all  number of all clusters
+ *   kept     [<= max_kept] ids (into the above) of clusters with size > min_size, ascending
+ *   rects    [<= max_kept][4] x, y, width, height of each kept cluster
+ *   num_kept number of kept clusters (may exceed max_kept; only max_kept are written)
+ * npoints == 0 is MDX_OK with zero clusters.  MDX_EINVAL: npoints or max_kept negative, npoints >
+ * MDX_CLUSTER_MAX_POINTS, points NULL with npoints > 0, a non-finite coordinate (the reference's
+ * behaviour there is an accident of NaN compares), a NaN distance_threshold.  A threshold <= 0 is
+ * valid: every point is its own cluster.  All pair distances are computed on the device
+ * (ceil(npoints / 256) launches); cluster sizes, ranks and rectangles are O(npoints) on the host
+ * after the call's one synchronising copy.  Synchronous.
+ */
+#define MDX_CLUSTER_MAX_POINTS 262144
+int mdx_cluster_euclidean(mdx_ctx* ctx, const float* points, int npoints, double distance_threshold,
+                          int min_size /* reference: 5 */, int32_t* labels, int* num_all,
+                          int32_t* kept, int32_t* rects, int max_kept, int* num_kept);
 
 /* Page-locked host memory for frames and outputs (e.g. the node's rgb8 staging buffer and its
  * trajectory outputs): copies between it and the device run as DMA at full link rate, while a

@@ -26,6 +26,7 @@ MDX_EDEGENERATE = 1
 FMT_GRAY8, FMT_RGB8, FMT_BGR8 = 0, 1, 2
 FIT_FIRST4, FIT_EXTERNAL, FIT_RANSAC = 0, 1, 2
 SUBSPACE_F64, SUBSPACE_F32 = 0, 1
+CLUSTER_MAX_POINTS = 262144   # include/mdx.h MDX_CLUSTER_MAX_POINTS
 
 # every symbol include/mdx.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -39,12 +40,13 @@ EXPORTED = [
     "mdx_ring_push", "mdx_ring_trajectory", "mdx_ring_reset", "mdx_input_ready",
     "mdx_host_alloc", "mdx_host_free", "mdx_probe_stream3_dev", "mdx_lk_fallbacks",
     "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
+    "mdx_cluster_euclidean",
 ]
-ABI_VERSION = 5   # include/mdx.h MDX_ABI_VERSION
+ABI_VERSION = 6   # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_internal.h", "mdx_api.cpp", "mdx_kernels.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_subspace.hip", "mdx_cluster.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -220,6 +222,9 @@ def lib() -> C.CDLL:
     L.mdx_fit_subspace.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(MdxRandState), vp, vp, vp,
                                    vp, C.POINTER(C.c_int)]
     L.mdx_fit_subspace.restype = C.c_int
+    L.mdx_cluster_euclidean.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, vp, C.POINTER(C.c_int), vp, vp, C.c_int,
+                                        C.POINTER(C.c_int)]
+    L.mdx_cluster_euclidean.restype = C.c_int
     _lib = L
     return L
 

@@ -65,6 +65,15 @@ class SubspaceResult:
     outlier_points: np.ndarray  # (n_outliers, 2) float32: each outlier's second-to-last point
 
 
+@dataclass
+class ClusterResult:
+    labels: np.ndarray          # (npoints,) int32: the point's cluster among all clusters, creation order
+    num_all: int                # number of all clusters
+    kept: np.ndarray            # (num_kept,) int32: ids of the clusters with size > min_size, ascending
+    rects: np.ndarray           # (num_kept, 4) int32: x, y, width, height of each kept cluster (cv::Rect)
+    num_kept: int = 0           # all kept clusters, also when max_kept cut kept / rects short
+
+
 class Context:
     """One device context (mdx_ctx): workspace sized at creation, one HIP stream."""
 
@@ -237,6 +246,24 @@ class Context:
         self._check(lib().mdx_fit_subspace(self._h, _ptr(traj), N, T, int(num_motions), float(sigma), C.byref(rng),
                                            _ptr(cols), _ptr(out), _ptr(res), _ptr(pts), C.byref(nout)))
         return SubspaceResult(cols, out, res, pts[:nout.value].copy())
+
+    # -- greedy Euclidean clustering (drop-in for FlowClusterer::clusterEuclidean + boundingRect)
+    def cluster_euclidean(self, points: np.ndarray, distance_threshold: float, min_size: int = 5,
+                          max_kept: int | None = None) -> "ClusterResult":
+        """max_kept (default: every kept cluster) caps how many kept ids / rectangles are returned."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        # a kept cluster has more than min_size points
+        cap = n // (max(int(min_size), 0) + 1) if max_kept is None else int(max_kept)
+        labels = np.zeros(n, np.int32)
+        kept = np.zeros(max(cap, 0), np.int32)
+        rects = np.zeros((max(cap, 0), 4), np.int32)
+        nall, nkept = C.c_int(0), C.c_int(0)
+        self._check(lib().mdx_cluster_euclidean(self._h, _ptr(pts), n, float(distance_threshold), int(min_size),
+                                                _ptr(labels), C.byref(nall), _ptr(kept), _ptr(rects), cap,
+                                                C.byref(nkept)))
+        m = min(nkept.value, cap)
+        return ClusterResult(labels, nall.value, kept[:m].copy(), rects[:m].copy(), nkept.value)
 
     # -- device entries (pointers are ints, e.g. torch.Tensor.data_ptr())
     def flow_warp_diff_batch_dev(self, batch: int, d_img1: int, d_img2: int, w: int, h: int, stride: int,

@@ -8,6 +8,7 @@
 #include "mdx_internal.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -80,6 +81,8 @@ struct mdx_ctx {
     DevBuf csum;                             // classify: per-block summaries
     DevBuf tin, tcur, tnp, tst, ttraj, tnum, tflag;   // trajectory tracking (ttraj: the four outputs, one block)
     DevBuf straj, sdata, sq, scnt, scols, sres, sout, sbest;      // subspace RANSAC
+    DevBuf clpts, clbest, clroot;            // clusterEuclidean: points, running keys, roots
+    std::vector<int32_t> cl_host;            // its host side (roots, ranks, sizes, boxes): only ever grows
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
     DevBuf wscr;                             // k_warp_prep's per-pair / per-tile tables
     WarpLaunch last_warp;                    // the last launch_warp_diff (mdx_debug_warp_paths)
@@ -507,6 +510,7 @@ extern "C" int mdx_destroy(mdx_ctx* c)
                       &c->cls, &c->Abuf, &c->ctab, &c->dbg, &c->csum, &c->tin, &c->tcur, &c->tnp, &c->tst,
                       &c->ttraj, &c->tnum, &c->tflag, &c->straj, &c->sdata, &c->sq,
                       &c->scnt, &c->scols, &c->sres, &c->sout, &c->sbest, &c->ring_pyr, &c->ring_der, &c->rin,
+                      &c->clpts, &c->clbest, &c->clroot,
                       &c->errw, &c->wscr, &c->rsc};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -1447,6 +1451,94 @@ extern "C" int mdx_fit_subspace(mdx_ctx* c, const float* traj, int ntraj, int tr
             for (int k = 0; k < d; k++) columns[k] = -1;
     }
     if (n_outliers) *n_outliers = nout;
+    return MDX_OK;
+}
+
+// clusterEuclidean (flow_clusterer.cpp:231-269) + boundingRect per kept cluster
+// (optical_flow_visualizer.cpp:230-236).  The O(N^2) key minimisation runs on the device
+// (mdx_cluster.hip) and leaves root[i], the first point of i's cluster; everything after it is O(N)
+// and runs here, after the one copy that brings root[] back.
+extern "C" int mdx_cluster_euclidean(mdx_ctx* c, const float* points, int npoints, double thr, int min_size,
+                                     int32_t* labels, int* num_all, int32_t* kept, int32_t* rects, int max_kept,
+                                     int* num_kept)
+{
+    if (!c) return MDX_EINVAL;
+    if (npoints < 0 || max_kept < 0 || (npoints > 0 && !points))
+        return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: bad argument");
+    if (npoints > MDX_CLUSTER_MAX_POINTS)
+        return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: more than %d points", MDX_CLUSTER_MAX_POINTS);
+    if (std::isnan(thr)) return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: distance_threshold is NaN");
+    for (size_t i = 0; i < (size_t)2 * npoints; i++)
+        if (!std::isfinite(points[i]))
+            return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: point %zu has a non-finite coordinate", i / 2);
+    if (num_all) *num_all = 0;
+    if (num_kept) *num_kept = 0;
+    if (npoints == 0) return MDX_OK;
+    // the threshold test sqrt((double)s) < thr as s <= s*: s* = the largest float that passes (sqrt
+    // is monotonic, so every smaller s passes too); slim = bits(s*) + 1, 0 when not even s = 0 passes
+    uint32_t slim = 0;
+    if (thr > 0.0) {
+        float f = (float)std::min(thr * thr, (double)FLT_MAX);
+        while (f < FLT_MAX && std::sqrt((double)std::nextafterf(f, INFINITY)) < thr) f = std::nextafterf(f, INFINITY);
+        while (f > 0.f && !(std::sqrt((double)f) < thr)) f = std::nextafterf(f, 0.f);
+        if (std::sqrt((double)f) < thr) {
+            std::memcpy(&slim, &f, 4);
+            slim += 1;
+        }
+    }
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const size_t N = (size_t)npoints;
+    int rc;
+    if ((rc = ensure(c, c->clpts, N * 8)) != MDX_OK) return rc;
+    if ((rc = ensure(c, c->clbest, N * 8)) != MDX_OK) return rc;
+    if ((rc = ensure(c, c->clroot, N * 4)) != MDX_OK) return rc;
+    if (c->cl_host.size() < 7 * N) c->cl_host.resize(7 * N);
+    int32_t* root = c->cl_host.data();            // [N] each: root, rank of a root, size, xmin, ymin, xmax, ymax
+    int32_t *rank = root + N, *size = rank + N, *x0 = size + N, *y0 = x0 + N, *x1 = y0 + N, *y1 = x1 + N;
+    hipStream_t s = c->stream;
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->clpts.p, points, N * 8, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, launch_cluster(s, c->clpts.as<float>(), npoints, slim, c->clbest.as<unsigned long long>(),
+                                    c->clroot.as<int32_t>()));
+    HIP_OR_RETURN(c, hipMemcpyAsync(root, c->clroot.p, N * 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    // clusters in creation order = roots in ascending order; a root precedes its members
+    int nall = 0;
+    for (size_t i = 0; i < N; i++) {
+        const int32_t r = root[i];
+        if (r < 0 || (size_t)r > i || root[r] != r)
+            return set_err(c, MDX_EHIP, "mdx_cluster_euclidean: inconsistent root %d of point %zu", r, i);
+        // cv::Mat(cluster).copyTo(vector<cv::Point>): saturate_cast<int>(float) = cvRound, half to even
+        const int32_t xi = (int32_t)std::lrint((double)points[2 * i]), yi = (int32_t)std::lrint((double)points[2 * i + 1]);
+        if ((size_t)r == i) {
+            rank[i] = nall++;
+            size[i] = 1;
+            x0[i] = x1[i] = xi;
+            y0[i] = y1[i] = yi;
+        } else {
+            size[r]++;
+            x0[r] = std::min(x0[r], xi);
+            x1[r] = std::max(x1[r], xi);
+            y0[r] = std::min(y0[r], yi);
+            y1[r] = std::max(y1[r], yi);
+        }
+        if (labels) labels[i] = rank[r];
+    }
+    int nk = 0;
+    for (size_t i = 0; i < N; i++) {
+        if ((size_t)root[i] != i || size[i] <= min_size) continue;
+        if (nk < max_kept) {
+            if (kept) kept[nk] = rank[i];
+            if (rects) {                          // boundingRect of integer points
+                rects[4 * nk] = x0[i];
+                rects[4 * nk + 1] = y0[i];
+                rects[4 * nk + 2] = (int32_t)((uint32_t)x1[i] - (uint32_t)x0[i] + 1u);
+                rects[4 * nk + 3] = (int32_t)((uint32_t)y1[i] - (uint32_t)y0[i] + 1u);
+            }
+        }
+        nk++;
+    }
+    if (num_all) *num_all = nall;
+    if (num_kept) *num_kept = nk;
     return MDX_OK;
 }
 

@@ -216,6 +216,13 @@ hipError_t launch_lk_chain(hipStream_t s, const LkArgs& a, const TrajChain& t, i
 hipError_t launch_subspace(hipStream_t s, const float* traj, int N, int T, int d, const int* cols, int nhyp,
                            double sigma, float* data, double* qbuf, int* counts, double* residuals,
                            uint8_t* is_outlier, int* best, int precision);
+// Greedy Euclidean clustering (clusterEuclidean, mdx_cluster.hip): root[i] = index of the first point
+// of point i's cluster.  pts [N][2]; slim: a squared distance s joins iff its float bits < slim
+// (bits of the largest passing s, plus 1; 0: nothing joins).  Scratch: best [N] keys.  ceil(N / kClB)
+// launches on s.
+constexpr int kClB = 256;    // points per block (= threads of k_cluster_step)
+hipError_t launch_cluster(hipStream_t s, const float* pts, int N, uint32_t slim, unsigned long long* best,
+                          int32_t* root);
 // Trajectory tracking (calculateOpticalFlowTrajectory): grid init and the per-pass point update.
 hipError_t launch_traj_init(hipStream_t s, int npts, int ny, int pixel_step, int nimg, float* cur, float* traj,
                             int* tlen, int* num, int* flag = nullptr);

@@ -20,14 +20,17 @@ By default (``live_chain=True``, as the reference's imageCallback and host/mdx_h
 follows the reference's live branch (:266-348): every ring frame goes to
 calculateOpticalFlowTrajectory (:295, runOpticalFlowTrajectory :94-110); with egomotion and at
 least one complete trajectory, fitSubspace(trajectories, outlier_points, num_motions, sigma) follows
-(:341-348).  ``on_result`` then receives a LiveResult.  ``live_chain=False`` drives the pair path
+(:341-348), and, when the ``distance_threshold`` parameter is set, clusterEuclidean on its outlier
+points (:355) and each kept cluster's bounding rectangle (optical_flow_visualizer.cpp:223-240), the
+rectangles MotionLogger::writeBoundingBox logs under ``log_contours`` (:431-434).  ``on_result``
+then receives a LiveResult.  ``live_chain=False`` drives the pair path
 the north star names (runOpticalFlow, :76-92) on the ring's last two frames, the only one that
 produces the motion mask.
 """
 from __future__ import annotations
 
 from collections import deque
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable
 
 import numpy as np
@@ -69,12 +72,16 @@ def to_rgb8(msg: Image) -> np.ndarray:
 
 @dataclass
 class LiveResult:
-    """Outputs of the live branch (node.cpp:266-348) up to the clustering it hands them to."""
+    """Outputs of the live branch (node.cpp:266-355, :431-434): trajectories, fitSubspace's outliers
+    and, when clustering is on (egomotion and a distance_threshold), their clusters and rectangles."""
     num_vectors: int
     optical_flow_vectors: np.ndarray     # (h, w, 4) Vec4d image (runOpticalFlowTrajectory :97-99)
     trajectories: list                   # complete trajectories, (T, 2) each
     outlier_points: list                 # fitSubspace's (egomotion only)
     subspace: list                       # fitSubspace's return value (egomotion only)
+    clusters: list = field(default_factory=list)     # clusterEuclidean's kept clusters, (n_k, 2) float32 each
+    rectangles: list = field(default_factory=list)   # their (x, y, width, height), as cv::Rect
+    frame_number: int = 0                # global_frame_count_ of this callback (the log's frame column)
 
 
 class MotionDetectionNode:
@@ -83,7 +90,10 @@ class MotionDetectionNode:
         # ring of 2*num_motions+1 frames, and imageCallback always runs the live branch on it
         # (live_chain True; False selects the pair path on the ring's last two frames)
         self.params = {"pixel_step": 10, "min_vector_size": 1.0, "skip_frames": 1, "num_motions": 2,
-                       "egomotion": True, "use_all_frames": True, "sigma": 0.5, "live_chain": True}
+                       "egomotion": True, "use_all_frames": True, "sigma": 0.5, "live_chain": True,
+                       # clustering: distance_threshold has no default in the reference (node.cpp:34;
+                       # the launch files set it) -- None leaves the stage off; log_contours false (:39), log_path "" (:42)
+                       "distance_threshold": None, "log_contours": False, "log_path": ""}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -93,6 +103,8 @@ class MotionDetectionNode:
         self.frames_processed = 0
         self.ofc = OpticalFlowCalculator(device=device)
         self.od = None                                    # OutlierDetector, created on first use
+        self.fc = None                                    # FlowClusterer, created on first use
+        self.logger = None                                # MotionLogger (log_contours with a log_path)
         self._device = device
 
     @property
@@ -139,8 +151,23 @@ class MotionDetectionNode:
                 self.od = OutlierDetector(seed=self.params.get("seed"), device=self._device)
             subspace = self.od.fitSubspace(trajectories, outliers, int(self.params["num_motions"]),
                                            float(self.params["sigma"]))
+        clusters: list = []
+        rectangles: list = []
+        thr = self.params.get("distance_threshold")
+        if trajectories and self.params["egomotion"] and thr is not None:
+            from .flow_clusterer import FlowClusterer, bounding_rects
+            if self.fc is None:
+                self.fc = FlowClusterer(device=self._device)
+            clusters = self.fc.clusterEuclidean(np.asarray(outliers, np.float32).reshape(-1, 2), float(thr))   # :355
+            rectangles = bounding_rects(clusters)
+            if self.params.get("log_contours") and self.params.get("log_path"):           # :431-434
+                if self.logger is None:
+                    from .formats import MotionLogger
+                    self.logger = MotionLogger(self.params["log_path"])
+                for k, rect in enumerate(rectangles):
+                    self.logger.writeBoundingBox(rect, self.global_frame_count, k)
         self.frames_processed += 1
-        res = LiveResult(num, vec, trajectories, outliers, subspace)
+        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters, rectangles, self.global_frame_count)
         if self.on_result is not None:
             self.on_result(res)
         return res
