@@ -45,7 +45,8 @@ EXPORTED = [
 ABI_VERSION = 6   # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
-STAMPED = ["Makefile", "mdx_internal.h", "mdx_api.cpp", "mdx_kernels.hip", "mdx_lk.hip", "mdx_warp.hip",
+STAMPED = ["Makefile", "mdx_internal.h", "mdx_ctx.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp", "mdx_post.cpp",
+           "mdx_kernels.hip", "mdx_lk.hip", "mdx_warp.hip",
            "mdx_subspace.hip", "mdx_cluster.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
@@ -78,8 +79,8 @@ class MdxError(RuntimeError):
 
 def build(force: bool = True) -> str:
     """Compile libmdx.so for gfx950 with hipcc (csrc/Makefile); force (default) rebuilds every
-    object from the sources in the tree (make -B)."""
-    cmd = ["make", "-s", "-C", CSRC] + (["-B"] if force else [])
+    object from the sources in the tree (make -B), up to 16 files at a time."""
+    cmd = ["make", "-s", "-j%d" % min(16, os.cpu_count() or 1), "-C", CSRC] + (["-B"] if force else [])
     subprocess.run(cmd, check=True)
     return LIB_PATH
 

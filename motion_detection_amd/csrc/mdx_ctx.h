@@ -1,0 +1,270 @@
+// mdx_ctx.h -- the context behind the C-ABI (include/mdx.h) and what every host file (mdx_api.cpp, mdx_pair.cpp,
+// mdx_traj.cpp, mdx_post.cpp) needs of it: owning types, errors, workspace growth, geometry, the frame check.
+#pragma once
+
+#include "../../include/mdx.h"
+#include "mdx_internal.h"
+
+#include <algorithm>
+#include <array>
+#include <cstdarg>
+#include <cstdio>
+#include <initializer_list>
+#include <string>
+#include <utility>
+#include <vector>
+
+// Device memory that frees itself.  Move-only; move assignment swaps, so the source frees the old memory.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        std::swap(p, o.p), std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+    bool alloc(size_t bytes)   // a fresh allocation (the old one is freed first); empty on failure
+    {
+        reset();
+        if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr;
+        cap = p ? bytes : 0;
+        return p != nullptr;
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+// The MDX_* environment knobs (INTEGRATION.md describes each), read once by mdx_create (read_tuning).
+struct LkTuning {
+    int lk_impl = 2;          // MDX_LK_IMPL: 1 = single-kernel LK (k_lk), 2 = class planes
+    int lk_g = 0;             // MDX_LK_G: LK group size, 0 = per level, 4 or 8
+    int lk_sub = 0;           // MDX_LK_SUB: > 0: LK sub-batch cap (tests)
+    bool lk_arows = true;     // MDX_LK_AROWS=0: A sums per group, not per row strip where the plan allows
+    int lk_astrip = 0;        // MDX_LK_ASTRIP: grid rows per A-sum strip (0: kAStripRows)
+    // MDX_LK_PFLOW: 1 per-point dataflow wherever the per-pair form does not apply (small batches,
+    // row bands), 2 everywhere; 0 (default) never -- measured slower for row bands
+    int lk_pflow = 0;
+    bool lk_debug = false;    // MDX_LK_DEBUG=1: per-level trace
+    bool traj_chain = true;   // MDX_TRAJ_CHAIN=0: trajectory passes one launch per pass, not chained
+    int traj_ppw = 4;         // MDX_TRAJ_PPW: trajectory LK points per wave (1, 2 or 4)
+    bool lk_aux = true;       // MDX_LK_AUX=0: no aux stream (LK class / A kernels do not run ahead)
+    bool aux_prio = false;    // MDX_AUX_PRIO=1: the aux stream gets the greatest dispatch priority
+    bool lk_flow = true;      // MDX_LK_FLOW=0: no LK dataflow (no second iteration stream)
+    // MDX_LK_CAP: dataflow launch share of the resident waves (%).  75: the aux stream's next-level
+    // class planes and A sums pace the level hand-offs (round 6, profiles/r06_ab_lk_w5_cap.txt: 60 -3%,
+    // 70 / 80 / 85 within 1%, 75 best and steadiest, 95 -1.2%)
+    int lk_cap = 75;
+    int spin_max = mdx::kLkSpinDefault;   // MDX_LK_SPIN_MAX (debug: < 0 injects timeouts)
+    // MDX_LK_XCALL=1: pipelined calls alternate the LK stream parity, so the next call's first level
+    // need not queue behind this call's fit / warp.  +0.5% (noise), and it moves the LK stage events: off
+    bool lk_xcall = false;
+};
+
+struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
+    int device = 0;
+    // what mdx_destroy releases: every stream, event and pinned block created (new_stream, new_events, pinned_ints)
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+    std::vector<void*> pinned;
+    hipStream_t stream = nullptr;
+    hipStream_t aux = nullptr;               // LK class / A kernels run ahead here (MDX_LK_AUX=0: off)
+    hipEvent_t lkev[mdx::kMaxLevels + 2] = {};    // launch_lk_v2's + the first frames' pyramids ready
+    hipStream_t iter2 = nullptr;             // LK dataflow: every other level's iteration launch (MDX_LK_FLOW)
+    hipEvent_t flowev[2] = {};
+    // Call pipelining (mdx_params.call_pipelining): the pyramid slabs have two halves used by
+    // alternate calls, and a call's front end runs on the aux stream right behind the previous
+    // call's last class planes and A sums, so it overlaps that call's last LK level and fit/warp.
+    // (A stream of its own measured 1.9x slower: a process gets 4 hardware queues, and a fifth
+    // stream shares one, so its event waits block the work queued behind them.)
+    hipEvent_t front_ev = nullptr;
+    hipEvent_t pyr_free[2] = {};             // on `stream`, after the last reader of each half
+    hipEvent_t lvl_done[mdx::kMaxLevels] = {};    // the last call's iteration launch of each level
+    hipEvent_t redo_ev[mdx::kMaxLevels] = {};     // LK dataflow: each level's launch + recompute done (fallback order)
+    mdx::LkLaunch lk;                          // launch_lk_v2's streams and events (run_lk adds the per-call part)
+    int pyr_half = 0;                        // the half the next pipelined call writes
+    hipEvent_t input_ev = nullptr;           // mdx_input_ready: the next device call's inputs (caller-owned)
+    uint8_t* last_pyr1 = nullptr;            // the last pair call's pyramids (debug copies)
+    uint8_t* last_pyr2 = nullptr;
+    // the latest mdx_band_flow_dev's pyramids, which its fit/warp reads (band_w == 0: none, or
+    // voided by another call that rebuilt the slabs since)
+    uint8_t* band_pyr1 = nullptr;
+    uint8_t* band_pyr2 = nullptr;
+    int band_half = 0;
+    const uint8_t* band_img1 = nullptr;      // the last mdx_band_flow_dev's frame 1 (its fit/warp reads it)
+    int band_built[2] = {0, 0};              // level-0 rows of frame 1 that call's pyramid build wrote
+    int band_stride = 0, band_fmt = 0;
+    // LK dataflow fallback statistics ([0] group waits and [1] gate waits that gave up, [2] levels
+    // recomputed), read back and cleared at the sync points, accumulated in lk_fallback
+    DevBuf errw;
+    int* err_host = nullptr;                 // pinned readback
+    int* tcnt_host = nullptr;                // pinned readback of the trajectory counts
+    long long lk_fallback[3] = {0, 0, 0};
+    int lk_parity = 0;                       // the next pipelined call's LK stream parity
+    mdx_params prm{};
+    int max_w = 0, max_h = 0, max_batch = 0;
+    DevBuf pyr1, pyr2, der, fits;            // pyramid / derivative / fit workspace
+    DevBuf in1, in2, np, st, vec, mask, H, Hext, num;   // host-path staging
+    DevBuf bnp, bst;                         // LK outputs the batched caller did not ask for
+    DevBuf cls, Abuf, ctab;                  // LK v2: class planes, A sums, residue tables
+    DevBuf dbg;                              // LK v2 per-level trace (MDX_LK_DEBUG=1)
+    DevBuf csum;                             // classify: per-block summaries
+    DevBuf tin, tcur, tnp, tst, ttraj, tnum, tflag;   // trajectory tracking (ttraj: the four outputs, one block)
+    DevBuf straj, sdata, sq, scnt, scols, sres, sout, sbest;      // subspace RANSAC
+    DevBuf clpts, clbest, clroot;            // clusterEuclidean: points, running keys, roots
+    std::vector<int32_t> cl_host;            // its host side (roots, ranks, sizes, boxes): only ever grows
+    DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
+    DevBuf wscr;                             // k_warp_prep's per-pair / per-tile tables
+    mdx::WarpLaunch last_warp;               // the last launch_warp_diff (mdx_debug_warp_paths)
+    DevBuf rsc;                              // MDX_FIT_RANSAC scratch (list, hypotheses, counts)
+    std::vector<int> ring_order;             // held slots, oldest first
+    int ring_cap = 0, ring_w = 0, ring_h = 0, ring_ml = -1;
+    int lk_epoch = 0;                        // per-point dataflow: the last call's epoch
+    void* pflag_mem = nullptr;               // the Abuf allocation and layout whose per-point flags were zeroed
+    size_t pflag_at = 0, pflag_bytes = 0, pflag_per = 0;
+    std::array<int, 6> plan_key{{-1, -1, -1, -1, -1, -1}};   // (w, h, pixel_step, levels, gy0, gy1) of `plan`
+    int band_w = 0, band_h = 0;              // frame of the last mdx_band_flow_dev (its pyramids are live)
+    mdx::ClassPlan plan{};
+    bool timing = false;
+    std::vector<hipEvent_t> ev;            // kSlots (mdx_api.cpp) x 7 events, once timing was enabled
+    int ncalls = 0;                        // calls recorded since enable
+    int cur = -1;                          // slot of the call in flight
+    std::string err;
+};
+
+namespace mdx {
+
+inline int set_err(mdx_ctx* c, int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (c) c->err = buf;
+    return code;
+}
+
+#define HIP_OR_RETURN(c, expr)                                                                 \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return set_err((c), MDX_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
+    } while (0)
+
+// buildOpticalFlowPyramid level count and the padded slab layout for a w x h frame.
+inline Geometry make_geometry(int w, int h, int max_level)
+{
+    Geometry g{};
+    int sw = w, sh = h;
+    long long img = 0, der = 0;
+    int lvl;
+    for (lvl = 0; lvl <= max_level; lvl++) {
+        Level& L = g.lv[lvl];
+        L.w = sw;
+        L.h = sh;
+        L.pitch = (kXOff + sw + kPad + 16 + 63) / 64 * 64;   // +16: slack for 16-B row loads
+        L.rows = kPad + sh + kPad;
+        L.img_off = img;
+        L.der_off = der;
+        img += (long long)L.pitch * L.rows;
+        der += (long long)L.pitch * L.rows;
+        g.nlev = lvl + 1;
+        sw = (sw + 1) / 2;
+        sh = (sh + 1) / 2;
+        if (sw <= kWin || sh <= kWin) break;
+    }
+    g.img_bytes = (img + 255) / 256 * 256;
+    g.der_words = (der + 63) / 64 * 64;
+    return g;
+}
+
+inline int ensure(mdx_ctx* c, DevBuf& b, size_t need)
+{
+    if (need == 0) need = 1;
+    if (b.p && b.cap >= need) return MDX_OK;
+    if (b.p) (void)hipStreamSynchronize(c->stream);   // the aux stream's work is always joined by c->stream
+    if (!b.alloc(need)) return set_err(c, MDX_ENOMEM, "hipMalloc(%zu) failed", need);
+    return MDX_OK;
+}
+
+// n page-locked ints, the context's until mdx_destroy; null on failure
+inline int* pinned_ints(mdx_ctx* c, int n)
+{
+    void* p = nullptr;
+    if (hipHostMalloc(&p, sizeof(int) * n, hipHostMallocDefault) != hipSuccess) return nullptr;
+    c->pinned.push_back(p);
+    return static_cast<int*>(p);
+}
+
+// ensure() for each (buffer, bytes) pair in turn; stops at the first failure
+inline int ensure_all(mdx_ctx* c, std::initializer_list<std::pair<DevBuf*, size_t>> needs)
+{
+    for (const auto& n : needs)
+        if (const int rc = ensure(c, *n.first, n.second); rc != MDX_OK) return rc;
+    return MDX_OK;
+}
+
+// With call pipelining the pyramid slabs hold two halves (ensure_workspace(.., two = true) makes the
+// slab at least twice one call's pyramids); other users take the slab from its start.
+inline size_t pyr_half_bytes(const DevBuf& b) { return b.cap / 2 / 256 * 256; }
+
+inline int ensure_workspace(mdx_ctx* c, const Geometry& g, int batch, bool two)
+{
+    const size_t half = ((size_t)g.img_bytes * batch + 255) / 256 * 256;
+    return ensure_all(c, {{&c->pyr1, two ? 2 * half : half}, {&c->pyr2, two ? 2 * half : half},
+                          {&c->der, (size_t)g.der_words * 4 * batch}, {&c->fits, sizeof(PairFit) * (size_t)batch}});
+}
+
+// Size, pixel format and stride of a caller's frame.  who: the entry's name, which prefixes the
+// message ("who: ..."); null in the pair entries, whose messages carry no prefix.
+inline int check_frame(mdx_ctx* c, const char* who, int w, int h, int stride, int fmt)
+{
+    const char* sep = who ? ": " : "";
+    if (!who) who = "";
+    if (w <= 0 || h <= 0) return set_err(c, MDX_EINVAL, "%s%sbad frame size", who, sep);
+    if (fmt < MDX_FMT_GRAY8 || fmt > MDX_FMT_BGR8) return set_err(c, MDX_EINVAL, "%s%sbad pixel format %d", who, sep, fmt);
+    const int cn = fmt == MDX_FMT_GRAY8 ? 1 : 3;
+    if (stride < w * cn) return set_err(c, MDX_EINVAL, "%s%sstride %d < w*channels %d", who, sep, stride, w * cn);
+    return MDX_OK;
+}
+
+// The LkArgs fields every LK of a w x h frame shares: geometry, the full grid and the clamped
+// iteration parameters.  The caller adds pyramids, outputs and start points.
+inline LkArgs lk_args_for(const mdx_ctx* c, const Geometry& g, int w, int h)
+{
+    const mdx_params& P = c->prm;
+    LkArgs a{};
+    a.g = g;
+    a.maxl = g.nlev - 1;
+    a.npts = mdx_grid_count(w, h, P.pixel_step);
+    a.ny = (h + P.pixel_step - 1) / P.pixel_step;
+    a.nyg = a.ny;
+    a.pixel_step = P.pixel_step;
+    a.max_iters = std::min(std::max(P.max_iters, 0), 100);
+    a.min_eig = P.min_eig;
+    const double e = std::min(std::max(P.eps, 0.), 10.);
+    a.eps2 = e * e;
+    return a;
+}
+
+// Non-pipelined users of the pyramid / derivative slabs (from the slab start, any size): the next
+// pipelined call's front end and aux work wait for them through both halves' events.
+inline void release_pyr_all(mdx_ctx* c)
+{
+    for (hipEvent_t e : c->pyr_free)
+        if (e) (void)hipEventRecord(e, c->stream);
+}
+
+// mdx_pair.cpp: the LK of a batch of pairs on the context's stream (the per-pass trajectory LK too)
+int run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int h, int gy0, int gy1, bool have_scharr,
+           hipEvent_t prev_ready = nullptr, int parity = -1, hipEvent_t out_free = nullptr);
+bool host_block_holds(const void* p, size_t bytes);   // mdx_api.cpp: inside one mdx_host_alloc block
+
+}  // namespace mdx

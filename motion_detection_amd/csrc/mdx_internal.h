@@ -1,5 +1,6 @@
-// mdx_internal.h -- shared between the HIP kernels (mdx_kernels.hip) and the host API
-// (mdx_api.cpp).  Not part of the C-ABI.
+// mdx_internal.h -- the one interface between the HIP kernel files (mdx_kernels.hip, mdx_lk.hip,
+// mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -229,31 +230,44 @@ hipError_t launch_traj_init(hipStream_t s, int npts, int ny, int pixel_step, int
 hipError_t launch_traj_update(hipStream_t s, int npts, const float* next_pts, const uint8_t* status, float* cur,
                               float* traj, int* tlen, int nimg, int w, int h, int last, double min_vector_size,
                               double* vectors, float* start_pts, int* num);
-// Ab: [nlev][batch][npts] per-point (A11, A12, A22, 1/D); qctr: [batch][kMaxLevels][8] (x kCtrPad) queue
-// heads.  aux (may be null): second stream for the flow-independent class / A kernels; ev: kMaxLevels
-// + 1 events (no timing) used to order the two streams.  prev_ready (may be null): recorded by the
-// caller once the first frames' pyramids exist; the aux work waits on it instead of on everything
-// enqueued on s so far (the second frames' pyramids may still be in flight on s).
-// Dataflow (s2 and flow_ev[2] non-null, done: kMaxLevels x batch + kLkFlagInts counters): the level launches alternate
-// between s and s2, so level L-1 starts in level L's tail; its groups wait for their pair's level-L
-// groups (done counters).  Used when every XCD's work range holds two or more whole pairs (batch a
-// multiple of 8, at least 16) and pairs' next_pts do not share 128-B lines (npts % 16 == 0).
-// lvl_done (may be null: calls do not overlap): [kMaxLevels] events, re-recorded after each level's
-// iteration launch; the aux stream waits for the previous call's before rewriting that level's
-// class planes, A sums and queue heads (call pipelining lets the aux stream run a call ahead).
+// launch_lk_v2 (mdx_lk.hip): where the class-plane LK of a call is enqueued.  Host only, never
+// passed to a kernel.  The context fills the first block once at create, run_lk the rest per call.
+struct LkLaunch {
+    hipStream_t s = nullptr;         // the context's stream: everything after the LK follows it
+    hipStream_t aux = nullptr;       // (may be null) second stream for the flow-independent class / A kernels
+    hipStream_t s2 = nullptr;        // (null: no dataflow) every other level's iteration launch
+    hipEvent_t* ev = nullptr;        // kMaxLevels + 1 events (no timing) used to order s and aux
+    hipEvent_t* flow_ev = nullptr;   // dataflow: 2 events
+    hipEvent_t* redo_ev = nullptr;   // dataflow fallback: kMaxLevels events
+    uint8_t* cls = nullptr;          // class planes
+    float4* Ab = nullptr;            // [nlev][batch][npts] per-point (A11, A12, A22, 1/D)
+    int* qctr = nullptr;             // [batch][kMaxLevels][8] (x kCtrPad) queue heads
+    int* done = nullptr;             // dataflow: kMaxLevels x batch + kLkFlagInts counters
+    // (may be null: calls do not overlap) [kMaxLevels] events, re-recorded after each level's
+    // iteration launch; the aux stream waits for the previous call's before rewriting that level's
+    // class planes, A sums and queue heads (call pipelining lets the aux stream run a call ahead)
+    hipEvent_t* lvl_done = nullptr;
+    // (may be null) recorded by the caller once the first frames' pyramids exist; the aux work waits
+    // on it instead of on everything enqueued on s so far (the second frames' pyramids may still be
+    // in flight on s)
+    hipEvent_t prev_ready = nullptr;
+    hipEvent_t out_free = nullptr;   // (may be null) the previous call's outputs have been read
+    int parity = 0;
+};
+// Dataflow (s2, flow_ev and done non-null): the level launches alternate between s and s2, so level
+// L-1 starts in level L's tail; its groups wait for their pair's level-L groups (done counters).
+// Used when every XCD's work range holds two or more whole pairs (batch a multiple of 8, at least
+// 16) and pairs' next_pts do not share 128-B lines (npts % 16 == 0).
 // Cross-call overlap (call pipelining): parity 1 swaps which of s / s2 carries the even levels, so
 // the next call's first level can start on the other stream while this call's classify / fit / warp
 // run on s; qctr and done must then be the parity's own counters and a.carry non-null, and out_free
-// (the previous call's outputs read) is waited for before level 0 writes next_pts / status.
+// is waited for before level 0 writes next_pts / status.
 // Dataflow fallback: a group whose wait gives up (the coarser level's launch was not dispatched in
 // time: a preempted, shared or serialized device) abandons its level, which then drains without
-// computing; right behind each level's launch, on its stream and after the coarser level's (redo_ev,
-// kMaxLevels events), a recompute launch re-runs the level in sequence if it gave up or the coarser
-// level was recomputed, and exits at once otherwise.  Results are then always exact.
-hipError_t launch_lk_v2(hipStream_t s, hipStream_t aux, hipEvent_t* ev, int batch, const LkArgs& a, uint8_t* cls,
-                        float4* Ab, int* qctr, hipEvent_t prev_ready = nullptr, hipStream_t s2 = nullptr,
-                        hipEvent_t* flow_ev = nullptr, int* done = nullptr, hipEvent_t* lvl_done = nullptr,
-                        int parity = 0, hipEvent_t out_free = nullptr, hipEvent_t* redo_ev = nullptr);
+// computing; right behind each level's launch, on its stream and after the coarser level's (redo_ev),
+// a recompute launch re-runs the level in sequence if it gave up or the coarser level was
+// recomputed, and exits at once otherwise.  Results are then always exact.
+hipError_t launch_lk_v2(const LkLaunch& L, int batch, const LkArgs& a);
 // MDX_FIT_RANSAC (mdx_kernels.hip k_ransac_*): device scratch and parameters
 constexpr int kRansacMaxIters = 1024;
 struct RansacArgs {

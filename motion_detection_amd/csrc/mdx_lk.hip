@@ -1246,10 +1246,28 @@ static void launch_iter(hipStream_t s, int batch, const LkArgs& a, const uint8_t
     else hipLaunchKernelGGL((k_lk_iter<G, UW, false>), dim3(W), dim3(64), 0, s, a, cls, Ab, qctr, l, ngroups, batch);
 }
 
-hipError_t launch_lk_v2(hipStream_t s, hipStream_t aux, hipEvent_t* ev, int batch, const LkArgs& a, uint8_t* cls,
-                        float4* Ab, int* qctr, hipEvent_t prev_ready, hipStream_t s2, hipEvent_t* flow_ev, int* done,
-                        hipEvent_t* lvl_done, int parity, hipEvent_t out_free, hipEvent_t* redo_ev)
+// One level's A sums (iter false: per row strip where the plan allows, else per group) or its
+// iteration launch, in the level's (G, UW) shape.  false: the plan names a shape that is not built.
+static bool launch_level(bool iter, hipStream_t st, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab, int* qctr,
+                         int l)
 {
+    const ClassLevel& C = a.plan.lv[l];
+    switch (C.G * 1000 + C.UW) {
+#define LK_CASE(g, uw)                                                   \
+    case g * 1000 + uw:                                                  \
+        if (iter) launch_iter<g, uw>(st, batch, a, cls, Ab, qctr, l);    \
+        else if (C.asp) launch_A_rows<g, uw>(st, batch, a, cls, Ab, qctr, l); \
+        else launch_A<g, uw>(st, batch, a, cls, Ab, qctr, l);            \
+        return true;
+        LK_SHAPES
+#undef LK_CASE
+    default: return false;
+    }
+}
+
+hipError_t launch_lk_v2(const LkLaunch& L, int batch, const LkArgs& a)
+{
+    int parity = L.parity;
     // An XCD range spans at most ceil(n/8) + 1 pairs; its class slabs (and pyramids) must stay
     // addressable by 32-bit buffer offsets, so very large batches of large frames run in
     // sub-batches (the plan already guarantees one pair's slab fits).
@@ -1262,7 +1280,7 @@ hipError_t launch_lk_v2(hipStream_t s, hipStream_t aux, hipEvent_t* ev, int batc
     // stream they run ahead (level L-1's while level L iterates, filling that kernel's tail);
     // every level has its own class planes, A buffer and queue heads, so nothing is overwritten
     // while still in use.
-    hipStream_t sa = aux ? aux : s;
+    hipStream_t sa = L.aux ? L.aux : L.s;
     for (int p = 0, si = 0; p < batch; p += sub, si++) {
         const int nb = std::min(sub, batch - p);
         LkArgs b = a;
@@ -1274,20 +1292,20 @@ hipError_t launch_lk_v2(hipStream_t s, hipStream_t aux, hipEvent_t* ev, int batc
         b.pflags = a.pflags ? a.pflags + (long long)p * a.npts : nullptr;      // pf_lstride: whole batch
         b.status = a.status + (long long)p * a.npts;
         if (p) b.dbg = nullptr;   // the trace covers the first sub-batch
-        uint8_t* bcls = cls + (long long)p * a.plan.bytes_per_pair;
-        int* bq = qctr + si * kMaxLevels * 8 * kCtrPad;
-        if (aux) {
-            hipEvent_t ready = prev_ready;
+        uint8_t* bcls = L.cls + (long long)p * a.plan.bytes_per_pair;
+        int* bq = L.qctr + si * kMaxLevels * 8 * kCtrPad;
+        if (L.aux) {
+            hipEvent_t ready = L.prev_ready;
             if (!ready || p) {   // later sub-batches follow everything on s (their slabs are reused)
-                if (hipError_t e = hipEventRecord(ev[kMaxLevels], s)) return e;
-                ready = ev[kMaxLevels];
+                if (hipError_t e = hipEventRecord(L.ev[kMaxLevels], L.s)) return e;
+                ready = L.ev[kMaxLevels];
             }
             if (hipError_t e = hipStreamWaitEvent(sa, ready, 0)) return e;
         }
         for (int l = a.maxl; l >= 0; l--) {
             const ClassLevel& C = a.plan.lv[l];
-            if (aux && lvl_done) {   // the previous call's level-l iterations read these planes / sums
-                if (hipError_t e = hipStreamWaitEvent(sa, lvl_done[l], 0)) return e;
+            if (L.aux && L.lvl_done) {   // the previous call's level-l iterations read these planes / sums
+                if (hipError_t e = hipStreamWaitEvent(sa, L.lvl_done[l], 0)) return e;
             }
             LkClassArgs ca;
             ca.g = a.g;
@@ -1307,27 +1325,17 @@ hipError_t launch_lk_v2(hipStream_t s, hipStream_t aux, hipEvent_t* ev, int batc
                     return e;
                 hipLaunchKernelGGL(k_lk_class, grid, dim3(64), 0, sa, b.pyr1, b.der, bcls, ca);
             }
-            float4* bA = Ab + ((long long)l * batch + p) * a.npts;
-            const int G = C.G, UW = C.UW;
-            switch (G * 1000 + UW) {
-#define LK_CASE(g, uw)                                                              \
-    case g * 1000 + uw:                                                             \
-        if (C.asp) launch_A_rows<g, uw>(sa, nb, b, bcls, bA, bq, l);               \
-        else launch_A<g, uw>(sa, nb, b, bcls, bA, bq, l);                          \
-        break;
-                LK_SHAPES
-#undef LK_CASE
-            default: return hipErrorInvalidValue;
-            }
-            if (aux) {
-                if (hipError_t e = hipEventRecord(ev[l], sa)) return e;
+            float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
+            if (!launch_level(false, sa, nb, b, bcls, bA, bq, l)) return hipErrorInvalidValue;
+            if (L.aux) {
+                if (hipError_t e = hipEventRecord(L.ev[l], sa)) return e;
             }
         }
         // dataflow: every XCD's work range must hold whole pairs (the hand-off stays in one L2) and
         // no two pairs' carried points may share a 128-B line; with one pair per XCD (batch 8) the
         // next level can only start once the whole level is done there, and the dataflow measured
         // 1.5% slower than levels in sequence, so it needs at least two
-        const bool flow_ok = aux && s2 && flow_ev && done && redo_ev && a.err && b.carry &&
+        const bool flow_ok = L.aux && L.s2 && L.flow_ev && L.done && L.redo_ev && a.err && b.carry &&
                              (reinterpret_cast<uintptr_t>(b.carry) & 127) == 0 && (a.carry_lstride % 32) == 0;
         // per pair (groups wait for their pair's whole coarser level) where every XCD range holds
         // two or more whole pairs; per point (groups wait for their own points) for small batches
@@ -1336,31 +1344,31 @@ hipError_t launch_lk_v2(hipStream_t s, hipStream_t aux, hipEvent_t* ev, int batc
                                (reinterpret_cast<uintptr_t>(b.next_pts) & 127) == 0;
         const bool flow_pt = flow_ok && !flow_pair && b.pflags;
         const bool flow = flow_pair || flow_pt;
-        int* lflags = flow ? done + (long long)kMaxLevels * nb * kCtrPad : nullptr;
+        int* lflags = flow ? L.done + (long long)kMaxLevels * nb * kCtrPad : nullptr;
         // the even levels' stream (the first level's) and the odd levels'; parity 1 swaps them so
         // that this call's first level does not queue behind the previous call's fit / warp on s
         const bool swap = flow && parity && b.carry;
-        hipStream_t s0 = swap ? s2 : s, s1 = swap ? s : s2;
+        hipStream_t s0 = swap ? L.s2 : L.s, s1 = swap ? L.s : L.s2;
         if (flow) {
-            if (hipError_t e = hipMemsetAsync(done, 0, sizeof(int) * ((long long)kMaxLevels * nb + kLkFlagInts) * kCtrPad, s0))
+            if (hipError_t e = hipMemsetAsync(L.done, 0, sizeof(int) * ((long long)kMaxLevels * nb + kLkFlagInts) * kCtrPad, s0))
                 return e;
-            if (hipError_t e = hipEventRecord(flow_ev[0], s0)) return e;   // counters zeroed, front end done
-            if (hipError_t e = hipStreamWaitEvent(s1, flow_ev[0], 0)) return e;
+            if (hipError_t e = hipEventRecord(L.flow_ev[0], s0)) return e;   // counters zeroed, front end done
+            if (hipError_t e = hipStreamWaitEvent(s1, L.flow_ev[0], 0)) return e;
         }
         for (int l = a.maxl; l >= 0; l--) {
             const ClassLevel& C = a.plan.lv[l];
             // levels alternate between the two streams: level l-1 is enqueued behind level l+1
             // only, so it starts as level l's waves leave
             hipStream_t st = flow && ((a.maxl - l) & 1) ? s1 : s0;
-            if (aux) {
-                if (hipError_t e = hipStreamWaitEvent(st, ev[l], 0)) return e;
+            if (L.aux) {
+                if (hipError_t e = hipStreamWaitEvent(st, L.ev[l], 0)) return e;
             }
             // level 0 writes next_pts / status: the previous call's readers of them come first
-            if (l == 0 && out_free) {
-                if (hipError_t e = hipStreamWaitEvent(st, out_free, 0)) return e;
+            if (l == 0 && L.out_free) {
+                if (hipError_t e = hipStreamWaitEvent(st, L.out_free, 0)) return e;
             }
             LkArgs bl = b;
-            bl.done = flow ? done : nullptr;
+            bl.done = flow ? L.done : nullptr;
             bl.done_stride = nb;
             bl.dep_groups = 0;
             bl.lflags = lflags;
@@ -1375,44 +1383,34 @@ hipError_t launch_lk_v2(hipStream_t s, hipStream_t aux, hipEvent_t* ev, int batc
                 const int ngc = (Cp.nxp / Cp.G) * a.nyg, ng = (C.nxp / C.G) * a.nyg;
                 // per point: the coarser queue handed out is the whole condition (dep_groups 0)
                 hipLaunchKernelGGL(k_lk_gate, dim3(1), dim3(64), 0, st, bq + (l + 1) * 8 * kCtrPad, (long long)nb * ngc,
-                                   done + (l + 1) * nb * kCtrPad, bl.dep_groups, ng, (long long)nb * ng, a.err,
+                                   L.done + (l + 1) * nb * kCtrPad, bl.dep_groups, ng, (long long)nb * ng, a.err,
                                    a.spin_max, lflags + (kLkFlagGiveup + l) * kCtrPad);
             }
-            const float4* bA = Ab + ((long long)l * batch + p) * a.npts;
-            switch (C.G * 1000 + C.UW) {
-#define LK_CASE(g, uw) case g * 1000 + uw: launch_iter<g, uw>(st, nb, bl, bcls, bA, bq, l); break;
-                LK_SHAPES
-#undef LK_CASE
-            default: return hipErrorInvalidValue;
-            }
+            float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
+            if (!launch_level(true, st, nb, bl, bcls, bA, bq, l)) return hipErrorInvalidValue;
             if (flow) {
                 // the level's recompute, behind it on its stream and behind the coarser level's
                 // (launch and recompute): exits at once unless the level gave up or the coarser
                 // one was recomputed.  The planes / A sums it reads are released (lvl_done) after it.
                 if (l < a.maxl) {
-                    if (hipError_t e = hipStreamWaitEvent(st, redo_ev[l + 1], 0)) return e;
+                    if (hipError_t e = hipStreamWaitEvent(st, L.redo_ev[l + 1], 0)) return e;
                     LkArgs br = bl;
                     br.done = nullptr;
                     br.dep_groups = 0;
                     br.dep_points = 0;
                     br.redo = 1;
                     br.dbg = nullptr;
-                    switch (C.G * 1000 + C.UW) {
-#define LK_CASE(g, uw) case g * 1000 + uw: launch_iter<g, uw>(st, nb, br, bcls, bA, bq, l); break;
-                        LK_SHAPES
-#undef LK_CASE
-                    default: return hipErrorInvalidValue;
-                    }
+                    if (!launch_level(true, st, nb, br, bcls, bA, bq, l)) return hipErrorInvalidValue;
                 }
-                if (hipError_t e = hipEventRecord(redo_ev[l], st)) return e;
+                if (hipError_t e = hipEventRecord(L.redo_ev[l], st)) return e;
             }
-            if (lvl_done) {
-                if (hipError_t e = hipEventRecord(lvl_done[l], st)) return e;
+            if (L.lvl_done) {
+                if (hipError_t e = hipEventRecord(L.lvl_done[l], st)) return e;
             }
         }
         if (flow) {   // join: everything after the LK (and the next sub-batch) follows both streams
-            if (hipError_t e = hipEventRecord(flow_ev[1], s2)) return e;
-            if (hipError_t e = hipStreamWaitEvent(s, flow_ev[1], 0)) return e;
+            if (hipError_t e = hipEventRecord(L.flow_ev[1], L.s2)) return e;
+            if (hipError_t e = hipStreamWaitEvent(L.s, L.flow_ev[1], 0)) return e;
         }
     }
     return hipGetLastError();

@@ -1,0 +1,624 @@
+// mdx_pair.cpp -- the per-call pair pipeline
+//   gray+pad -> pyrDown x L (both frames) -> Scharr x (L+1) -> LK -> classify+fit -> warp+diff
+// enqueued on the context's HIP streams.  Replaces OpticalFlowCalculator::calculateOpticalFlow
+// (reference common/src/optical_flow_calculator.cpp:30-130); no allocation on the per-frame
+// path once the workspace fits the frame size.  Also the entries that run parts of it: the
+// warp-only and probe entries and the row bands.
+#include "mdx_ctx.h"
+
+#include <cmath>
+#include <cstdlib>
+
+using namespace mdx;
+
+// Residue classes of the grid at each level (see mdx_lk.hip), the class-grouped point order and
+// the class-plane layout.  Rebuilt and uploaded only when frame size / pixel_step / levels change.
+// plan.nch == 0 means some group's union is wider than 512 columns (pixel_step >~ 66) or a pair's
+// class slab exceeds 2 GB: the caller then runs the single-kernel LK instead.
+static int ensure_class_plan(mdx_ctx* c, const Geometry& g, int w, int h, int ps, int batch, int gy0, int gy1)
+{
+    int rc;
+    const std::array<int, 6> key = {w, h, ps, g.nlev, gy0, gy1};
+    if (c->plan_key != key) {
+        const int nx = (w + ps - 1) / ps, ny = (h + ps - 1) / ps;
+        static_assert(kMaxLevels <= 8, "residue tables sized for 2^7 residues");
+        std::vector<int16_t> tab(2 * kMaxLevels * 2 * 128, (int16_t)-1);
+        std::vector<int16_t> ord;
+        int16_t* cmap = tab.data();
+        int16_t* rlist = tab.data() + kMaxLevels * 2 * 128;
+        ClassPlan P{};
+        bool usable = true;
+        for (int l = 0; l < g.nlev; l++) {
+            const int m = (1 << l) - 1;
+            int n[2] = {0, 0};
+            for (int axis = 0; axis < 2; axis++) {
+                const int cnt = axis == 0 ? nx : ny;
+                for (int i = 0; i < cnt; i++) {
+                    const int r = (i * ps) & m;
+                    int16_t& slot = cmap[(l * 2 + axis) * 128 + r];
+                    if (slot < 0) {
+                        slot = (int16_t)n[axis];
+                        rlist[(l * 2 + axis) * 128 + n[axis]] = (int16_t)r;
+                        n[axis]++;
+                    }
+                    if (n[axis] == m + 1) break;
+                }
+            }
+            ClassLevel& C = P.lv[l];
+            C.nrx = n[0];
+            C.nry = n[1];
+            // columns: each class's members in x order.  Group size per level: 4 points when a
+            // 4-group's union fits 64 columns (no extra union loads), else 8 (MDX_LK_G forces one)
+            C.ord_off = (int)ord.size();
+            const int16_t* cmx = cmap + (l * 2 + 0) * 128;
+            const float scale = (float)(1. / (1 << l));
+            auto ipx_of = [&](int gx) { return (int)std::floor((float)(gx * ps) * scale - 19.5f); };
+            std::vector<std::vector<int16_t>> runs(n[0]);
+            for (int i = 0; i < nx; i++) runs[cmx[(i * ps) & m]].push_back((int16_t)i);
+            auto union_of = [&](int G) {
+                int u = 0;
+                for (const auto& r : runs)
+                    for (size_t q = 0; q < r.size(); q += G)
+                        u = std::max(u, ipx_of(r[std::min(r.size(), q + G) - 1]) - ipx_of(r[q]) + kWin);
+                return u;
+            };
+            // group size 4 (less lockstep) unless 8 stages a row with fewer DMA pieces; union
+            // width = the smallest kernel shape that fits (MDX_LK_G=4/8 forces the group size)
+            const int u4 = union_of(4), u8 = union_of(8);
+            auto fit = [](const int* uws, int n, int u) {
+                for (int i = 0; i < n; i++)
+                    if (uws[i] >= u) return uws[i];
+                return 0;
+            };
+            const int uw4 = fit(kLkUW4, (int)(sizeof(kLkUW4) / sizeof(int)), u4);
+            const int uw8 = fit(kLkUW8, (int)(sizeof(kLkUW8) / sizeof(int)), u8);
+            // a row's staging cost goes by LDS-DMA pieces (1 KiB, one per 64 lanes x 16 B): the
+            // wave's union row is 4 slots x uw4 or 2 slots x uw8 pairs of 8 B
+            auto pieces = [](int slots, int uw) { return (slots * uw * 8 + 1023) / 1024; };
+            const bool g4 = c->lk_g == 4 ? uw4 > 0
+                          : c->lk_g == 8 ? false
+                          : uw4 > 0 && (uw8 == 0 || pieces(4, uw4) <= pieces(2, uw8));
+            if (g4) {
+                C.G = 4;
+                C.UW = uw4;
+            } else {
+                C.G = 8;
+                C.UW = uw8;
+            }
+            if (C.UW == 0) usable = false;
+            for (const auto& r : runs) {   // each run padded to a multiple of G with -1
+                ord.insert(ord.end(), r.begin(), r.end());
+                for (size_t q = r.size(); q % C.G; q++) ord.push_back((int16_t)-1);
+            }
+            C.nxp = (int)ord.size() - C.ord_off;
+            // rows of the band [gy0, gy1): grouped by class the same way (no padding: a group is
+            // one row)
+            const size_t r0 = ord.size();
+            for (int i = gy0; i < gy1; i++) ord.push_back((int16_t)i);
+            const int16_t* cmy = cmap + (l * 2 + 1) * 128;
+            std::stable_sort(ord.begin() + r0, ord.end(),
+                             [&](int16_t u, int16_t v) { return cmy[(u * ps) & m] < cmy[(v * ps) & m]; });
+            // A-sum strips (k_lk_A_rows): runs of one y-class cut into kAStripRows rows; the first
+            // window rows v0 = ipy + 40 of a class's rows must be evenly spaced (asp rows apart)
+            const size_t r1 = ord.size();
+            auto v0_row = [&](int gy) { return (int)std::floor((float)(gy * ps) * scale - 19.5f) + kPad; };
+            int asp = 0;
+            bool uniform = true;
+            std::vector<int16_t> strips;
+            for (size_t i = r0; i < r1;) {
+                size_t e = i + 1;
+                const int cls = cmy[(ord[i] * ps) & m];
+                while (e < r1 && cmy[(ord[e] * ps) & m] == cls) {
+                    const int d = v0_row(ord[e]) - v0_row(ord[e - 1]);
+                    if (asp == 0) asp = d;
+                    if (d != asp) uniform = false;
+                    e++;
+                }
+                // small-batch contexts (C4 row bands: one pair per call) take short strips: more
+                // waves in flight for the few pairs' A sums, which then finish sooner (one band
+                // 1.196-1.197 against 1.217-1.226 ms at 16, profiles/r05_ab_astrip.txt); at batch 32
+                // 4..16 rows measured within noise
+                const size_t srows = c->lk_astrip > 0 ? (size_t)c->lk_astrip
+                                                      : (size_t)(c->max_batch <= 4 ? 4 : kAStripRows);
+                for (size_t s = i; s < e; s += srows) {
+                    strips.push_back((int16_t)(s - r0));
+                    strips.push_back((int16_t)std::min<size_t>(srows, e - s));
+                }
+                i = e;
+            }
+            if (asp == 0) asp = kWin;   // one row per class: windows never overlap
+            C.asp = uniform && asp >= 5 && c->lk_arows ? asp : 0;
+            C.nstrip = (int)strips.size() / 2;
+            C.strip_off = (int)ord.size();
+            ord.insert(ord.end(), strips.begin(), strips.end());
+        }
+        (void)ny;
+        long long off = 0;
+        for (int l = 0; l < g.nlev; l++) {
+            ClassLevel& C = P.lv[l];
+            C.UH = g.lv[l].h + 79;
+            C.PW = (g.lv[l].w + kPad + std::max(C.UW, 64) + 3) & ~3;
+            // plane rows the band's windows read: first rows v0 = clamp(ipy + 40, 0, UH - 40) of
+            // its first and last grid rows (ipy is monotone in gy), 40 rows each
+            const float scale = (float)(1. / (1 << l));
+            auto v0_of = [&](int gy) {
+                const int ipy = (int)std::floor((float)(gy * ps) * scale - 19.5f);
+                return std::min(std::max(ipy + kPad, 0), C.UH - kWin);
+            };
+            C.vlo = v0_of(gy0);
+            C.vhi = v0_of(gy1 - 1) + kWin;
+            C.class_bytes = (long long)C.UH * C.PW * 8;
+            C.off = off;
+            off += (long long)C.nrx * C.nry * C.class_bytes;
+        }
+        // the kernels address a pair's slab with 32-bit buffer offsets
+        if (off > 0x7fff0000LL) usable = false;
+        P.nch = usable ? 1 : 0;
+        P.bytes_per_pair = (off + 255) / 256 * 256;
+        tab.insert(tab.end(), ord.begin(), ord.end());
+        if ((rc = ensure(c, c->ctab, tab.size() * sizeof(int16_t))) != MDX_OK) return rc;
+        // kernels of earlier calls may still read the old tables: the copy waits for them (the
+        // stream is non-blocking, so a plain hipMemcpy would not)
+        HIP_OR_RETURN(c, hipStreamSynchronize(c->stream));
+        HIP_OR_RETURN(c, hipMemcpy(c->ctab.p, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        c->plan = P;
+        c->plan_key = key;
+    }
+    if (c->plan.nch == 0) return MDX_OK;
+    if ((rc = ensure(c, c->cls, (size_t)c->plan.bytes_per_pair * batch + 64)) != MDX_OK) return rc;
+    return MDX_OK;
+}
+
+// The next device call's first stage waits for the caller's input event (mdx_input_ready), once.
+static int wait_input(mdx_ctx* c, hipStream_t st)
+{
+    if (!c->input_ev) return MDX_OK;
+    hipEvent_t e = c->input_ev;
+    c->input_ev = nullptr;
+    HIP_OR_RETURN(c, hipStreamWaitEvent(st, e, 0));
+    return MDX_OK;
+}
+
+static inline void mark(mdx_ctx* c, int i, hipStream_t st = nullptr)
+{
+    if (!c->timing || c->ev.empty()) return;
+    if (i == 0) {
+        c->cur = c->ncalls < (int)c->ev.size() / 7 ? c->ncalls : -1;
+        c->ncalls++;
+    }
+    if (c->cur >= 0) (void)hipEventRecord(c->ev[c->cur * 7 + i], st ? st : c->stream);
+}
+
+// The LK of a batch of pairs on the context's stream.  Grid start points (a.prev_pts null) on a
+// dense enough grid take the class-plane kernels, which launch each level's Scharr planes
+// themselves; otherwise the single kernel, after the Scharr planes unless the caller already
+// computed them (have_scharr).  a: every field but the class-plan ones.
+int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int h, int gy0, int gy1, bool have_scharr,
+                hipEvent_t prev_ready, int parity, hipEvent_t out_free)
+{
+    int rc;
+    hipStream_t s = c->stream;
+    bool v2 = c->lk_impl == 2 && a.prev_pts == nullptr;
+    if (v2) {
+        if ((rc = ensure_class_plan(c, g, w, h, c->prm.pixel_step, batch, gy0, gy1)) != MDX_OK) return rc;
+        v2 = c->plan.nch != 0;   // very sparse grids: the single-kernel LK
+    }
+    if (!v2) {
+        if (gy0 != 0 || gy1 != a.ny)
+            return set_err(c, MDX_EINVAL, "row bands need the class-plane LK (pixel_step too large)");
+        if (!have_scharr)
+            for (int l = 0; l < g.nlev; l++)
+                HIP_OR_RETURN(c, launch_scharr(s, batch, a.pyr1, const_cast<uint32_t*>(a.der), g, l));
+        HIP_OR_RETURN(c, launch_lk(s, batch, a));
+        return MDX_OK;
+    }
+    a.plan = c->plan;
+    a.max_sub = c->lk_sub;
+    a.err = c->errw.as<int>();
+    a.spin_max = c->spin_max;
+    a.flow_cap = c->lk_cap;
+    a.cmap = c->ctab.as<int16_t>();
+    a.rlist = c->ctab.as<int16_t>() + kMaxLevels * 2 * 128;
+    a.ord = c->ctab.as<int16_t>() + 2 * kMaxLevels * 2 * 128;
+    const int npts = a.npts;
+    if (c->lk_debug) {
+        if ((rc = ensure(c, c->dbg, ((size_t)npts * g.nlev * batch + kLkDbgStampOff + kMaxLevels * kLkDbgWaves) * 16)) !=
+            MDX_OK)
+            return rc;
+        a.dbg = c->dbg.as<float4>();
+        const char* e = std::getenv("MDX_LK_DEBUG_PT");
+        a.dbg_pt = e ? std::atoi(e) : -1;
+    }
+    // A sums, then per parity (parity < 0: no cross-call overlap, parity 0's) the queue heads
+    // ([sub-batch][level][XCD]), the dataflow counters ([level][pair]) and the points carried
+    // between levels ([pair][point]; cross-call overlap only: the next call's coarse levels then
+    // never touch the next_pts this call's classify still reads)
+    const size_t abytes = (size_t)g.nlev * batch * npts * sizeof(float4);
+    const size_t qbytes = (size_t)batch * kMaxLevels * 8 * kCtrPad * sizeof(int);
+    const size_t dbytes = ((size_t)kMaxLevels * batch + kLkFlagInts) * kCtrPad * sizeof(int);
+    const size_t lbytes = ((size_t)batch * npts * 8 + 127) / 128 * 128;   // one level's carried points
+    const size_t cbytes = lbytes * g.nlev;
+    // per-point dataflow flags: [level][pair][point] epochs, per parity (zeroed once per allocation;
+    // every call's epoch exceeds the earlier ones', so stale stamps never satisfy a wait)
+    const size_t fbytes = ((size_t)batch * npts * 4 + 127) / 128 * 128;
+    const size_t pbytes = fbytes * g.nlev;
+    const size_t per = qbytes + dbytes + cbytes + pbytes;
+    if ((rc = ensure(c, c->Abuf, abytes + 2 * per)) != MDX_OK) return rc;
+    // (re)zeroed whenever the flags move: stale bytes of another layout (A sums, carried points)
+    // could read as large epochs
+    const size_t pf_at = abytes + qbytes + dbytes + cbytes;
+    if (c->lk_epoch >= (1 << 30)) {   // epochs wrap: start again from zeroed flags
+        c->lk_epoch = 0;
+        c->pflag_mem = nullptr;
+    }
+    if (c->pflag_mem != c->Abuf.p || c->pflag_at != pf_at || c->pflag_bytes != pbytes || c->pflag_per != per) {
+        // only the flag regions: the aux stream may already write the A sums of this allocation;
+        // the flags' writers and readers (the iteration launches) follow c->stream
+        for (int q = 0; q < 2; q++)
+            HIP_OR_RETURN(c, hipMemsetAsync(c->Abuf.as<uint8_t>() + abytes + q * per + qbytes + dbytes + cbytes, 0,
+                                            pbytes, c->stream));
+        // the coarsest level may run on the second iteration stream (MDX_LK_XCALL, parity 1), which
+        // does not follow c->stream: finish the zeroing before any launch reads the flags (this runs
+        // only when the flag regions move, i.e. on a reallocation or a layout change)
+        HIP_OR_RETURN(c, hipStreamSynchronize(c->stream));
+        c->pflag_mem = c->Abuf.p;
+        c->pflag_at = pf_at;
+        c->pflag_bytes = pbytes;
+        c->pflag_per = per;
+    }
+    const int par = parity < 0 ? 0 : parity;
+    uint8_t* base = c->Abuf.as<uint8_t>() + abytes + par * per;
+    a.carry = reinterpret_cast<float*>(base + qbytes + dbytes);
+    a.carry_lstride = (long long)(lbytes / sizeof(float));
+    a.pflags = c->lk_pflow <= 0 ? nullptr : reinterpret_cast<int*>(base + qbytes + dbytes + cbytes);
+    a.pf_lstride = (long long)(fbytes / sizeof(int));
+    a.epoch = ++c->lk_epoch;
+    a.pflow_force = c->lk_pflow > 1 ? 1 : 0;
+    LkLaunch L = c->lk;
+    L.cls = c->cls.as<uint8_t>();
+    L.Ab = c->Abuf.as<float4>();
+    L.qctr = reinterpret_cast<int*>(base);
+    L.done = reinterpret_cast<int*>(base + qbytes);
+    L.lvl_done = c->prm.call_pipelining ? c->lvl_done : nullptr;
+    L.prev_ready = prev_ready;
+    L.out_free = out_free;
+    L.parity = par;
+    HIP_OR_RETURN(c, launch_lk_v2(L, batch, a));
+    return MDX_OK;
+}
+
+// Row-band mode: the previous frame's (pyr1) core rows a band's class planes read at each level --
+// padded rows [vlo - 1, vhi + 2) of the planes' source (k_lk_class_fused reads y-1 .. y+2, the
+// Scharr planes behind k_lk_class the same), reflect-101 border rows folded onto the core rows they
+// mirror -- and the rows the next level's pyrDown reads from it (pyramids.cpp: dst row r reads rows
+// 2r-2 .. 2r+2).  Only those rows of pyr1 are built; the next frame's pyramid stays whole, since J
+// may be read anywhere in it.
+static void band_rows(const Geometry& g, const ClassPlan& P, RowSpan* rows)
+{
+    for (int l = g.nlev - 1; l >= 0; l--) {
+        const int h = g.lv[l].h;
+        const int lo = P.lv[l].vlo - 1 - kPad, hi = P.lv[l].vhi + 2 - kPad;   // core coordinates
+        int clo = std::max(lo, 0), chi = std::min(hi, h);
+        if (lo < 0) chi = std::max(chi, std::min(h, 1 - lo));                 // rows lo..-1 mirror 1..-lo
+        if (hi > h) clo = std::min(clo, std::max(0, 2 * h - 1 - hi));         // rows h..hi-1 mirror down to 2h-1-hi
+        if (l + 1 < g.nlev) {
+            clo = std::min(clo, std::max(0, 2 * rows[l + 1].lo - 2));
+            chi = std::max(chi, std::min(h, 2 * rows[l + 1].hi + 2));
+        }
+        rows[l] = RowSpan{clo, std::max(clo, chi)};
+    }
+}
+
+// The pipeline on device buffers.  d_np/d_st must be valid (LK writes them).
+// Row-band mode (cand != null, batch 1): LK and classification for grid rows [gy0, gy1) only, the
+// band's record to *cand, no fit and no mask.
+static int run_pipeline(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint8_t* d_img2, int w, int h, int stride,
+                        size_t frame_stride, int fmt, float* d_np, uint8_t* d_st, double* d_vec, uint8_t* d_mask,
+                        double* d_H, const double* d_Hext, int* d_num, int gy0 = 0, int gy1 = -1,
+                        mdx_band_cand* cand = nullptr, bool may_overlap = false)
+{
+    const mdx_params& P = c->prm;
+    if (w <= 0 || h <= 0 || batch <= 0) return set_err(c, MDX_EINVAL, "bad frame size or batch");
+    int rc = check_frame(c, nullptr, w, h, stride, fmt);
+    if (rc != MDX_OK) return rc;
+    if (batch > 1 && frame_stride < (size_t)stride * h) return set_err(c, MDX_EINVAL, "frame_stride too small");
+    if (P.fit_mode == MDX_FIT_EXTERNAL && !d_Hext) return set_err(c, MDX_EINVAL, "fit_mode EXTERNAL needs H_external");
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    // call pipelining: this call's pyramids go to the half the previous call did not use, and its
+    // front end runs on the front stream once that half's last reader (two calls back) is done
+    const bool pipe = may_overlap && P.call_pipelining && c->aux && c->lk_impl == 2;
+    Geometry g = make_geometry(w, h, P.max_level);
+    if ((rc = ensure_workspace(c, g, batch, pipe)) != MDX_OK) return rc;
+    const int npts = mdx_grid_count(w, h, P.pixel_step);
+    const int ny = (h + P.pixel_step - 1) / P.pixel_step;
+    if (gy1 < 0) gy1 = ny;
+    const int nyb = gy1 - gy0;
+    hipStream_t s = c->stream;
+    uint8_t* pyr1 = c->pyr1.as<uint8_t>();
+    uint8_t* pyr2 = c->pyr2.as<uint8_t>();
+    uint32_t* der = c->der.as<uint32_t>();
+    PairFit* fits = c->fits.as<PairFit>();
+    hipStream_t fs_ = s;
+    int half = 0;
+    if (pipe) {
+        half = c->pyr_half;
+        c->pyr_half ^= 1;
+        pyr1 += half * pyr_half_bytes(c->pyr1);
+        pyr2 += half * pyr_half_bytes(c->pyr2);
+        fs_ = c->aux;
+        HIP_OR_RETURN(c, hipStreamWaitEvent(fs_, c->pyr_free[half], 0));
+    }
+    if ((rc = wait_input(c, fs_)) != MDX_OK) return rc;
+    c->last_pyr1 = pyr1;
+    c->last_pyr2 = pyr2;
+    // a row band's fit/warp reads these pyramids; any other call voids the band's
+    if (cand) {
+        c->band_pyr1 = pyr1;
+        c->band_pyr2 = pyr2;
+        c->band_half = half;
+    } else {
+        c->band_w = c->band_h = 0;
+    }
+
+    mark(c, 0, fs_);
+    // The class planes and A sums need only the first frames' pyramids: build those first and let
+    // the aux stream start on them while the second frames' pyramids are built.  Stage "gray_pad"
+    // = gray + pad + level 1 of the first frames (k_front), "pyrdown" = the rest of the pyramids.
+    hipEvent_t prev_ready = nullptr;
+    const long long fs = (long long)frame_stride;
+    // a row band (batch 1): the rows of the previous frame's pyramid its class planes read
+    RowSpan rows[kMaxLevels];
+    const RowSpan* prows = nullptr;
+    if (cand && c->lk_impl == 2 && npts > 0 && nyb > 0 && nyb < ny) {
+        if ((rc = ensure_class_plan(c, g, w, h, P.pixel_step, batch, gy0, gy1)) != MDX_OK) return rc;
+        if (c->plan.nch != 0) {
+            band_rows(g, c->plan, rows);
+            prows = rows;
+        }
+    }
+    // level-0 rows of frame 1 this call builds (mdx_band_fit_warp_dev converts the others it needs);
+    // k_front writes whole level-1 bands, i.e. level-0 rows 2*lo1 .. 2*hi1 of the widened range
+    c->band_built[0] = 0;
+    c->band_built[1] = h;
+    if (prows) {
+        const int lo1 = std::min(rows[1].lo, rows[0].lo / 2), hi1 = std::max(rows[1].hi, (rows[0].hi + 1) / 2);
+        c->band_built[0] = std::max(0, 2 * lo1);
+        c->band_built[1] = std::min(h, 2 * hi1);
+    }
+    if (c->aux && c->lk_impl == 2) {
+        HIP_OR_RETURN(c, launch_front(fs_, batch, d_img1, d_img2, w, h, stride, fs, fmt, pyr1, pyr2, g, 1, prows));
+        mark(c, 1, fs_);
+        HIP_OR_RETURN(c, launch_pyr_levels(fs_, batch, pyr1, pyr2, g, 1, prows));
+        HIP_OR_RETURN(c, hipEventRecord(c->lkev[kMaxLevels + 1], fs_));
+        prev_ready = c->lkev[kMaxLevels + 1];
+        HIP_OR_RETURN(c, launch_front(fs_, batch, d_img1, d_img2, w, h, stride, fs, fmt, pyr1, pyr2, g, 2));
+        HIP_OR_RETURN(c, launch_pyr_levels(fs_, batch, pyr1, pyr2, g, 2));
+        if (pipe) {
+            mark(c, 2, fs_);
+            HIP_OR_RETURN(c, hipEventRecord(c->front_ev, fs_));
+            HIP_OR_RETURN(c, hipStreamWaitEvent(s, c->front_ev, 0));
+        }
+    } else {
+        HIP_OR_RETURN(c, launch_front(s, batch, d_img1, d_img2, w, h, stride, fs, fmt, pyr1, pyr2, g));
+        mark(c, 1);
+        HIP_OR_RETURN(c, launch_pyr_levels(s, batch, pyr1, pyr2, g));
+    }
+    if (!pipe) mark(c, 2);
+    // Scharr derivatives feed only the LK.  The class-plane LK launches them itself, on its
+    // aux stream right before each level's class planes, so they overlap the coarser levels'
+    // iterations; the single-kernel LK needs them up front.
+    mark(c, 3);
+    if (npts > 0 && nyb > 0) {
+        LkArgs a = lk_args_for(c, g, w, h);
+        a.pyr1 = pyr1;
+        a.pyr2 = pyr2;
+        a.der = der;
+        a.nyg = nyb;
+        a.next_pts = d_np;
+        a.status = d_st;
+        // pipelined calls alternate the LK's stream parity (cross-call overlap: this call's first
+        // level need not wait for the previous call's classify / fit / warp on the context stream);
+        // level 0 waits for the previous call's warp (pyr_free of its half) before writing outputs
+        int parity = -1;
+        hipEvent_t out_free = nullptr;
+        if (pipe && c->lk_xcall) {
+            parity = c->lk_parity;
+            c->lk_parity ^= 1;
+            out_free = c->pyr_free[half ^ 1];
+        }
+        if ((rc = run_lk(c, g, a, batch, w, h, gy0, gy1, false, prev_ready, parity, out_free)) != MDX_OK) return rc;
+    }
+    mark(c, 4);
+    if ((rc = ensure(c, c->csum, classify_scratch_bytes(batch, npts))) != MDX_OK) return rc;
+    RansacArgs ra{};
+    if (P.fit_mode == MDX_FIT_RANSAC && !cand) {
+        if ((rc = ensure(c, c->rsc, ransac_scratch_bytes(batch, npts, P.ransac_iters))) != MDX_OK) return rc;
+        uint8_t* base = c->rsc.as<uint8_t>();
+        ra.iters = P.ransac_iters;
+        ra.thresh = P.ransac_thresh;
+        ra.seed = P.ransac_seed;
+        ra.list = reinterpret_cast<int*>(base);
+        ra.hyps = reinterpret_cast<double*>(base + (((size_t)batch * npts * 4 + 7) & ~(size_t)7));
+        ra.counts = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(ra.hyps) + (size_t)batch * P.ransac_iters * 72);
+    }
+    HIP_OR_RETURN(c, launch_classify_fit(s, batch, d_np, d_st, npts, ny, gy0, gy1, P.pixel_step, P.min_vector_size, d_vec,
+                                         fits, P.fit_mode, d_Hext, c->csum.p, cand, &ra));
+    mark(c, 5);
+    if (d_mask && !cand) {
+        const Level& L0 = g.lv[0];
+        const uint8_t* g1 = pyr1 + L0.img_off + L0.core();
+        const uint8_t* g2 = pyr2 + L0.img_off + L0.core();
+        const size_t wsb = warp_scratch_bytes(batch, w, h);
+        if ((rc = ensure(c, c->wscr, wsb)) != MDX_OK) return rc;
+        HIP_OR_RETURN(c, launch_warp_diff(s, batch, g1, g.img_bytes, L0.pitch, g2, g.img_bytes, L0.pitch, w, h, fits,
+                                          d_mask, (long long)w * h, P.thresh, c->wscr.p, wsb, 0, -1, &c->last_warp));
+    }
+    if ((d_H || d_num) && !cand) HIP_OR_RETURN(c, launch_export_fit(s, batch, fits, d_H, d_num));
+    // (a row band: mdx_band_fit_warp_dev reads these pyramids, whichever half they are in, and
+    // records their release again after its warp)
+    if (pipe) HIP_OR_RETURN(c, hipEventRecord(c->pyr_free[half], s));
+    else release_pyr_all(c);
+    mark(c, 6);
+    return MDX_OK;
+}
+
+extern "C" int mdx_flow_warp_diff_batch_dev(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint8_t* d_img2,
+                                            int w, int h, int stride, size_t frame_stride, int fmt, float* d_next_pts,
+                                            uint8_t* d_status, double* d_vectors, uint8_t* d_mask, double* d_H,
+                                            const double* d_H_external, int* d_num_vectors)
+{
+    if (!c) return MDX_EINVAL;
+    if (!d_img1 || !d_img2 || batch <= 0) return set_err(c, MDX_EINVAL, "null frame pointer or batch <= 0");
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const size_t need = (size_t)mdx_grid_count(w, h, c->prm.pixel_step) * batch;
+    int rc;
+    if (!d_next_pts) {
+        if ((rc = ensure(c, c->bnp, need * 8)) != MDX_OK) return rc;
+        d_next_pts = c->bnp.as<float>();
+    }
+    if (!d_status) {
+        if ((rc = ensure(c, c->bst, need)) != MDX_OK) return rc;
+        d_status = c->bst.as<uint8_t>();
+    }
+    return run_pipeline(c, batch, d_img1, d_img2, w, h, stride, frame_stride, fmt, d_next_pts, d_status, d_vectors,
+                        d_mask, d_H, d_H_external, d_num_vectors, 0, -1, nullptr, true);
+}
+
+extern "C" int mdx_flow_warp_diff(mdx_ctx* c, const uint8_t* img1, const uint8_t* img2, int w, int h, int stride,
+                                  int fmt, float* next_pts, uint8_t* status, double* vectors, uint8_t* mask, double* H,
+                                  const double* H_external, int* num_vectors)
+{
+    if (!c) return MDX_EINVAL;
+    if (!img1 || !img2) return set_err(c, MDX_EINVAL, "null frame pointer");
+    int rc = check_frame(c, nullptr, w, h, stride, fmt);
+    if (rc != MDX_OK) return rc;
+    if (c->prm.fit_mode == MDX_FIT_EXTERNAL && !H_external)
+        return set_err(c, MDX_EINVAL, "fit_mode EXTERNAL needs H_external");
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const size_t in_bytes = (size_t)stride * h;
+    const int npts = mdx_grid_count(w, h, c->prm.pixel_step);
+    const size_t pts = (size_t)(npts > 0 ? npts : 1);
+    if ((rc = ensure_all(c, {{&c->in1, in_bytes}, {&c->in2, in_bytes}, {&c->np, pts * 8}, {&c->st, pts},
+                             {&c->vec, pts * 32}, {&c->mask, (size_t)w * h}, {&c->H, 72}, {&c->Hext, 72},
+                             {&c->num, 4}})) != MDX_OK)
+        return rc;
+
+    hipStream_t s = c->stream;
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->in1.p, img1, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->in2.p, img2, in_bytes, hipMemcpyHostToDevice, s));
+    if (H_external) HIP_OR_RETURN(c, hipMemcpyAsync(c->Hext.p, H_external, 72, hipMemcpyHostToDevice, s));
+    rc = run_pipeline(c, 1, c->in1.as<uint8_t>(), c->in2.as<uint8_t>(), w, h, stride, in_bytes, fmt, c->np.as<float>(),
+                      c->st.as<uint8_t>(), vectors ? c->vec.as<double>() : nullptr,
+                      mask ? c->mask.as<uint8_t>() : nullptr, c->H.as<double>(),
+                      H_external ? c->Hext.as<double>() : nullptr, c->num.as<int>());
+    if (rc != MDX_OK) return rc;
+    int num = 0;
+    if (next_pts && npts > 0) HIP_OR_RETURN(c, hipMemcpyAsync(next_pts, c->np.p, (size_t)npts * 8, hipMemcpyDeviceToHost, s));
+    if (status && npts > 0) HIP_OR_RETURN(c, hipMemcpyAsync(status, c->st.p, (size_t)npts, hipMemcpyDeviceToHost, s));
+    if (vectors && npts > 0) HIP_OR_RETURN(c, hipMemcpyAsync(vectors, c->vec.p, (size_t)npts * 32, hipMemcpyDeviceToHost, s));
+    if (mask) HIP_OR_RETURN(c, hipMemcpyAsync(mask, c->mask.p, (size_t)w * h, hipMemcpyDeviceToHost, s));
+    if (H) HIP_OR_RETURN(c, hipMemcpyAsync(H, c->H.p, 72, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(&num, c->num.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    if (num_vectors) *num_vectors = num;
+    if (c->prm.fit_mode != MDX_FIT_EXTERNAL && num < 4) return MDX_EDEGENERATE;
+    return MDX_OK;
+}
+
+extern "C" int mdx_warp_diff_dev(mdx_ctx* c, int batch, const uint8_t* d_gray1, const uint8_t* d_gray2, int w, int h,
+                                 int stride, size_t frame_stride, const double* d_H, uint8_t* d_mask)
+{
+    if (!c) return MDX_EINVAL;
+    if (!d_gray1 || !d_gray2 || !d_H || !d_mask || batch <= 0 || w <= 0 || h <= 0 || stride < w)
+        return set_err(c, MDX_EINVAL, "mdx_warp_diff_dev: bad argument");
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    int rc = ensure(c, c->fits, sizeof(PairFit) * (size_t)batch);
+    if (rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    PairFit* fits = c->fits.as<PairFit>();
+    if ((rc = wait_input(c, s)) != MDX_OK) return rc;
+    for (int i = 0; i < 5; i++) mark(c, i);
+    HIP_OR_RETURN(c, launch_set_fit_external(s, batch, d_H, fits));
+    mark(c, 5);
+    const size_t wsb = warp_scratch_bytes(batch, w, h);
+    if ((rc = ensure(c, c->wscr, wsb)) != MDX_OK) return rc;
+    HIP_OR_RETURN(c, launch_warp_diff(s, batch, d_gray1, (long long)frame_stride, stride, d_gray2,
+                                      (long long)frame_stride, stride, w, h, fits, d_mask, (long long)w * h,
+                                      c->prm.thresh, c->wscr.p, wsb, 0, -1, &c->last_warp));
+    mark(c, 6);
+    return MDX_OK;
+}
+
+extern "C" int mdx_probe_stream3_dev(mdx_ctx* c, size_t n, const uint8_t* d_a, const uint8_t* d_b, uint8_t* d_mask,
+                                     int thresh)
+{
+    if (!c) return MDX_EINVAL;
+    if (!d_a || !d_b || !d_mask || n == 0 || n % 16 || ((uintptr_t)d_a | (uintptr_t)d_b | (uintptr_t)d_mask) % 16)
+        return set_err(c, MDX_EINVAL, "mdx_probe_stream3_dev: bad argument");
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    for (int i = 0; i < 6; i++) mark(c, i);
+    HIP_OR_RETURN(c, launch_stream3(c->stream, n, d_a, d_b, d_mask, thresh));
+    mark(c, 6);
+    return MDX_OK;
+}
+
+extern "C" int mdx_band_flow_dev(mdx_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int w, int h, int stride,
+                                 int fmt, int y0, int y1, float* d_next_pts, uint8_t* d_status, double* d_vectors,
+                                 mdx_band_cand* d_cand)
+{
+    if (!c) return MDX_EINVAL;
+    if (!d_img1 || !d_img2 || !d_next_pts || !d_status || !d_cand)
+        return set_err(c, MDX_EINVAL, "mdx_band_flow_dev: null pointer");
+    if (w <= 0 || h <= 0 || y0 < 0 || y1 > h || y0 >= y1) return set_err(c, MDX_EINVAL, "bad band [%d, %d) of %d rows", y0, y1, h);
+    if (c->prm.fit_mode != MDX_FIT_FIRST4) return set_err(c, MDX_EINVAL, "row bands need fit_mode FIRST4");
+    const int ps = c->prm.pixel_step;
+    // grid rows whose y = gy*ps lies in [y0, y1)
+    const int gy0 = (y0 + ps - 1) / ps, gy1 = (y1 + ps - 1) / ps;
+    c->band_w = c->band_h = 0;
+    const int rc = run_pipeline(c, 1, d_img1, d_img2, w, h, stride, (size_t)stride * h, fmt, d_next_pts, d_status,
+                                d_vectors, nullptr, nullptr, nullptr, nullptr, gy0, gy1, d_cand, true);
+    if (rc == MDX_OK) {
+        c->band_w = w;
+        c->band_h = h;
+        c->band_img1 = d_img1;
+        c->band_stride = stride;
+        c->band_fmt = fmt;
+    }
+    return rc;
+}
+
+extern "C" int mdx_band_fit_warp_dev(mdx_ctx* c, int nrec, const mdx_band_cand* d_cands, int y0, int y1,
+                                     uint8_t* d_mask_band, double* d_H, int* d_num_vectors)
+{
+    if (!c) return MDX_EINVAL;
+    if (nrec <= 0 || !d_cands || !d_mask_band) return set_err(c, MDX_EINVAL, "mdx_band_fit_warp_dev: bad argument");
+    const int w = c->band_w, h = c->band_h;
+    if (w <= 0 || h <= 0)
+        return set_err(c, MDX_EINVAL, "mdx_band_fit_warp_dev: no mdx_band_flow_dev before, or another call rebuilt "
+                                      "the context's pyramids since");
+    if (y0 < 0 || y1 > h || y0 >= y1) return set_err(c, MDX_EINVAL, "bad band [%d, %d) of %d rows", y0, y1, h);
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const Geometry g = make_geometry(w, h, c->prm.max_level);
+    hipStream_t s = c->stream;
+    PairFit* fits = c->fits.as<PairFit>();
+    if (!c->band_pyr1 || !c->band_img1) return set_err(c, MDX_EINVAL, "mdx_band_fit_warp_dev: no mdx_band_flow_dev before");
+    HIP_OR_RETURN(c, launch_band_fit(s, nrec, d_cands, fits, w, h, y0, y1));
+    const Level& L0 = g.lv[0];
+    // the band's flow built frame 1's pyramid for its own rows only: the rows this band's warp
+    // reads beyond them (the fit is known now) are converted from the frame
+    HIP_OR_RETURN(c, launch_gray_rows(s, c->band_img1, w, h, c->band_stride, c->band_fmt,
+                                      c->band_pyr1 + L0.img_off + L0.core(), L0.pitch, fits, c->band_built[0],
+                                      c->band_built[1]));
+    const uint8_t* g1 = c->band_pyr1 + L0.img_off + L0.core();
+    const uint8_t* g2 = c->band_pyr2 + L0.img_off + L0.core();
+    const size_t wsb = warp_scratch_bytes(1, w, y1 - y0);
+    if (const int erc = ensure(c, c->wscr, wsb); erc != MDX_OK) return erc;
+    HIP_OR_RETURN(c, launch_warp_diff(s, 1, g1, g.img_bytes, L0.pitch, g2, g.img_bytes, L0.pitch, w, h, fits, d_mask_band,
+                                      (long long)w * (y1 - y0), c->prm.thresh, c->wscr.p, wsb, y0, y1,
+                                      &c->last_warp));
+    if (d_H || d_num_vectors) HIP_OR_RETURN(c, launch_export_fit(s, 1, fits, d_H, d_num_vectors));
+    // the band's pyramids have been read: the pipelined call two calls on may overwrite them
+    if (c->prm.call_pipelining) HIP_OR_RETURN(c, hipEventRecord(c->pyr_free[c->band_half], s));
+    else release_pyr_all(c);
+    return MDX_OK;
+}

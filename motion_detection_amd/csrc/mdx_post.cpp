@@ -1,0 +1,179 @@
+// mdx_post.cpp -- what follows the flow: the reference's random stream, the trajectory subspace
+// fit (OutlierDetector::fitSubspace) and Euclidean clustering (FlowClusterer::clusterEuclidean).
+#include "mdx_ctx.h"
+
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+
+using namespace mdx;
+
+// glibc rand() (random_r TYPE_3), the generator of fitSubspace's samples
+// (outlier_detector.cpp:17 srand(time(NULL)), :226 rand() % data.cols()).
+extern "C" void mdx_srand(mdx_rand_state* st, uint32_t seed)
+{
+    int32_t r[34];
+    r[0] = (int32_t)(seed ? seed : 1u);
+    for (int i = 1; i < 31; i++) {
+        const int64_t hi = r[i - 1] / 127773, lo = r[i - 1] % 127773;
+        int64_t word = 16807 * lo - 2836 * hi;
+        if (word < 0) word += 2147483647;
+        r[i] = (int32_t)word;
+    }
+    for (int i = 31; i < 34; i++) r[i] = r[i - 31];
+    for (int i = 0; i < 34; i++) st->x[i] = (uint32_t)r[i];
+    st->pos = 34;
+    for (int k = 0; k < 310; k++) (void)mdx_rand(st);
+}
+
+extern "C" int mdx_rand(mdx_rand_state* st)
+{
+    const int i = st->pos;                       // ring of 34: x[i] = x[i-31] + x[i-3]
+    const uint32_t v = st->x[(i - 31) % 34] + st->x[(i - 3) % 34];
+    st->x[i % 34] = v;
+    st->pos = (i + 1) % 34 + 34;
+    return (int)(v >> 1);
+}
+
+// fitSubspace (outlier_detector.cpp:236-331): samples drawn on the host from the caller's
+// generator state (the reference's OutlierDetector keeps one stream across calls), the rest on
+// the device (mdx_subspace.hip).
+extern "C" int mdx_fit_subspace(mdx_ctx* c, const float* traj, int ntraj, int traj_len, int num_motions, double sigma,
+                                mdx_rand_state* rng, int* columns, uint8_t* is_outlier, double* residuals,
+                                float* outlier_points, int* n_outliers)
+{
+    if (!c) return MDX_EINVAL;
+    const int n = 2 * traj_len, d = 4 * num_motions;
+    if (!traj || !rng || ntraj <= 0 || traj_len < 1 || num_motions < 1)
+        return set_err(c, MDX_EINVAL, "mdx_fit_subspace: bad argument (the reference needs >= 1 trajectory: rand() %% 0)");
+    if (d > n) return set_err(c, MDX_EINVAL, "mdx_fit_subspace: 4*num_motions > 2*traj_len (reference reads U past its columns)");
+    if (n > 32) return set_err(c, MDX_EINVAL, "mdx_fit_subspace: trajectories longer than 16 points");
+    if (n - d == 10) return set_err(c, MDX_EINVAL, "mdx_fit_subspace: n - d == 10 (reference chi_square_table.at(10) throws)");
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    constexpr int kHyp = 50;                      // num_iterations (:250)
+    std::vector<int> cols((size_t)kHyp * d);
+    for (auto& v : cols) v = mdx_rand(rng) % ntraj;   // fillSubset, hypothesis by hypothesis (:223-230)
+    const size_t N = (size_t)ntraj;
+    const size_t qb = std::max((size_t)n * std::max(n - d, 1) * 8, (size_t)n * n * 4);   // F64 basis / F32 Pnd
+    const int rc = ensure_all(c, {{&c->straj, N * n * 4}, {&c->sdata, (N * n + 2) * 4},   // + the two means
+                                  {&c->sq, (size_t)kHyp * qb}, {&c->scnt, kHyp * 4}, {&c->scols, cols.size() * 4},
+                                  {&c->sres, N * 8}, {&c->sout, N}, {&c->sbest, 4}});
+    if (rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->straj.p, traj, N * n * 4, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->scols.p, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, launch_subspace(s, c->straj.as<float>(), ntraj, traj_len, d, c->scols.as<int>(), kHyp, sigma,
+                                     c->sdata.as<float>(), c->sq.as<double>(), c->scnt.as<int>(), c->sres.as<double>(),
+                                     c->sout.as<uint8_t>(), c->sbest.as<int>(), c->prm.subspace_precision));
+    std::vector<uint8_t> out(N);
+    int best = -1;
+    HIP_OR_RETURN(c, hipMemcpyAsync(out.data(), c->sout.p, N, hipMemcpyDeviceToHost, s));
+    if (residuals) HIP_OR_RETURN(c, hipMemcpyAsync(residuals, c->sres.p, N * 8, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(&best, c->sbest.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    int nout = 0;
+    for (size_t i = 0; i < N; i++) {
+        if (!out[i]) continue;
+        if (outlier_points) {     // the trajectory's second-to-last point (:322)
+            const int j = traj_len >= 2 ? traj_len - 2 : 0;
+            outlier_points[2 * nout] = traj[(i * traj_len + j) * 2];
+            outlier_points[2 * nout + 1] = traj[(i * traj_len + j) * 2 + 1];
+        }
+        nout++;
+    }
+    if (is_outlier) std::memcpy(is_outlier, out.data(), N);
+    if (columns) {
+        if (best >= 0)
+            std::memcpy(columns, cols.data() + (size_t)best * d, (size_t)d * 4);
+        else
+            for (int k = 0; k < d; k++) columns[k] = -1;
+    }
+    if (n_outliers) *n_outliers = nout;
+    return MDX_OK;
+}
+
+// clusterEuclidean (flow_clusterer.cpp:231-269) + boundingRect per kept cluster
+// (optical_flow_visualizer.cpp:230-236).  The O(N^2) key minimisation runs on the device
+// (mdx_cluster.hip) and leaves root[i], the first point of i's cluster; everything after it is O(N)
+// and runs here, after the one copy that brings root[] back.
+extern "C" int mdx_cluster_euclidean(mdx_ctx* c, const float* points, int npoints, double thr, int min_size,
+                                     int32_t* labels, int* num_all, int32_t* kept, int32_t* rects, int max_kept,
+                                     int* num_kept)
+{
+    if (!c) return MDX_EINVAL;
+    if (npoints < 0 || max_kept < 0 || (npoints > 0 && !points))
+        return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: bad argument");
+    if (npoints > MDX_CLUSTER_MAX_POINTS)
+        return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: more than %d points", MDX_CLUSTER_MAX_POINTS);
+    if (std::isnan(thr)) return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: distance_threshold is NaN");
+    for (size_t i = 0; i < (size_t)2 * npoints; i++)
+        if (!std::isfinite(points[i]))
+            return set_err(c, MDX_EINVAL, "mdx_cluster_euclidean: point %zu has a non-finite coordinate", i / 2);
+    if (num_all) *num_all = 0;
+    if (num_kept) *num_kept = 0;
+    if (npoints == 0) return MDX_OK;
+    // the threshold test sqrt((double)s) < thr as s <= s*: s* = the largest float that passes (sqrt
+    // is monotonic, so every smaller s passes too); slim = bits(s*) + 1, 0 when not even s = 0 passes
+    uint32_t slim = 0;
+    if (thr > 0.0) {
+        float f = (float)std::min(thr * thr, (double)FLT_MAX);
+        while (f < FLT_MAX && std::sqrt((double)std::nextafterf(f, INFINITY)) < thr) f = std::nextafterf(f, INFINITY);
+        while (f > 0.f && !(std::sqrt((double)f) < thr)) f = std::nextafterf(f, 0.f);
+        if (std::sqrt((double)f) < thr) {
+            std::memcpy(&slim, &f, 4);
+            slim += 1;
+        }
+    }
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const size_t N = (size_t)npoints;
+    const int rc = ensure_all(c, {{&c->clpts, N * 8}, {&c->clbest, N * 8}, {&c->clroot, N * 4}});
+    if (rc != MDX_OK) return rc;
+    if (c->cl_host.size() < 7 * N) c->cl_host.resize(7 * N);
+    int32_t* root = c->cl_host.data();            // [N] each: root, rank of a root, size, xmin, ymin, xmax, ymax
+    int32_t *rank = root + N, *size = rank + N, *x0 = size + N, *y0 = x0 + N, *x1 = y0 + N, *y1 = x1 + N;
+    hipStream_t s = c->stream;
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->clpts.p, points, N * 8, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, launch_cluster(s, c->clpts.as<float>(), npoints, slim, c->clbest.as<unsigned long long>(),
+                                    c->clroot.as<int32_t>()));
+    HIP_OR_RETURN(c, hipMemcpyAsync(root, c->clroot.p, N * 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    // clusters in creation order = roots in ascending order; a root precedes its members
+    int nall = 0;
+    for (size_t i = 0; i < N; i++) {
+        const int32_t r = root[i];
+        if (r < 0 || (size_t)r > i || root[r] != r)
+            return set_err(c, MDX_EHIP, "mdx_cluster_euclidean: inconsistent root %d of point %zu", r, i);
+        // cv::Mat(cluster).copyTo(vector<cv::Point>): saturate_cast<int>(float) = cvRound, half to even
+        const int32_t xi = (int32_t)std::lrint((double)points[2 * i]), yi = (int32_t)std::lrint((double)points[2 * i + 1]);
+        if ((size_t)r == i) {
+            rank[i] = nall++;
+            size[i] = 1;
+            x0[i] = x1[i] = xi;
+            y0[i] = y1[i] = yi;
+        } else {
+            size[r]++;
+            x0[r] = std::min(x0[r], xi);
+            x1[r] = std::max(x1[r], xi);
+            y0[r] = std::min(y0[r], yi);
+            y1[r] = std::max(y1[r], yi);
+        }
+        if (labels) labels[i] = rank[r];
+    }
+    int nk = 0;
+    for (size_t i = 0; i < N; i++) {
+        if ((size_t)root[i] != i || size[i] <= min_size) continue;
+        if (nk < max_kept) {
+            if (kept) kept[nk] = rank[i];
+            if (rects) {                          // boundingRect of integer points
+                rects[4 * nk] = x0[i];
+                rects[4 * nk + 1] = y0[i];
+                rects[4 * nk + 2] = (int32_t)((uint32_t)x1[i] - (uint32_t)x0[i] + 1u);
+                rects[4 * nk + 3] = (int32_t)((uint32_t)y1[i] - (uint32_t)y0[i] + 1u);
+            }
+        }
+        nk++;
+    }
+    if (num_all) *num_all = nall;
+    if (num_kept) *num_kept = nk;
+    return MDX_OK;
+}

@@ -4,7 +4,7 @@ Runs the bench's 1080p x 32 step (4 distinct synthetic pairs) with MDX_LK_DEBUG=
 per-(pair, level, point) trace k_lk_iter writes (npx, npy, iterations, status).  Per level it prints
 the tracked points, the Newton iterations they execute, and what the persistent slots execute:
 a group of G class members iterates max(its points) times, so the slot cost is G x that sum.  The
-grouping is the host plan's (mdx_api.cpp ensure_class_plan: one residue class's members along a
+grouping is the host plan's (mdx_pair.cpp ensure_class_plan: one residue class's members along a
 grid row, in x order, padded to G); both G = 4 and G = 8 are evaluated per level.
 
 With --times <kernel_trace.csv> (a rocprofv3 --kernel-trace of the bench with MDX_LK_FLOW=0, so
