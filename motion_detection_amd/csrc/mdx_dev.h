@@ -1,0 +1,83 @@
+// mdx_dev.h -- device-only helpers shared by the stage kernel files (mdx_front.hip,
+// mdx_lk_point.hip, mdx_fit.hip): reflect-101 indexing, 4-byte-aligned vector loads, the gray
+// conversion.  Nothing host-visible: mdx_internal.h is the one host/device interface.
+#pragma once
+
+#include "mdx_internal.h"
+
+namespace mdx {
+
+__device__ __forceinline__ int r101(int p, int len)
+{
+    // borderInterpolate(p, len, BORDER_REFLECT_101), any number of folds.
+    if ((unsigned)p < (unsigned)len) return p;
+    if (len == 1) return 0;
+    do {
+        if (p < 0) p = -p;
+        else p = 2 * len - 2 - p;
+    } while ((unsigned)p >= (unsigned)len);
+    return p;
+}
+
+// Front-end kernels (A1, A3, A4) work on aligned 16-byte chunks of each padded row (4 words
+// for the derivative rows): a level's padded columns -40 .. w+39 sit at row bytes 24 .. 64+w+39
+// and every row has >= 16 B of slack after them, so a chunk may spill into the unused margin.
+// Interior chunks take vector loads; chunks that touch a border fall back to per-pixel
+// reflect-101 addressing.  One aligned dwordx4 store per thread.
+struct __attribute__((aligned(4))) u4a4k { uint32_t x, y, z, w; };
+struct __attribute__((aligned(4))) u3a4k { uint32_t x, y, z; };
+struct __attribute__((aligned(4))) u2a4k { uint32_t x, y; };
+// a load from a global address held as an integer: through an address-space-1 pointer, so that it is
+// a global_load (vmcnt only).  Through a generic pointer it is a flat_load, which also counts in
+// lgkmcnt: every LDS wait would then wait for it, and a load issued ahead of use would be waited
+// for at the next LDS access.
+template <typename T>
+__device__ __forceinline__ T gload(uintptr_t a)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *reinterpret_cast<const __attribute__((address_space(1))) T*>(a);
+#else
+    return *reinterpret_cast<const T*>(a);   // the host pass only type-checks device code
+#endif
+}
+
+__device__ __forceinline__ int gray_of(const uint8_t* s, int fmt)
+{
+    // color.cpp RGB2Gray<uchar>, blueIdx 0 on rgb8 data: R gets the blue weight
+    if (fmt == 1) return (s[0] * 1868 + s[1] * 9617 + s[2] * 4899 + 8192) >> 14;
+    return (s[2] * 1868 + s[1] * 9617 + s[0] * 4899 + 8192) >> 14;   // bgr8 -> converted to rgb8 first
+}
+
+__device__ __forceinline__ void gray_chunk(const uint8_t* s, int px0, int w, int fmt, uint32_t (&o)[4])
+{
+    if (px0 >= 0 && px0 + 16 <= w && fmt == 0 && (((uintptr_t)(s + px0)) & 3) == 0) {
+        const u4a4k v = *reinterpret_cast<const u4a4k*>(s + px0);
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    } else if (px0 >= 0 && px0 + 16 <= w && fmt != 0 && (((uintptr_t)(s + 3 * px0)) & 3) == 0) {
+        uint32_t b[12];
+        const u4a4k* q = reinterpret_cast<const u4a4k*>(s + 3 * px0);
+#pragma unroll
+        for (int t = 0; t < 3; t++) { const u4a4k v = q[t]; b[4 * t] = v.x; b[4 * t + 1] = v.y; b[4 * t + 2] = v.z; b[4 * t + 3] = v.w; }
+        const uint8_t* bb = reinterpret_cast<const uint8_t*>(b);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            uint32_t d = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) d |= (uint32_t)gray_of(bb + 3 * (4 * t + i), fmt) << (8 * i);
+            o[t] = d;
+        }
+    } else {
+        for (int t = 0; t < 4; t++) {
+            uint32_t d = 0;
+            for (int i = 0; i < 4; i++) {
+                const int px = px0 + 4 * t + i;
+                if (px < -kPad || px >= w + kPad) continue;           // row margin: value unused
+                const int sx = r101(px, w);
+                d |= (uint32_t)(fmt == 0 ? s[sx] : gray_of(s + 3 * sx, fmt)) << (8 * i);
+            }
+            o[t] = d;
+        }
+    }
+}
+
+}  // namespace mdx

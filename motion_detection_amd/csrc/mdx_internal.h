@@ -1,5 +1,5 @@
-// mdx_internal.h -- the one interface between the HIP kernel files (mdx_kernels.hip, mdx_lk.hip,
-// mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
 // mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
@@ -166,7 +166,7 @@ struct RowSpan {
     int lo, hi;
 };
 
-// Launchers (mdx_kernels.hip).  All enqueue on `s`.
+// Launchers (mdx_front.hip; launch_lk: mdx_lk_point.hip).  All enqueue on `s`.
 // fsel: 0 both frames of every pair, 1 the first frame only, 2 the second frame only
 hipError_t launch_gray_pad(hipStream_t s, int batch, const uint8_t* in1, const uint8_t* in2, int w, int h,
                            int stride, long long frame_stride, int fmt, uint8_t* pyr1, uint8_t* pyr2,
@@ -179,9 +179,10 @@ hipError_t launch_front(hipStream_t s, int batch, const uint8_t* in1, const uint
                         int fsel = 0, const RowSpan* rows = nullptr);
 hipError_t launch_pyr_levels(hipStream_t s, int batch, uint8_t* pyr1, uint8_t* pyr2, const Geometry& g, int fsel = 0,
                              const RowSpan* rows = nullptr);
-// padded rows [prow0, prow1) of the level's derivative planes (default: all)
 // every level's Scharr planes, whole levels, one launch
 hipError_t launch_scharr_levels(hipStream_t s, int batch, const uint8_t* pyr1, uint32_t* der, const Geometry& g);
+// padded rows [prow0, prow1) of one level's derivative planes (default: all): the class-plane LK's
+// per-level launches, which need only the rows its planes read (mdx_lk.hip launch_lk_v2)
 hipError_t launch_scharr(hipStream_t s, int batch, const uint8_t* pyr1, uint32_t* der, const Geometry& g, int level,
                          int prow0 = 0, int prow1 = -1);
 hipError_t launch_lk(hipStream_t s, int batch, const LkArgs& a);
@@ -268,7 +269,7 @@ struct LkLaunch {
 // a recompute launch re-runs the level in sequence if it gave up or the coarser level was
 // recomputed, and exits at once otherwise.  Results are then always exact.
 hipError_t launch_lk_v2(const LkLaunch& L, int batch, const LkArgs& a);
-// MDX_FIT_RANSAC (mdx_kernels.hip k_ransac_*): device scratch and parameters
+// MDX_FIT_RANSAC (mdx_fit.hip k_ransac_*): device scratch and parameters
 constexpr int kRansacMaxIters = 1024;
 struct RansacArgs {
     int iters;

@@ -1,7 +1,7 @@
 // mdx_lk.hip -- pyramidal Lucas-Kanade (reference row A5: calcOpticalFlowPyrLK as called at
 // optical_flow_calculator.cpp:71), restructured for CDNA4 while keeping OpenCV 2.4's x86 SSE2
 // arithmetic bit for bit.  This is the "class plane" LK (MDX_LK_IMPL=2, default); the
-// single-kernel k_lk in mdx_kernels.hip is the fallback for very sparse grids.
+// single-kernel k_lk in mdx_lk_point.hip is the fallback for very sparse grids.
 //
 // Per pyramid level, from maxLevel down to 0, three kernels:
 //

@@ -206,9 +206,7 @@ int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int 
     if (!v2) {
         if (gy0 != 0 || gy1 != a.ny)
             return set_err(c, MDX_EINVAL, "row bands need the class-plane LK (pixel_step too large)");
-        if (!have_scharr)
-            for (int l = 0; l < g.nlev; l++)
-                HIP_OR_RETURN(c, launch_scharr(s, batch, a.pyr1, const_cast<uint32_t*>(a.der), g, l));
+        if (!have_scharr) HIP_OR_RETURN(c, launch_scharr_levels(s, batch, a.pyr1, const_cast<uint32_t*>(a.der), g));
         HIP_OR_RETURN(c, launch_lk(s, batch, a));
         return MDX_OK;
     }

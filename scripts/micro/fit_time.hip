@@ -6,7 +6,7 @@
 // collinear picks, a repeated point, all-zero destinations, 8K-scale coordinates) compared bit for bit.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -Imotion_detection_amd/csrc \
 //        scripts/micro/fit_time.hip -Lmotion_detection_amd/lib -lmdx -Wl,-rpath,$PWD/motion_detection_amd/lib
-#include "../../motion_detection_amd/csrc/mdx_kernels.hip"
+#include "../../motion_detection_amd/csrc/mdx_fit.hip"
 #include <cstdio>
 #include <cstring>
 #include <vector>

@@ -3,7 +3,7 @@
 // bytes as the ceiling.  (Round 2 measured the superseded k_gray_pad + per-level k_pyrdown path
 // here at 107 + 42 us against 44 + 32 us; k_pyrdown has since been removed.)
 // hipcc --offload-arch=gfx950 -O3 -I../../include -I../../motion_detection_amd/csrc front_bench.hip -o front_bench
-#include "../../motion_detection_amd/csrc/mdx_kernels.hip"
+#include "../../motion_detection_amd/csrc/mdx_front.hip"
 
 #include <stdio.h>
 #include <algorithm>

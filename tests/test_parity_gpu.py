@@ -168,6 +168,11 @@ def test_warp_diff_dev_batch(mdx, ctx, oracle):
     (16, {"MDX_LK_FLOW": "0"}, (320, 240)),
     (16, {"MDX_LK_G": "8"}, (320, 240)),
     (16, {}, (640, 480)),
+    # the single-kernel LK (k_lk<64, false>) over a batch: blockIdx.y > 0, grid start points, three
+    # pyramid levels, 825 points.  Only the knob reaches it at this size: the default path falls back
+    # to it when a level's group union is wider than 512 columns, and a 330-px row's widest union
+    # is 369 (pixel_step 80: one 8-group of 5 points, 4 * 80 + 40 = 360 -> the 512 shape)
+    (3, {"MDX_LK_IMPL": "1"}, (330, 250)),
 ])
 def test_batch_dev_matches_host_path(mdx, oracle, monkeypatch, B, env, wh):
     """The zero-copy batched entry gives the same per-pair results as the oracle."""

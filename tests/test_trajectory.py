@@ -196,3 +196,36 @@ def test_trajectory_chain_equals_per_pass_launches(mdx, oracle, monkeypatch):
     np.testing.assert_array_equal(a.traj.view(np.uint32), b.traj.view(np.uint32))
     np.testing.assert_array_equal(a.start_pts.view(np.uint32), b.start_pts.view(np.uint32))
     np.testing.assert_array_equal(a.vectors.view(np.uint64), b.vectors.view(np.uint64))
+
+
+_PPW_SHAPE = (330, 250, 4, 10)   # three pyramid levels (330x250, 165x125, 83x63); 33 x 25 = 825 points
+_ppw_shared = {}                 # frames and oracle result, computed once; every case's GPU result
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ppw", ["1", "2", "4"])
+def test_trajectory_points_per_wave(mdx, oracle, monkeypatch, ppw):
+    """MDX_TRAJ_PPW (read at context creation) picks k_lk<64>, <32> or <16> for the chained passes:
+    each equals the oracle bit for bit, and so each other.  825 points is odd, so the last wave has
+    lanes without a point at 2 and at 4 points per wave."""
+    w, h, n, ps = _PPW_SHAPE
+    assert mdx.grid_count(w, h, ps) == 825
+    if "ref" not in _ppw_shared:
+        _ppw_shared["frames"] = sequence(mdx, oracle, w, h, n, seed=15, channels=1)
+        _ppw_shared["ref"] = oracle.flow_trajectory(_ppw_shared["frames"], pixel_step=ps, nthreads=8)
+        _ppw_shared["res"] = {}
+    monkeypatch.setenv("MDX_TRAJ_PPW", ppw)
+    c = mdx.Context(0, w, h, 1)
+    try:
+        c.set_params(pixel_step=ps)
+        res = c.flow_trajectory(_ppw_shared["frames"])
+    finally:
+        c.close()
+    _compare(res, _ppw_shared["ref"], f"ppw {ppw}")
+    for other, b in _ppw_shared["res"].items():
+        assert res.num_vectors == b.num_vectors, (ppw, other)
+        np.testing.assert_array_equal(res.traj_len, b.traj_len)
+        np.testing.assert_array_equal(res.traj.view(np.uint32), b.traj.view(np.uint32))
+        np.testing.assert_array_equal(res.start_pts.view(np.uint32), b.start_pts.view(np.uint32))
+        np.testing.assert_array_equal(res.vectors.view(np.uint64), b.vectors.view(np.uint64))
+    _ppw_shared["res"][ppw] = res
