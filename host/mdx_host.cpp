@@ -1,6 +1,7 @@
 // mdx_host.cpp -- see mdx_host.h.  Reference sites cited per function.
 #include "mdx_host.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -138,6 +139,19 @@ void MotionDetectionNode::run_pair(const Image& a, const Image& b, FrameResult* 
     }
     publish(kTopicFlowMarkers, flow_image(a, r->vector_image, ps, p_.min_vector_size));   // (not :83-85's arrows)
     publish(kTopicMask, mask_image(r->mask, w, h));
+    r->num_regions_all = 0;
+    r->regions.clear();
+    if (p_.region_min_area <= 0) return;
+    // a kept region has at least region_min_area pixels
+    static_assert(sizeof(mdx_region) == 8 * sizeof(int32_t), "mdx_region is eight int32");
+    const int cap = (int)std::min<long long>((long long)w * h / p_.region_min_area, (long long)((w + 1) / 2) * ((h + 1) / 2));
+    int nkept = 0;
+    r->regions.assign((size_t)8 * cap, 0);
+    const int grc = mdx_mask_regions(ctx_, r->mask.data(), w, h, w, p_.region_open ? MDX_REGIONS_OPEN3 : 0,
+                                     p_.region_min_area, reinterpret_cast<mdx_region*>(r->regions.data()), cap,
+                                     &r->num_regions_all, &nkept, nullptr, nullptr);
+    if (grc < 0) throw std::runtime_error(std::string("mdx_mask_regions: ") + mdx_last_error(ctx_));
+    r->regions.resize((size_t)8 * std::min(nkept, cap));
 }
 
 // runOpticalFlowTrajectory (node.cpp:94-110) over the nimg ring frames already on the device, and,

@@ -57,6 +57,11 @@ struct Params {
     // it).  0: the clustering stage is off
     double distance_threshold = 0;
     bool log_contours = false;     // node.cpp:39: log each kept cluster's rectangle (mdx_node: motion.log)
+    // the pair path's mask labelled into regions on the device (mdx_mask_regions: getMotionContours'
+    // recipe, background_subtractor.cpp:31-35).  region_min_area 0: the stage is off; region_open: its
+    // 3x3 opening
+    int region_min_area = 0;
+    bool region_open = true;
 };
 
 // One processed frame's outputs (what the node hands to its publishers / logs).
@@ -71,6 +76,8 @@ struct FrameResult {
     std::vector<uint8_t> mask;                 // h * w, thresholded |warp(gray1) - gray2|
     double H[9] = {0};
     int rc = 0;                                // MDX_OK or MDX_EDEGENERATE
+    int num_regions_all = 0;                   // region_min_area > 0: every component of the (opened) mask
+    std::vector<int32_t> regions;              // x, y, width, height, area, seed_x, seed_y, id of each kept one
     // live path
     std::vector<std::vector<float>> trajectories;   // complete ones, (x, y) * traj_size each
     std::vector<float> outlier_points;              // fitSubspace's outlier_points, (x, y) each

@@ -6,6 +6,8 @@
 //            [subspace_precision=0]   (0 double, 1 the reference's float arithmetic shape)
 //            [distance_threshold=0]   (clusterEuclidean's threshold; 0: no clustering)
 //            [log_contours=0]
+//            [region_min_area=0]      (pair path: label the mask into regions of at least this area; 0: off)
+//            [region_open=1]          (the 3x3 opening in front of the labelling)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -20,6 +22,9 @@
 //   clusters_<k>.bin              live path with egomotion and distance_threshold > 0: i32 num_all,
 //                                 num_kept; i32 labels[nout]; i32 kept[num_kept]; i32 rects[num_kept][4]
 //                                 (x, y, width, height)
+//   regions_<k>.bin               pair path with region_min_area > 0: i32 num_all, num_kept; i32
+//                                 records[num_kept][8] (x, y, width, height, area, seed_x, seed_y, id);
+//                                 with log_contours=1 each record's rectangle goes to motion.log too
 //   motion.log                    log_contours=1: created at start; MotionLogger::writeBoundingBox of
 //                                 every kept cluster's rectangle (node.cpp:431-434), "frame, id, tl.x,
 //                                 tl.y, br.x, br.y" with frame = the node's global_frame_count_ during
@@ -100,6 +105,8 @@ int main(int argc, char** argv)
         p.subspace_precision = std::atoi(get("subspace_precision", "0").c_str());
         p.distance_threshold = std::atof(get("distance_threshold", "0").c_str());
         p.log_contours = std::atoi(get("log_contours", "0").c_str()) != 0;
+        p.region_min_area = std::atoi(get("region_min_area", "0").c_str());
+        p.region_open = std::atoi(get("region_open", "1").c_str()) != 0;
         const int device = std::atoi(get("device", "0").c_str());
         const std::string out = argv[2];
         const std::vector<Image> frames = read_frames(argv[1]);
@@ -148,6 +155,17 @@ int main(int argc, char** argv)
                     for (size_t i = 0; i < r.kept_clusters.size(); i++)
                         ml->write_bounding_box(r.rectangles[4 * i], r.rectangles[4 * i + 1], r.rectangles[4 * i + 2],
                                                r.rectangles[4 * i + 3], frame, (int)i);
+            }
+            if (!p.live_path && p.region_min_area > 0) {
+                const int32_t ghdr[2] = {r.num_regions_all, (int32_t)(r.regions.size() / 8)};
+                std::vector<uint8_t> gb((const uint8_t*)ghdr, (const uint8_t*)ghdr + sizeof(ghdr));
+                gb.insert(gb.end(), (const uint8_t*)r.regions.data(), (const uint8_t*)(r.regions.data() + r.regions.size()));
+                write_bytes(out + "/regions_" + std::to_string(k) + ".bin", gb.data(), gb.size());
+                const int frame = (int)node.global_frame_count() - 1;
+                if (ml)
+                    for (size_t i = 0; i < r.regions.size() / 8; i++)
+                        ml->write_bounding_box(r.regions[8 * i], r.regions[8 * i + 1], r.regions[8 * i + 2],
+                                               r.regions[8 * i + 3], frame, (int)i);
             }
             write_bytes(out + "/res_" + std::to_string(k) + ".bin", buf.data(), buf.size());
             write_flow(r.vector_image, r.w, r.h, p.pixel_step, out + "/flow_" + std::to_string(k));

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 6    /* 2: mdx_params.call_pipelining, mdx_input_ready.
+#define MDX_ABI_VERSION 7    /* 2: mdx_params.call_pipelining, mdx_input_ready.
                                 3: mdx_lk_fallbacks; mdx_params grew ransac_iters, ransac_thresh and
                                    ransac_seed (16 more bytes: a caller built against ABI 2 passes a
                                    shorter struct); mdx_sync / mdx_device_sync return MDX_OK after an
@@ -33,7 +33,9 @@ extern "C" {
                                    a mismatch means the header and the library differ.
                                 5: mdx_debug_warp_paths (a new entry, as 3 and 4 were: nothing existing
                                    changes, but a caller's header and library must be the same age).
-                                6: mdx_cluster_euclidean (a new entry; mdx_params is unchanged, 80 bytes). */
+                                6: mdx_cluster_euclidean (a new entry; mdx_params is unchanged, 80 bytes).
+                                7: mdx_mask_regions_dev and mdx_mask_regions (new entries; mdx_params is
+                                   unchanged, 80 bytes). */
 
 /* Return codes */
 #define MDX_OK           0
@@ -355,6 +357,50 @@ int  mdx_fit_subspace(mdx_ctx* ctx, const float* traj, int ntraj, int traj_len, 
 int mdx_cluster_euclidean(mdx_ctx* ctx, const float* points, int npoints, double distance_threshold,
                           int min_size /* reference: 5 */, int32_t* labels, int* num_all,
                           int32_t* kept, int32_t* rects, int max_kept, int* num_kept);
+
+/*
+ * The motion mask labelled into regions: the pair path's mask turned into
+ * detections on the device, by the reference's own recipe for a mask,
+ * BackgroundSubtractor::getMotionContours (common/src/background_subtractor.cpp:31-35: cv::erode then
+ * cv::dilate with the default 3x3 element, then findContours' 8-connected foreground blobs), each
+ * blob reduced to its boundingRect (optical_flow_visualizer.cpp:230-236).  Restated from the source;
+ * unpinned against a real build (no OpenCV 2.4 to compare with).
+ *   Foreground: a mask byte != 0.
+ *   Opening (flags & MDX_REGIONS_OPEN3): E(x, y) = 1 iff every in-image pixel of the 3x3
+ *   neighbourhood of (x, y), itself included, is foreground; D(x, y) = 1 iff some in-image pixel of
+ *   the 3x3 neighbourhood has E = 1 (out-of-image neighbours never erode and never dilate:
+ *   morphologyDefaultBorderValue, one iteration, centre anchor).  Without the flag D is the
+ *   foreground itself.
+ *   Components: the 8-connected components of D, ordered by the raster index y*w + x of their first
+ *   pixel.  Nested components are all reported: RETR_EXTERNAL would drop a blob that lies inside
+ *   another blob's hole; no hierarchy is built.
+ *   Record: x, y, width, height = (xmin, ymin, xmax - xmin + 1, ymax - ymin + 1), as
+ *   mdx_cluster_euclidean's rects; area = pixel count; seed_x, seed_y = the first pixel; id = the
+ *   component's index among ALL components.
+ *   Kept: area >= min_area (min_area <= 1 keeps every component), listed in ascending id.
+ * mdx_mask_regions_dev is asynchronous on the context stream and never synchronises with the host:
+ * it chains behind mdx_flow_warp_diff_batch_dev on that call's d_mask with no round trip, and it
+ * honours mdx_input_ready like the other device entries.  Every pointer is a device pointer; any
+ * output may be NULL.  num_kept may exceed max_regions: only max_regions records per mask are
+ * written and nothing past them is touched.  The input mask is never modified (d_mask_out must not
+ * overlap it).  Scratch belongs to the context, is a function of (batch, w, h) alone (about 9 bytes
+ * per pixel) and only grows: no allocation after the first call at a given (batch, w, h).
+ * MDX_EINVAL: a null context; batch < 1; w or h < 1; stride < w; frame_stride < h*stride;
+ * w*h > 2^30; max_regions < 0; d_regions NULL with max_regions > 0; unknown flag bits;
+ * d_mask_out == d_mask.
+ */
+#define MDX_REGIONS_OPEN3 1
+typedef struct mdx_region { int32_t x, y, width, height, area, seed_x, seed_y, id; } mdx_region;  /* 32 bytes */
+int mdx_mask_regions_dev(mdx_ctx* ctx, int batch, const uint8_t* d_mask, int w, int h, int stride,
+                         size_t frame_stride, int flags, int min_area,
+                         mdx_region* d_regions /* [batch][max_regions] or NULL */, int max_regions,
+                         int32_t* d_num_all /* [batch] or NULL */, int32_t* d_num_kept /* [batch] or NULL */,
+                         int32_t* d_labels /* [batch][h][w]: id among ALL components, -1 background; or NULL */,
+                         uint8_t* d_mask_out /* [batch][h][w] D as 0/255, row pitch w; or NULL */);
+/* The same for one mask in host memory, synchronous; same outputs (any may be NULL), same errors. */
+int mdx_mask_regions(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                     mdx_region* regions, int max_regions, int* num_all, int* num_kept,
+                     int32_t* labels, uint8_t* mask_out);
 
 /* Page-locked host memory for frames and outputs (e.g. the node's rgb8 staging buffer and its
  * trajectory outputs): copies between it and the device run as DMA at full link rate, while a

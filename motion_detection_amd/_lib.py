@@ -27,6 +27,7 @@ FMT_GRAY8, FMT_RGB8, FMT_BGR8 = 0, 1, 2
 FIT_FIRST4, FIT_EXTERNAL, FIT_RANSAC = 0, 1, 2
 SUBSPACE_F64, SUBSPACE_F32 = 0, 1
 CLUSTER_MAX_POINTS = 262144   # include/mdx.h MDX_CLUSTER_MAX_POINTS
+REGIONS_OPEN3 = 1             # include/mdx.h MDX_REGIONS_OPEN3
 
 # every symbol include/mdx.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -40,14 +41,14 @@ EXPORTED = [
     "mdx_ring_push", "mdx_ring_trajectory", "mdx_ring_reset", "mdx_input_ready",
     "mdx_host_alloc", "mdx_host_free", "mdx_probe_stream3_dev", "mdx_lk_fallbacks",
     "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
-    "mdx_cluster_euclidean",
+    "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions",
 ]
-ABI_VERSION = 6   # include/mdx.h MDX_ABI_VERSION
+ABI_VERSION = 7   # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_internal.h", "mdx_ctx.h", "mdx_dev.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp",
            "mdx_post.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "mdx_cluster.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_regions.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -61,7 +62,13 @@ class MdxRandState(C.Structure):
     _fields_ = [("x", C.c_uint32 * 34), ("pos", C.c_int32)]
 
 
+class MdxRegion(C.Structure):
+    """mdx_region (include/mdx.h): one kept component of the labelled motion mask."""
+    _fields_ = [(n, C.c_int32) for n in ("x", "y", "width", "height", "area", "seed_x", "seed_y", "id")]
+
+
 BAND_CAND_BYTES = 96
+assert C.sizeof(MdxRegion) == 32
 assert C.sizeof(MdxBandCand) == BAND_CAND_BYTES
 
 
@@ -226,6 +233,12 @@ def lib() -> C.CDLL:
     L.mdx_cluster_euclidean.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, vp, C.POINTER(C.c_int), vp, vp, C.c_int,
                                         C.POINTER(C.c_int)]
     L.mdx_cluster_euclidean.restype = C.c_int
+    L.mdx_mask_regions_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp,
+                                       C.c_int, vp, vp, vp, vp]
+    L.mdx_mask_regions_dev.restype = C.c_int
+    L.mdx_mask_regions.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                   C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]
+    L.mdx_mask_regions.restype = C.c_int
     _lib = L
     return L
 

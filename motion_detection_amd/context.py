@@ -39,6 +39,7 @@ class FlowResult:
     mask: np.ndarray | None  # (h, w) uint8 or None
     H: np.ndarray           # (3, 3) float64 (zeros when no fit)
     code: int               # MDX_OK or MDX_EDEGENERATE
+    regions: "RegionResult | None" = None   # the mask labelled into regions (the node's region_min_area)
 
 
 @dataclass
@@ -72,6 +73,21 @@ class ClusterResult:
     kept: np.ndarray            # (num_kept,) int32: ids of the clusters with size > min_size, ascending
     rects: np.ndarray           # (num_kept, 4) int32: x, y, width, height of each kept cluster (cv::Rect)
     num_kept: int = 0           # all kept clusters, also when max_kept cut kept / rects short
+
+
+@dataclass
+class RegionResult:
+    """The motion mask labelled into regions (include/mdx.h mdx_mask_regions)."""
+    regions: np.ndarray         # (min(num_kept, max_regions), 8) int32: x, y, width, height, area, seed_x, seed_y, id
+    num_all: int                # every 8-connected component of the (opened) mask
+    num_kept: int               # those with area >= min_area, also when max_regions cut `regions` short
+    labels: np.ndarray | None = None    # (h, w) int32: id among all components, -1 background (want_labels)
+    mask_out: np.ndarray | None = None  # (h, w) uint8: the opened mask as 0 / 255 (want_mask)
+
+    @property
+    def rectangles(self) -> list:
+        """(x, y, width, height) of each kept region, as cv::Rect."""
+        return [tuple(int(v) for v in r[:4]) for r in self.regions]
 
 
 class Context:
@@ -264,6 +280,38 @@ class Context:
                                                 C.byref(nkept)))
         m = min(nkept.value, cap)
         return ClusterResult(labels, nall.value, kept[:m].copy(), rects[:m].copy(), nkept.value)
+
+    # -- the motion mask labelled into regions (getMotionContours' recipe: opening, 8-connected blobs, boundingRect)
+    def mask_regions(self, mask: np.ndarray, open3: bool = True, min_area: int = 1, max_regions: int | None = None,
+                     want_labels: bool = False, want_mask: bool = False) -> "RegionResult":
+        """max_regions (default: every component the frame can hold) caps how many records are returned."""
+        mask = np.asarray(mask, dtype=np.uint8)
+        if mask.ndim != 2 or mask.strides[1] != 1 or mask.strides[0] < mask.shape[1]:
+            mask = np.ascontiguousarray(mask)
+        if mask.ndim != 2:
+            raise ValueError("mask must be (h, w)")
+        h, w = mask.shape
+        cap = ((w + 1) // 2) * ((h + 1) // 2) if max_regions is None else int(max_regions)
+        if max_regions is None and min_area > 1:
+            cap = min(cap, (w * h) // int(min_area))      # a kept component has at least min_area pixels
+        regs = np.zeros((max(cap, 0), 8), np.int32)
+        labels = np.empty((h, w), np.int32) if want_labels else None
+        mout = np.empty((h, w), np.uint8) if want_mask else None
+        nall, nkept = C.c_int(0), C.c_int(0)
+        self._check(lib().mdx_mask_regions(self._h, _ptr(mask), w, h, mask.strides[0],
+                                           _lib.REGIONS_OPEN3 if open3 else 0, int(min_area),
+                                           _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
+                                           _ptr(labels), _ptr(mout)))
+        return RegionResult(regs[:min(nkept.value, max(cap, 0))].copy(), nall.value, nkept.value, labels, mout)
+
+    def mask_regions_dev(self, batch: int, d_mask: int, w: int, h: int, stride: int, frame_stride: int,
+                         open3: bool = True, min_area: int = 1, d_regions: int = 0, max_regions: int = 0,
+                         d_num_all: int = 0, d_num_kept: int = 0, d_labels: int = 0, d_mask_out: int = 0) -> int:
+        """Asynchronous on the context stream (include/mdx.h mdx_mask_regions_dev); pointers are ints."""
+        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        return self._check(lib().mdx_mask_regions_dev(
+            self._h, batch, v(d_mask), w, h, stride, frame_stride, _lib.REGIONS_OPEN3 if open3 else 0, int(min_area),
+            v(d_regions), max_regions, v(d_num_all), v(d_num_kept), v(d_labels), v(d_mask_out)))
 
     # -- device entries (pointers are ints, e.g. torch.Tensor.data_ptr())
     def flow_warp_diff_batch_dev(self, batch: int, d_img1: int, d_img2: int, w: int, h: int, stride: int,

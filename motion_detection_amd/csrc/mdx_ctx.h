@@ -119,6 +119,8 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf straj, sdata, sq, scnt, scols, sres, sout, sbest;      // subspace RANSAC
     DevBuf clpts, clbest, clroot;            // clusterEuclidean: points, running keys, roots
     std::vector<int32_t> cl_host;            // its host side (roots, ranks, sizes, boxes): only ever grows
+    DevBuf rgscr;                            // mdx_mask_regions_dev: labels, block counts, component records
+    DevBuf rgin, rgout;                      // mdx_mask_regions (host entry): the mask, every output
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
     DevBuf wscr;                             // k_warp_prep's per-pair / per-tile tables
     mdx::WarpLaunch last_warp;               // the last launch_warp_diff (mdx_debug_warp_paths)

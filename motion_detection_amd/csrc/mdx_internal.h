@@ -1,5 +1,5 @@
 // mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
-// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_regions.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
 // mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
@@ -324,5 +324,17 @@ hipError_t debug_warp_paths(hipStream_t s, const WarpLaunch& L, int32_t* out, in
 hipError_t launch_div32(hipStream_t s, const double* in, double* out, int n);   // test hook
 hipError_t launch_stream3(hipStream_t s, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* o, int thresh);
 hipError_t launch_export_fit(hipStream_t s, int batch, const PairFit* fits, double* H, int* num_vectors);
+// mdx_regions.hip: the motion mask labelled into regions.  Seven launches on s, no
+// host synchronisation.  scratch: regions_scratch_bytes(batch, w, h) of device memory, a function
+// of (batch, w, h) alone (about 9 B per pixel: a 4-B label, 20 B per possible component, of which a
+// w x h image has at most ceil(w/2) * ceil(h/2)); `lay`, when given, receives its layout.
+constexpr int kRegionsMaxBatch = 65535;   // images per launch (grid y)
+struct RegionsScratch {
+    size_t lab, blk, stats, nall;   // byte offsets: labels, per-block root counts, records, component counts
+};
+size_t regions_scratch_bytes(int batch, int w, int h, RegionsScratch* lay = nullptr);
+hipError_t launch_mask_regions(hipStream_t s, int batch, const uint8_t* mask, int w, int h, int stride,
+                               size_t frame_stride, int open3, int min_area, mdx_region* regions, int max_regions,
+                               int32_t* num_all, int32_t* num_kept, int32_t* labels, uint8_t* mask_out, void* scratch);
 
 }  // namespace mdx

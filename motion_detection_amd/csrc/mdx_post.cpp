@@ -1,5 +1,6 @@
 // mdx_post.cpp -- what follows the flow: the reference's random stream, the trajectory subspace
-// fit (OutlierDetector::fitSubspace) and Euclidean clustering (FlowClusterer::clusterEuclidean).
+// fit (OutlierDetector::fitSubspace), Euclidean clustering (FlowClusterer::clusterEuclidean) and the
+// pair path's mask labelled into regions (BackgroundSubtractor::getMotionContours' recipe).
 #include "mdx_ctx.h"
 
 #include <cfloat>
@@ -175,5 +176,94 @@ extern "C" int mdx_cluster_euclidean(mdx_ctx* c, const float* points, int npoint
     }
     if (num_all) *num_all = nall;
     if (num_kept) *num_kept = nk;
+    return MDX_OK;
+}
+
+// getMotionContours' recipe on the pair path's mask: opening, 8-connected
+// components, one record per kept component.  All of it runs on the device (mdx_regions.hip); the
+// call only queues launches on the context's stream.
+static int check_regions(mdx_ctx* c, const char* who, int batch, const void* mask, int w, int h, int stride,
+                         size_t frame_stride, int flags, const void* regions, int max_regions, const void* mask_out)
+{
+    if (!mask || batch < 1 || w < 1 || h < 1) return set_err(c, MDX_EINVAL, "%s: bad mask, batch or size", who);
+    if (stride < w) return set_err(c, MDX_EINVAL, "%s: stride %d < w %d", who, stride, w);
+    if (frame_stride < (size_t)h * (size_t)stride) return set_err(c, MDX_EINVAL, "%s: frame_stride < h*stride", who);
+    if ((long long)w * h > (1ll << 30)) return set_err(c, MDX_EINVAL, "%s: more than 2^30 pixels", who);
+    if (max_regions < 0 || (max_regions > 0 && !regions))
+        return set_err(c, MDX_EINVAL, "%s: max_regions %d without room for the records", who, max_regions);
+    if (flags & ~MDX_REGIONS_OPEN3) return set_err(c, MDX_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (mask_out == mask) return set_err(c, MDX_EINVAL, "%s: mask_out is the input mask", who);
+    return MDX_OK;
+}
+
+extern "C" int mdx_mask_regions_dev(mdx_ctx* c, int batch, const uint8_t* d_mask, int w, int h, int stride,
+                                    size_t frame_stride, int flags, int min_area, mdx_region* d_regions,
+                                    int max_regions, int32_t* d_num_all, int32_t* d_num_kept, int32_t* d_labels,
+                                    uint8_t* d_mask_out)
+{
+    if (!c) return MDX_EINVAL;
+    if (const int rc = check_regions(c, "mdx_mask_regions_dev", batch, d_mask, w, h, stride, frame_stride, flags,
+                                     d_regions, max_regions, d_mask_out);
+        rc != MDX_OK)
+        return rc;
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const int chunk = std::min(batch, kRegionsMaxBatch);
+    if (const int rc = ensure(c, c->rgscr, regions_scratch_bytes(chunk, w, h)); rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    if (c->input_ev) {      // mdx_input_ready: one-shot
+        hipEvent_t e = c->input_ev;
+        c->input_ev = nullptr;
+        HIP_OR_RETURN(c, hipStreamWaitEvent(s, e, 0));
+    }
+    const size_t N = (size_t)w * h;
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+        const int nb = std::min(chunk, batch - b0);
+        HIP_OR_RETURN(c, launch_mask_regions(s, nb, d_mask + b0 * frame_stride, w, h, stride, frame_stride,
+                                             flags & MDX_REGIONS_OPEN3, min_area,
+                                             d_regions ? d_regions + (size_t)b0 * max_regions : nullptr, max_regions,
+                                             d_num_all ? d_num_all + b0 : nullptr, d_num_kept ? d_num_kept + b0 : nullptr,
+                                             d_labels ? d_labels + b0 * N : nullptr,
+                                             d_mask_out ? d_mask_out + b0 * N : nullptr, c->rgscr.p));
+    }
+    return MDX_OK;
+}
+
+extern "C" int mdx_mask_regions(mdx_ctx* c, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                                mdx_region* regions, int max_regions, int* num_all, int* num_kept, int32_t* labels,
+                                uint8_t* mask_out)
+{
+    if (!c) return MDX_EINVAL;
+    const size_t fs = (size_t)std::max(h, 0) * (size_t)std::max(stride, 0);
+    if (const int rc = check_regions(c, "mdx_mask_regions", 1, mask, w, h, stride, fs, flags, regions, max_regions,
+                                     mask_out);
+        rc != MDX_OK)
+        return rc;
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    // one output block: counts (num_all, num_kept), records, labels, mask
+    const size_t N = (size_t)w * h, o_rec = 256, o_lab = o_rec + ((size_t)max_regions * sizeof(mdx_region) + 255) / 256 * 256,
+                 o_msk = o_lab + (labels ? N * 4 : 0);
+    // the caller's last row holds w bytes, not stride
+    const size_t in_bytes = (size_t)(h - 1) * stride + w;
+    if (const int rc = ensure_all(c, {{&c->rgin, fs}, {&c->rgout, o_msk + (mask_out ? N : 0)}}); rc != MDX_OK)
+        return rc;
+    hipStream_t s = c->stream;
+    char* out = c->rgout.as<char>();
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->rgin.p, mask, in_bytes, hipMemcpyHostToDevice, s));
+    int32_t* d_cnt = reinterpret_cast<int32_t*>(out);
+    const int rc = mdx_mask_regions_dev(c, 1, c->rgin.as<uint8_t>(), w, h, stride, fs, flags, min_area,
+                                        max_regions ? reinterpret_cast<mdx_region*>(out + o_rec) : nullptr, max_regions,
+                                        d_cnt, d_cnt + 1, labels ? reinterpret_cast<int32_t*>(out + o_lab) : nullptr,
+                                        mask_out ? reinterpret_cast<uint8_t*>(out + o_msk) : nullptr);
+    if (rc != MDX_OK) return rc;
+    int32_t cnt[2] = {0, 0};
+    HIP_OR_RETURN(c, hipMemcpyAsync(cnt, d_cnt, 8, hipMemcpyDeviceToHost, s));
+    if (labels) HIP_OR_RETURN(c, hipMemcpyAsync(labels, out + o_lab, N * 4, hipMemcpyDeviceToHost, s));
+    if (mask_out) HIP_OR_RETURN(c, hipMemcpyAsync(mask_out, out + o_msk, N, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    const int nrec = std::min(cnt[1], max_regions);
+    if (nrec > 0)
+        HIP_OR_RETURN(c, hipMemcpy(regions, out + o_rec, (size_t)nrec * sizeof(mdx_region), hipMemcpyDeviceToHost));
+    if (num_all) *num_all = cnt[0];
+    if (num_kept) *num_kept = cnt[1];
     return MDX_OK;
 }

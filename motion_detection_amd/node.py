@@ -25,7 +25,10 @@ points (:355) and each kept cluster's bounding rectangle (optical_flow_visualize
 rectangles MotionLogger::writeBoundingBox logs under ``log_contours`` (:431-434).  ``on_result``
 then receives a LiveResult.  ``live_chain=False`` drives the pair path
 the north star names (runOpticalFlow, :76-92) on the ring's last two frames, the only one that
-produces the motion mask.
+produces the motion mask.  With ``region_min_area`` set, that mask is labelled into regions on the
+device (BackgroundSubtractor::getMotionContours' recipe: ``region_open`` is its 3x3 opening) and the
+FlowResult carries them as ``regions``; under ``log_contours`` each kept region's rectangle is logged
+like a cluster's.
 """
 from __future__ import annotations
 
@@ -93,7 +96,10 @@ class MotionDetectionNode:
                        "egomotion": True, "use_all_frames": True, "sigma": 0.5, "live_chain": True,
                        # clustering: distance_threshold has no default in the reference (node.cpp:34;
                        # the launch files set it) -- None leaves the stage off; log_contours false (:39), log_path "" (:42)
-                       "distance_threshold": None, "log_contours": False, "log_path": ""}
+                       "distance_threshold": None, "log_contours": False, "log_path": "",
+                       # the pair path's mask labelled into regions (getMotionContours' recipe):
+                       # region_min_area None leaves the stage off; region_open is the 3x3 opening
+                       "region_min_area": None, "region_open": True}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -176,6 +182,17 @@ class MotionDetectionNode:
         """runOpticalFlow (node.cpp:76-92)."""
         res = self.ofc.compute(image1, image2, int(self.params["pixel_step"]), float(self.params["min_vector_size"]),
                                fmt=_lib.FMT_RGB8)
+        min_area = self.params.get("region_min_area")
+        if min_area is not None and res.mask is not None:
+            # the mask is labelled on the device; what comes back is the records
+            res.regions = self.ofc.context.mask_regions(res.mask, open3=bool(self.params.get("region_open", True)),
+                                                        min_area=int(min_area))
+            if self.params.get("log_contours") and self.params.get("log_path"):
+                if self.logger is None:
+                    from .formats import MotionLogger
+                    self.logger = MotionLogger(self.params["log_path"])
+                for k, rect in enumerate(res.regions.rectangles):
+                    self.logger.writeBoundingBox(rect, self.global_frame_count, k)
         self.frames_processed += 1
         if self.on_result is not None:
             self.on_result(res)

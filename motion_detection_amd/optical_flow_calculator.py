@@ -99,6 +99,13 @@ class OpticalFlowCalculator:
         ctx = self._context(w, h, pixel_step, min_vector_size)
         return ctx.flow_warp_diff(image1, image2, fmt=fmt, want_mask=want_mask)
 
+    @property
+    def context(self) -> Context:
+        """The device context of the last call (its later stages run on the same stream)."""
+        if self._ctx is None:
+            raise RuntimeError("no call has created the context yet")
+        return self._ctx
+
     def close(self):
         if self._ctx is not None:
             self._ctx.close()
