@@ -187,7 +187,32 @@ void MotionDetectionNode::run_live(int nimg, FrameResult* r)
     r->cluster_labels.clear();
     r->kept_clusters.clear();
     r->rectangles.clear();
-    if (r->trajectories.empty() || !p_.egomotion) return;       // :296-318 / :357-389 (getClusters: out of scope)
+    r->num_active_vectors = 0;
+    if (r->trajectories.empty()) return;                        // :296-318
+    if (!p_.egomotion) {                                        // :357-389
+        if (!(p_.distance_threshold > 0) || !(p_.angular_threshold > 0)) return;
+        // getClusters(optical_flow_vectors, pixel_step, distance_threshold, angular_threshold) (:375):
+        // the Vec4d image's grid in its visiting order, rows outer (flow_clusterer.cpp:180-184)
+        std::vector<double> grid;
+        for (int y = 0; y < h; y += ps)
+            for (int x = 0; x < w; x += ps) {
+                const double* e = &r->vector_image[((size_t)y * w + x) * 4];
+                grid.insert(grid.end(), e, e + 4);
+            }
+        const int n = (int)(grid.size() / 4), max_kept = n / 6;   // a kept cluster has more than 5 vectors
+        int nkept = 0;
+        r->cluster_labels.assign(n, 0);
+        r->kept_clusters.assign(max_kept, 0);
+        r->rectangles.assign((size_t)4 * max_kept, 0);
+        const int vrc = mdx_cluster_vectors(ctx_, grid.data(), n, p_.distance_threshold, p_.angular_threshold, 5,
+                                            p_.abs_int ? MDX_VCLUSTER_ABS_INT : 0, r->cluster_labels.data(),
+                                            &r->num_active_vectors, &r->num_clusters, r->kept_clusters.data(),
+                                            r->rectangles.data(), max_kept, &nkept);
+        if (vrc < 0) throw std::runtime_error(std::string("mdx_cluster_vectors: ") + mdx_last_error(ctx_));
+        r->kept_clusters.resize(nkept);
+        r->rectangles.resize((size_t)4 * nkept);
+        return;
+    }
     const int nt = (int)r->trajectories.size(), d = 4 * p_.num_motions;
     std::vector<float> flat((size_t)nt * nimg * 2);
     for (int i = 0; i < nt; i++) std::memcpy(&flat[(size_t)i * nimg * 2], r->trajectories[i].data(), (size_t)nimg * 8);

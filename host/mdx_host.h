@@ -56,6 +56,12 @@ struct Params {
     // clusterEuclidean's threshold (node.cpp:320-321, :355; no default there, the launch files set
     // it).  0: the clustering stage is off
     double distance_threshold = 0;
+    // getClusters' second threshold (node.cpp:35, :375; no default there, the launch files set it):
+    // with egomotion false and both thresholds > 0 the live path clusters the trajectory pass's flow
+    // vectors by distance and angle (mdx_cluster_vectors).  0: that stage is off.  abs_int: the
+    // angular distance truncated, the reference's int abs (MDX_VCLUSTER_ABS_INT)
+    double angular_threshold = 0;
+    bool abs_int = false;
     bool log_contours = false;     // node.cpp:39: log each kept cluster's rectangle (mdx_node: motion.log)
     // the pair path's mask labelled into regions on the device (mdx_mask_regions: getMotionContours'
     // recipe, background_subtractor.cpp:31-35).  region_min_area 0: the stage is off; region_open: its
@@ -87,6 +93,10 @@ struct FrameResult {
     std::vector<int32_t> cluster_labels;            // per outlier point: its cluster among all, creation order
     std::vector<int32_t> kept_clusters;             // ids of the clusters with more than 5 points
     std::vector<int32_t> rectangles;                // x, y, w, h of each kept cluster's boundingRect
+    // getClusters on the vector image's grid (:375), when egomotion is off and both thresholds are > 0:
+    // the four fields above are filled the same way, cluster_labels per grid vector in the reference's
+    // visiting order (image rows outer), -1 for a vector without flow
+    int num_active_vectors = 0;                     // grid vectors with a non-zero flow
 };
 
 using Publisher = std::function<void(const std::string& topic, const Image& msg)>;

@@ -5,6 +5,9 @@
 //            [num_motions=2] [egomotion=1] [live_path=1] [sigma=0.5] [seed=1] [device=0]
 //            [subspace_precision=0]   (0 double, 1 the reference's float arithmetic shape)
 //            [distance_threshold=0]   (clusterEuclidean's threshold; 0: no clustering)
+//            [angular_threshold=0]    (egomotion=0: getClusters' angular threshold; with distance_threshold
+//                                      > 0 too, the flow vectors are clustered by distance and angle; 0: off)
+//            [abs_int=0]              (getClusters: truncate the angular distance, the reference's int abs)
 //            [log_contours=0]
 //            [region_min_area=0]      (pair path: label the mask into regions of at least this area; 0: off)
 //            [region_open=1]          (the 3x3 opening in front of the labelling)
@@ -22,6 +25,11 @@
 //   clusters_<k>.bin              live path with egomotion and distance_threshold > 0: i32 num_all,
 //                                 num_kept; i32 labels[nout]; i32 kept[num_kept]; i32 rects[num_kept][4]
 //                                 (x, y, width, height)
+//   vclusters_<k>.bin             live path with egomotion=0 and both thresholds > 0: i32 n (grid vectors,
+//                                 image rows outer), num_active, num_all, num_kept; f64 vectors[n][4] (the
+//                                 grid of the node's vector image as getClusters visits it); i32 labels[n]
+//                                 (-1: no flow); i32 kept[num_kept]; i32 rects[num_kept][4] (x, y, width,
+//                                 height); with log_contours=1 each rectangle goes to motion.log too
 //   regions_<k>.bin               pair path with region_min_area > 0: i32 num_all, num_kept; i32
 //                                 records[num_kept][8] (x, y, width, height, area, seed_x, seed_y, id);
 //                                 with log_contours=1 each record's rectangle goes to motion.log too
@@ -104,6 +112,8 @@ int main(int argc, char** argv)
         p.seed = (uint32_t)std::strtoul(get("seed", "1").c_str(), nullptr, 10);
         p.subspace_precision = std::atoi(get("subspace_precision", "0").c_str());
         p.distance_threshold = std::atof(get("distance_threshold", "0").c_str());
+        p.angular_threshold = std::atof(get("angular_threshold", "0").c_str());
+        p.abs_int = std::atoi(get("abs_int", "0").c_str()) != 0;
         p.log_contours = std::atoi(get("log_contours", "0").c_str()) != 0;
         p.region_min_area = std::atoi(get("region_min_area", "0").c_str());
         p.region_open = std::atoi(get("region_open", "1").c_str()) != 0;
@@ -120,6 +130,7 @@ int main(int argc, char** argv)
         std::unique_ptr<MotionLogger> ml;
         if (p.log_contours) ml.reset(new MotionLogger(out + "/motion.log"));
         const bool clustering = p.live_path && p.egomotion && p.distance_threshold > 0;
+        const bool vclustering = p.live_path && !p.egomotion && p.distance_threshold > 0 && p.angular_threshold > 0;
         for (size_t fi = 0; fi < frames.size(); fi++) {
             FrameResult r;
             if (!node.image_callback(frames[fi], &r)) continue;
@@ -150,6 +161,24 @@ int main(int argc, char** argv)
                 cput(r.rectangles.data(), r.rectangles.size() * 4);
                 write_bytes(out + "/clusters_" + std::to_string(k) + ".bin", cb.data(), cb.size());
                 // the callback's global_frame_count_ (node.cpp:433), before its closing increment (:454)
+                const int frame = (int)node.global_frame_count() - 1;
+                if (ml)
+                    for (size_t i = 0; i < r.kept_clusters.size(); i++)
+                        ml->write_bounding_box(r.rectangles[4 * i], r.rectangles[4 * i + 1], r.rectangles[4 * i + 2],
+                                               r.rectangles[4 * i + 3], frame, (int)i);
+            }
+            if (vclustering) {
+                const int32_t n = (int32_t)r.cluster_labels.size();
+                const int32_t vhdr[4] = {n, r.num_active_vectors, r.num_clusters, (int32_t)r.kept_clusters.size()};
+                std::vector<uint8_t> vb((const uint8_t*)vhdr, (const uint8_t*)vhdr + sizeof(vhdr));
+                auto vput = [&](const void* q, size_t len) { vb.insert(vb.end(), (const uint8_t*)q, (const uint8_t*)q + len); };
+                if (n > 0)                                      // (no trajectory survived: no grid, n = 0)
+                    for (int y = 0; y < r.h; y += p.pixel_step)
+                        for (int x = 0; x < r.w; x += p.pixel_step) vput(&r.vector_image[((size_t)y * r.w + x) * 4], 32);
+                vput(r.cluster_labels.data(), r.cluster_labels.size() * 4);
+                vput(r.kept_clusters.data(), r.kept_clusters.size() * 4);
+                vput(r.rectangles.data(), r.rectangles.size() * 4);
+                write_bytes(out + "/vclusters_" + std::to_string(k) + ".bin", vb.data(), vb.size());
                 const int frame = (int)node.global_frame_count() - 1;
                 if (ml)
                     for (size_t i = 0; i < r.kept_clusters.size(); i++)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 7    /* 2: mdx_params.call_pipelining, mdx_input_ready.
+#define MDX_ABI_VERSION 8    /* 2: mdx_params.call_pipelining, mdx_input_ready.
                                 3: mdx_lk_fallbacks; mdx_params grew ransac_iters, ransac_thresh and
                                    ransac_seed (16 more bytes: a caller built against ABI 2 passes a
                                    shorter struct); mdx_sync / mdx_device_sync return MDX_OK after an
@@ -35,7 +35,8 @@ extern "C" {
                                    changes, but a caller's header and library must be the same age).
                                 6: mdx_cluster_euclidean (a new entry; mdx_params is unchanged, 80 bytes).
                                 7: mdx_mask_regions_dev and mdx_mask_regions (new entries; mdx_params is
-                                   unchanged, 80 bytes). */
+                                   unchanged, 80 bytes).
+                                8: mdx_cluster_vectors (a new entry; mdx_params is unchanged, 80 bytes). */
 
 /* Return codes */
 #define MDX_OK           0
@@ -357,6 +358,58 @@ int  mdx_fit_subspace(mdx_ctx* ctx, const float* traj, int ntraj, int traj_len, 
 int mdx_cluster_euclidean(mdx_ctx* ctx, const float* points, int npoints, double distance_threshold,
                           int min_size /* reference: 5 */, int32_t* labels, int* num_all,
                           int32_t* kept, int32_t* rects, int max_kept, int* num_kept);
+
+/*
+ * First-fit clustering of flow vectors by distance and angle, and bounding rectangles (DESIGN.md
+ * §7g): replaces FlowClusterer::getClusters (common/src/flow_clusterer.cpp:178-227), which the node
+ * runs on the last trajectory pass's Vec4d image when egomotion is off
+ * (motion_detection_node.cpp:375), and boundingRect of each kept cluster (:376-395).  Restated from
+ * the source; unpinned against a real build (no OpenCV 2.4 to compare with).
+ *   vectors [n][4] double host, (x, y, dx, dy) each, in the order the reference visits them: image
+ *   rows outer, columns inner, both stepping pixel_step (:180-184) -- y-major, NOT the x-major grid
+ *   order of the flow entries above; the caller does that gather.
+ *   A vector is active iff fabs(dx) > 0 || fabs(dy) > 0 (:185); the others are skipped (label -1).
+ *   Pair tests of an active vector i and an earlier active vector j:
+ *     N(i, j)  sqrt((xi-xj)*(xi-xj) + (yi-yj)*(yi-yj)) < distance_threshold, all in double, each
+ *              operation rounded (vector_cluster.cpp:118-121).  Exact.
+ *     G(i, j)  the angular distance below angular_threshold.  Each vector's angle is atan2(dy, dx),
+ *              plus 2 pi when negative (:131-139), by the host's libm; the distance is
+ *              w = |angle_i - angle_j|, and 2 pi - w where w > pi (pi = M_PI, 2 pi = 2 * M_PI as
+ *              doubles).  That is what the reference's |atan2(sin d, cos d)| (:123-129) computes, to
+ *              within a few ulp: a decision closer than that to the threshold may differ from a
+ *              reference build.
+ *     MDX_VCLUSTER_ABS_INT  the reference calls unqualified abs on that double (:43).  Where only
+ *              int abs(int) is in scope (<cmath> included, no global abs(double): the 2014 toolchain
+ *              the reference was written with) the distance is truncated toward zero first: G is
+ *              trunc(w) < angular_threshold, which for a threshold in (0, 1] is w < 1.  Without the
+ *              flag (the default): fabs, what was meant and what a current libstdc++ resolves to.
+ *   Assignment (:189-204), first fit with split minima: vector i joins the EARLIEST-created cluster
+ *   that has some earlier member j with N(i, j) and some earlier member j' with G(i, j') -- j' need
+ *   not be j (getClosestDistance and getClosestOrientation are separate minima over the cluster) --
+ *   and starts a new cluster when none qualifies.  Not the nearest cluster, unlike
+ *   mdx_cluster_euclidean.  Clusters never merge.  Kept clusters: size > min_size (:213).
+ *   Rectangle: the members' (x, y) converted to float (node.cpp:382), then exactly
+ *   mdx_cluster_euclidean's rectangle.
+ * Outputs (any may be NULL):
+ *   labels     [n] index of the vector's cluster among ALL clusters, creation order; -1 inactive
+ *   num_active number of active vectors
+ *   num_all    number of all clusters
+ *   kept       [<= max_kept] ids (into the above) of clusters with size > min_size, ascending
+ *   rects      [<= max_kept][4] x, y, width, height of each kept cluster
+ *   num_kept   number of kept clusters (may exceed max_kept; only max_kept are written)
+ * n == 0, or no active vector, is MDX_OK with zero clusters.  MDX_EINVAL: a null context; n or
+ * max_kept negative; n > MDX_VCLUSTER_MAX_POINTS; vectors NULL with n > 0; a non-finite component; a
+ * NaN threshold; unknown flag bits.  A threshold <= 0 is valid: every active vector is its own
+ * cluster.  Every pair test and the first-fit resolution run on the device (3 * ceil(active / 256) - 1
+ * launches); angles, compaction, sizes, ranks and rectangles are O(n) on the host around the call's
+ * one synchronising copy.  Scratch belongs to the context and only grows.  Synchronous.
+ */
+#define MDX_VCLUSTER_ABS_INT 1
+#define MDX_VCLUSTER_MAX_POINTS 131072   /* covers 4K at pixel_step 10 (82,944) */
+int mdx_cluster_vectors(mdx_ctx* ctx, const double* vectors, int n, double distance_threshold,
+                        double angular_threshold, int min_size /* reference: 5 */, int flags, int32_t* labels,
+                        int* num_active, int* num_all, int32_t* kept, int32_t* rects, int max_kept,
+                        int* num_kept);
 
 /*
  * The motion mask labelled into regions: the pair path's mask turned into

@@ -28,6 +28,8 @@ FIT_FIRST4, FIT_EXTERNAL, FIT_RANSAC = 0, 1, 2
 SUBSPACE_F64, SUBSPACE_F32 = 0, 1
 CLUSTER_MAX_POINTS = 262144   # include/mdx.h MDX_CLUSTER_MAX_POINTS
 REGIONS_OPEN3 = 1             # include/mdx.h MDX_REGIONS_OPEN3
+VCLUSTER_ABS_INT = 1          # include/mdx.h MDX_VCLUSTER_ABS_INT
+VCLUSTER_MAX_POINTS = 131072  # include/mdx.h MDX_VCLUSTER_MAX_POINTS
 
 # every symbol include/mdx.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -41,14 +43,14 @@ EXPORTED = [
     "mdx_ring_push", "mdx_ring_trajectory", "mdx_ring_reset", "mdx_input_ready",
     "mdx_host_alloc", "mdx_host_free", "mdx_probe_stream3_dev", "mdx_lk_fallbacks",
     "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
-    "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions",
+    "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions", "mdx_cluster_vectors",
 ]
-ABI_VERSION = 7   # include/mdx.h MDX_ABI_VERSION
+ABI_VERSION = 8   # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_internal.h", "mdx_ctx.h", "mdx_dev.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp",
            "mdx_post.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_regions.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_regions.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -233,6 +235,9 @@ def lib() -> C.CDLL:
     L.mdx_cluster_euclidean.argtypes = [vp, vp, C.c_int, C.c_double, C.c_int, vp, C.POINTER(C.c_int), vp, vp, C.c_int,
                                         C.POINTER(C.c_int)]
     L.mdx_cluster_euclidean.restype = C.c_int
+    L.mdx_cluster_vectors.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int), vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.mdx_cluster_vectors.restype = C.c_int
     L.mdx_mask_regions_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp,
                                        C.c_int, vp, vp, vp, vp]
     L.mdx_mask_regions_dev.restype = C.c_int

@@ -76,6 +76,17 @@ class ClusterResult:
 
 
 @dataclass
+class VectorClusterResult:
+    """Flow vectors clustered by distance and angle (include/mdx.h mdx_cluster_vectors)."""
+    labels: np.ndarray          # (n,) int32: the vector's cluster among all clusters, creation order; -1 inactive
+    num_active: int             # vectors with a non-zero flow
+    num_all: int                # number of all clusters
+    kept: np.ndarray            # (num_kept,) int32: ids of the clusters with size > min_size, ascending
+    rects: np.ndarray           # (num_kept, 4) int32: x, y, width, height of each kept cluster (cv::Rect)
+    num_kept: int = 0           # all kept clusters, also when max_kept cut kept / rects short
+
+
+@dataclass
 class RegionResult:
     """The motion mask labelled into regions (include/mdx.h mdx_mask_regions)."""
     regions: np.ndarray         # (min(num_kept, max_regions), 8) int32: x, y, width, height, area, seed_x, seed_y, id
@@ -280,6 +291,25 @@ class Context:
                                                 C.byref(nkept)))
         m = min(nkept.value, cap)
         return ClusterResult(labels, nall.value, kept[:m].copy(), rects[:m].copy(), nkept.value)
+
+    # -- first-fit clustering by distance and angle (drop-in for FlowClusterer::getClusters + boundingRect)
+    def cluster_vectors(self, vectors: np.ndarray, distance_threshold: float, angular_threshold: float,
+                        min_size: int = 5, abs_int: bool = False) -> "VectorClusterResult":
+        """vectors: (n, 4) float64 (x, y, dx, dy) in the reference's visiting order (image rows outer).
+        abs_int: MDX_VCLUSTER_ABS_INT, the angular distance truncated as the reference's int abs does."""
+        vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, 4)
+        n = vec.shape[0]
+        cap = n // (max(int(min_size), 0) + 1)        # a kept cluster has more than min_size vectors
+        labels = np.zeros(n, np.int32)
+        kept = np.zeros(cap, np.int32)
+        rects = np.zeros((cap, 4), np.int32)
+        nact, nall, nkept = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(lib().mdx_cluster_vectors(self._h, _ptr(vec), n, float(distance_threshold), float(angular_threshold),
+                                              int(min_size), _lib.VCLUSTER_ABS_INT if abs_int else 0, _ptr(labels),
+                                              C.byref(nact), C.byref(nall), _ptr(kept), _ptr(rects), cap,
+                                              C.byref(nkept)))
+        m = min(nkept.value, cap)
+        return VectorClusterResult(labels, nact.value, nall.value, kept[:m].copy(), rects[:m].copy(), nkept.value)
 
     # -- the motion mask labelled into regions (getMotionContours' recipe: opening, 8-connected blobs, boundingRect)
     def mask_regions(self, mask: np.ndarray, open3: bool = True, min_area: int = 1, max_regions: int | None = None,

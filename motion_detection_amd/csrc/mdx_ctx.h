@@ -119,6 +119,10 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf straj, sdata, sq, scnt, scols, sres, sout, sbest;      // subspace RANSAC
     DevBuf clpts, clbest, clroot;            // clusterEuclidean: points, running keys, roots
     std::vector<int32_t> cl_host;            // its host side (roots, ranks, sizes, boxes): only ever grows
+    DevBuf vcpts, vcroot, vcrows, vcq;       // getClusters: (x, y, angle) planes, roots, scan rows, qscan + cand
+    std::vector<double> vc_host;             // its staging of the active vectors' planes: only ever grows
+    std::vector<float> vc_pts;               // the active vectors' (x, y) as float, for the rectangles
+    std::vector<int32_t> vc_idx;             // active vector -> input index, then the compact labels
     DevBuf rgscr;                            // mdx_mask_regions_dev: labels, block counts, component records
     DevBuf rgin, rgout;                      // mdx_mask_regions (host entry): the mask, every output
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)

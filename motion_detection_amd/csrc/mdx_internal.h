@@ -1,5 +1,5 @@
 // mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
-// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_regions.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_regions.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
 // mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
@@ -225,6 +225,14 @@ hipError_t launch_subspace(hipStream_t s, const float* traj, int N, int T, int d
 constexpr int kClB = 256;    // points per block (= threads of k_cluster_step)
 hipError_t launch_cluster(hipStream_t s, const float* pts, int N, uint32_t slim, unsigned long long* best,
                           int32_t* root);
+// First-fit clustering of flow vectors by distance and angle (getClusters, mdx_vcluster.hip): root[i] =
+// index of the first vector of active vector i's cluster.  xyt: [3][nA] doubles (x, y, angle in
+// [0, 2 pi]) of the nA active vectors; slim: a squared distance s joins iff s <= slim (< 0: nothing
+// joins); athr: the angular threshold; abs_int: MDX_VCLUSTER_ABS_INT.  Scratch: rows
+// (vcluster_rows_bytes(nA)), qscan [kClB] and cand [kClB][32] words.  3 * ceil(nA / kClB) - 1 launches on s.
+size_t vcluster_rows_bytes(int nA);
+hipError_t launch_vcluster(hipStream_t s, const double* xyt, int nA, double slim, double athr, int abs_int,
+                           uint32_t* rows, uint32_t* qscan, uint32_t* cand, int32_t* root);
 // Trajectory tracking (calculateOpticalFlowTrajectory): grid init and the per-pass point update.
 hipError_t launch_traj_init(hipStream_t s, int npts, int ny, int pixel_step, int nimg, float* cur, float* traj,
                             int* tlen, int* num, int* flag = nullptr);

@@ -93,6 +93,55 @@ extern "C" int mdx_fit_subspace(mdx_ctx* c, const float* traj, int ntraj, int tr
     return MDX_OK;
 }
 
+// What follows the one copy that brings root[] back, O(N) on the host: clusters in creation order =
+// roots in ascending order (a root precedes its members); ranks, sizes, each kept cluster's
+// boundingRect.  cl: the context's [7 N] host block whose first N entries are the roots.
+static int clusters_from_roots(mdx_ctx* c, const char* who, const float* points, size_t N, int32_t* cl, int min_size,
+                               int32_t* labels, int* num_all, int32_t* kept, int32_t* rects, int max_kept,
+                               int* num_kept)
+{
+    int32_t* root = cl;                           // [N] each: root, rank of a root, size, xmin, ymin, xmax, ymax
+    int32_t *rank = root + N, *size = rank + N, *x0 = size + N, *y0 = x0 + N, *x1 = y0 + N, *y1 = x1 + N;
+    int nall = 0;
+    for (size_t i = 0; i < N; i++) {
+        const int32_t r = root[i];
+        if (r < 0 || (size_t)r > i || root[r] != r)
+            return set_err(c, MDX_EHIP, "%s: inconsistent root %d of point %zu", who, r, i);
+        // cv::Mat(cluster).copyTo(vector<cv::Point>): saturate_cast<int>(float) = cvRound, half to even
+        const int32_t xi = (int32_t)std::lrint((double)points[2 * i]), yi = (int32_t)std::lrint((double)points[2 * i + 1]);
+        if ((size_t)r == i) {
+            rank[i] = nall++;
+            size[i] = 1;
+            x0[i] = x1[i] = xi;
+            y0[i] = y1[i] = yi;
+        } else {
+            size[r]++;
+            x0[r] = std::min(x0[r], xi);
+            x1[r] = std::max(x1[r], xi);
+            y0[r] = std::min(y0[r], yi);
+            y1[r] = std::max(y1[r], yi);
+        }
+        if (labels) labels[i] = rank[r];
+    }
+    int nk = 0;
+    for (size_t i = 0; i < N; i++) {
+        if ((size_t)root[i] != i || size[i] <= min_size) continue;
+        if (nk < max_kept) {
+            if (kept) kept[nk] = rank[i];
+            if (rects) {                          // boundingRect of integer points
+                rects[4 * nk] = x0[i];
+                rects[4 * nk + 1] = y0[i];
+                rects[4 * nk + 2] = (int32_t)((uint32_t)x1[i] - (uint32_t)x0[i] + 1u);
+                rects[4 * nk + 3] = (int32_t)((uint32_t)y1[i] - (uint32_t)y0[i] + 1u);
+            }
+        }
+        nk++;
+    }
+    if (num_all) *num_all = nall;
+    if (num_kept) *num_kept = nk;
+    return MDX_OK;
+}
+
 // clusterEuclidean (flow_clusterer.cpp:231-269) + boundingRect per kept cluster
 // (optical_flow_visualizer.cpp:230-236).  The O(N^2) key minimisation runs on the device
 // (mdx_cluster.hip) and leaves root[i], the first point of i's cluster; everything after it is O(N)
@@ -130,52 +179,89 @@ extern "C" int mdx_cluster_euclidean(mdx_ctx* c, const float* points, int npoint
     const int rc = ensure_all(c, {{&c->clpts, N * 8}, {&c->clbest, N * 8}, {&c->clroot, N * 4}});
     if (rc != MDX_OK) return rc;
     if (c->cl_host.size() < 7 * N) c->cl_host.resize(7 * N);
-    int32_t* root = c->cl_host.data();            // [N] each: root, rank of a root, size, xmin, ymin, xmax, ymax
-    int32_t *rank = root + N, *size = rank + N, *x0 = size + N, *y0 = x0 + N, *x1 = y0 + N, *y1 = x1 + N;
+    int32_t* root = c->cl_host.data();
     hipStream_t s = c->stream;
     HIP_OR_RETURN(c, hipMemcpyAsync(c->clpts.p, points, N * 8, hipMemcpyHostToDevice, s));
     HIP_OR_RETURN(c, launch_cluster(s, c->clpts.as<float>(), npoints, slim, c->clbest.as<unsigned long long>(),
                                     c->clroot.as<int32_t>()));
     HIP_OR_RETURN(c, hipMemcpyAsync(root, c->clroot.p, N * 4, hipMemcpyDeviceToHost, s));
     HIP_OR_RETURN(c, hipStreamSynchronize(s));
-    // clusters in creation order = roots in ascending order; a root precedes its members
-    int nall = 0;
-    for (size_t i = 0; i < N; i++) {
-        const int32_t r = root[i];
-        if (r < 0 || (size_t)r > i || root[r] != r)
-            return set_err(c, MDX_EHIP, "mdx_cluster_euclidean: inconsistent root %d of point %zu", r, i);
-        // cv::Mat(cluster).copyTo(vector<cv::Point>): saturate_cast<int>(float) = cvRound, half to even
-        const int32_t xi = (int32_t)std::lrint((double)points[2 * i]), yi = (int32_t)std::lrint((double)points[2 * i + 1]);
-        if ((size_t)r == i) {
-            rank[i] = nall++;
-            size[i] = 1;
-            x0[i] = x1[i] = xi;
-            y0[i] = y1[i] = yi;
-        } else {
-            size[r]++;
-            x0[r] = std::min(x0[r], xi);
-            x1[r] = std::max(x1[r], xi);
-            y0[r] = std::min(y0[r], yi);
-            y1[r] = std::max(y1[r], yi);
-        }
-        if (labels) labels[i] = rank[r];
+    return clusters_from_roots(c, "mdx_cluster_euclidean", points, N, root, min_size, labels, num_all, kept, rects,
+                               max_kept, num_kept);
+}
+
+// getClusters (flow_clusterer.cpp:178-227) + boundingRect per kept cluster (node.cpp:376-395).  The
+// host does the O(n) work in front -- which vectors are active, each one's angle by libm
+// (vector_cluster.cpp:131-139), the distance limit s* -- and behind (clusters_from_roots); every pair
+// test and the whole first-fit resolution run on the device (mdx_vcluster.hip).
+extern "C" int mdx_cluster_vectors(mdx_ctx* c, const double* vectors, int n, double thr, double athr, int min_size,
+                                   int flags, int32_t* labels, int* num_active, int* num_all, int32_t* kept,
+                                   int32_t* rects, int max_kept, int* num_kept)
+{
+    if (!c) return MDX_EINVAL;
+    if (n < 0 || max_kept < 0 || (n > 0 && !vectors)) return set_err(c, MDX_EINVAL, "mdx_cluster_vectors: bad argument");
+    if (n > MDX_VCLUSTER_MAX_POINTS)
+        return set_err(c, MDX_EINVAL, "mdx_cluster_vectors: more than %d vectors", MDX_VCLUSTER_MAX_POINTS);
+    if (std::isnan(thr) || std::isnan(athr)) return set_err(c, MDX_EINVAL, "mdx_cluster_vectors: a threshold is NaN");
+    if (flags & ~MDX_VCLUSTER_ABS_INT) return set_err(c, MDX_EINVAL, "mdx_cluster_vectors: unknown flag bits 0x%x", flags);
+    for (size_t i = 0; i < (size_t)4 * n; i++)
+        if (!std::isfinite(vectors[i]))
+            return set_err(c, MDX_EINVAL, "mdx_cluster_vectors: vector %zu has a non-finite component", i / 4);
+    if (num_active) *num_active = 0;
+    if (num_all) *num_all = 0;
+    if (num_kept) *num_kept = 0;
+    // active: fabs(dx) > 0 || fabs(dy) > 0 (:185); the others are skipped
+    size_t N = 0;
+    for (int i = 0; i < n; i++) N += vectors[4 * i + 2] != 0.0 || vectors[4 * i + 3] != 0.0;
+    if (labels)
+        for (int i = 0; i < n; i++) labels[i] = -1;
+    if (N == 0) return MDX_OK;
+    if (c->vc_host.size() < 3 * N) c->vc_host.resize(3 * N);
+    if (c->vc_pts.size() < 2 * N) c->vc_pts.resize(2 * N);
+    if (c->vc_idx.size() < 2 * N) c->vc_idx.resize(2 * N);
+    if (c->cl_host.size() < 7 * N) c->cl_host.resize(7 * N);
+    double *hx = c->vc_host.data(), *hy = hx + N, *ht = hy + N;
+    float* pts = c->vc_pts.data();
+    int32_t *idx = c->vc_idx.data(), *lab = idx + N;
+    size_t k = 0;
+    for (int i = 0; i < n; i++) {
+        const double* v = vectors + 4 * (size_t)i;
+        if (!(v[2] != 0.0 || v[3] != 0.0)) continue;
+        hx[k] = v[0];
+        hy[k] = v[1];
+        double ang = std::atan2(v[3], v[2]);      // getAngle (:131-139)
+        if (ang < 0.0) ang += 2 * M_PI;
+        ht[k] = ang;
+        pts[2 * k] = (float)v[0];                 // cv::Point2f(vec[0], vec[1]) (node.cpp:382)
+        pts[2 * k + 1] = (float)v[1];
+        idx[k++] = i;
     }
-    int nk = 0;
-    for (size_t i = 0; i < N; i++) {
-        if ((size_t)root[i] != i || size[i] <= min_size) continue;
-        if (nk < max_kept) {
-            if (kept) kept[nk] = rank[i];
-            if (rects) {                          // boundingRect of integer points
-                rects[4 * nk] = x0[i];
-                rects[4 * nk + 1] = y0[i];
-                rects[4 * nk + 2] = (int32_t)((uint32_t)x1[i] - (uint32_t)x0[i] + 1u);
-                rects[4 * nk + 3] = (int32_t)((uint32_t)y1[i] - (uint32_t)y0[i] + 1u);
-            }
-        }
-        nk++;
+    // sqrt(s) < thr as s <= s*: s* = the largest double that passes (sqrt is monotonic); -1: none does
+    double slim = -1.0;
+    if (thr > 0.0) {
+        double f = std::min(thr * thr, DBL_MAX);
+        while (f < DBL_MAX && std::sqrt(std::nextafter(f, INFINITY)) < thr) f = std::nextafter(f, INFINITY);
+        while (f > 0.0 && !(std::sqrt(f) < thr)) f = std::nextafter(f, 0.0);
+        if (std::sqrt(f) < thr) slim = f;
     }
-    if (num_all) *num_all = nall;
-    if (num_kept) *num_kept = nk;
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const int rc = ensure_all(c, {{&c->vcpts, N * 24}, {&c->vcroot, N * 4}, {&c->vcrows, vcluster_rows_bytes((int)N)},
+                                  {&c->vcq, (size_t)kClB * 33 * 4}});
+    if (rc != MDX_OK) return rc;
+    int32_t* root = c->cl_host.data();
+    hipStream_t s = c->stream;
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->vcpts.p, hx, N * 24, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, launch_vcluster(s, c->vcpts.as<double>(), (int)N, slim, athr, flags & MDX_VCLUSTER_ABS_INT,
+                                     c->vcrows.as<uint32_t>(), c->vcq.as<uint32_t>(), c->vcq.as<uint32_t>() + kClB,
+                                     c->vcroot.as<int32_t>()));
+    HIP_OR_RETURN(c, hipMemcpyAsync(root, c->vcroot.p, N * 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    const int frc = clusters_from_roots(c, "mdx_cluster_vectors", pts, N, root, min_size, labels ? lab : nullptr,
+                                        num_all, kept, rects, max_kept, num_kept);
+    if (frc != MDX_OK) return frc;
+    if (labels)
+        for (size_t a = 0; a < N; a++) labels[idx[a]] = lab[a];
+    if (num_active) *num_active = (int)N;
     return MDX_OK;
 }
 

@@ -15,7 +15,17 @@ cv::Rect (optical_flow_visualizer.cpp:223-240) that MotionLogger::writeBoundingB
 * returns the clusters with more than 5 points (:263) as (n_k, 2) float32 arrays, in creation
   order, members in input order, like the reference's vector<vector<Point2f>>.
 
-All pair distances run on the MI355X through libmdx.so (mdx_cluster_euclidean); there is no CPU
+With egomotion off the node clusters the last trajectory pass's Vec4d image instead
+(getClusters, flow_clusterer.cpp:178-227, node.cpp:375): first fit by distance and angle.
+
+    clusters = fc.getClusters(optical_flow_vectors, pixel_step, distance_threshold, angular_threshold)
+
+* flow_vectors: the (h, w, 4) float64 Vec4d image; its grid is visited in the reference's order,
+  image rows outer (y-major), and only vectors with a non-zero flow take part.
+* returns the clusters with more than 5 vectors (:213) as (n_k, 4) float64 arrays, in creation
+  order, members in visiting order, like the reference's vector<vector<Vec4d>>.
+
+All pair tests run on the MI355X through libmdx.so (mdx_cluster_euclidean, mdx_cluster_vectors); there is no CPU
 fallback.  Restated from the source; unpinned against a real build (no OpenCV 2.4 to compare with):
 the copyTo conversion (cvRound) and boundingRect in particular.
 """
@@ -23,7 +33,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .context import ClusterResult, Context
+from .context import ClusterResult, Context, VectorClusterResult
 
 MIN_SIZE = 5          # clusters.at(i).size() > 5 (flow_clusterer.cpp:263)
 
@@ -51,6 +61,17 @@ def bounding_rects(clusters) -> list:
     return out
 
 
+def grid_vectors(flow_vectors, pixel_step: int) -> np.ndarray:
+    """The Vec4d image's grid as getClusters visits it (flow_clusterer.cpp:180-184): rows i = 0,
+    pixel_step, .. outer, columns j inner -- y-major, unlike the x-major grid of the flow entries.
+    (n, 4) float64."""
+    img = np.asarray(flow_vectors, dtype=np.float64)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("flow_vectors must be (h, w, 4)")
+    ps = int(pixel_step)
+    return np.ascontiguousarray(img[::ps, ::ps]).reshape(-1, 4)
+
+
 class FlowClusterer:
     def __init__(self, device: int = 0, context: Context | None = None):
         """context: an existing Context to run on (not closed by this object); else one is created
@@ -58,7 +79,7 @@ class FlowClusterer:
         self._device = device
         self._ctx = context
         self._own = context is None
-        self.last: ClusterResult | None = None
+        self.last: ClusterResult | VectorClusterResult | None = None
 
     def clusterEuclidean(self, points, distance_threshold: float) -> list:
         pts = np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, 2)
@@ -67,6 +88,16 @@ class FlowClusterer:
         res = self._ctx.cluster_euclidean(pts, float(distance_threshold), MIN_SIZE)
         self.last = res
         return clusters_from_labels(pts, res.labels, res.kept)
+
+    def getClusters(self, flow_vectors, pixel_step: int, distance_threshold: float, angular_threshold: float,
+                    abs_int: bool = False) -> list:
+        """abs_int: the reference's int abs on the angular distance (include/mdx.h MDX_VCLUSTER_ABS_INT)."""
+        vec = grid_vectors(flow_vectors, pixel_step)
+        if self._ctx is None:
+            self._ctx = Context(self._device, 64, 64, 1)
+        res = self._ctx.cluster_vectors(vec, float(distance_threshold), float(angular_threshold), MIN_SIZE, abs_int)
+        self.last = res
+        return [vec[res.labels == int(k)] for k in res.kept]
 
     def close(self):
         if self._ctx is not None and self._own:

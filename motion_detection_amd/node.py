@@ -22,9 +22,12 @@ calculateOpticalFlowTrajectory (:295, runOpticalFlowTrajectory :94-110); with eg
 least one complete trajectory, fitSubspace(trajectories, outlier_points, num_motions, sigma) follows
 (:341-348), and, when the ``distance_threshold`` parameter is set, clusterEuclidean on its outlier
 points (:355) and each kept cluster's bounding rectangle (optical_flow_visualizer.cpp:223-240), the
-rectangles MotionLogger::writeBoundingBox logs under ``log_contours`` (:431-434).  ``on_result``
-then receives a LiveResult.  ``live_chain=False`` drives the pair path
-the north star names (runOpticalFlow, :76-92) on the ring's last two frames, the only one that
+rectangles MotionLogger::writeBoundingBox logs under ``log_contours`` (:431-434).  Without egomotion
+the ring holds 2 frames and, when ``distance_threshold`` and ``angular_threshold`` are both set,
+FlowClusterer::getClusters runs on the trajectory pass's Vec4d image (:375, first fit by distance and
+angle; ``abs_int`` selects the reference's truncating abs); each kept cluster's points
+(:376-386) and rectangle follow the same way.  ``on_result`` then receives a LiveResult.
+``live_chain=False`` drives the pair path the north star names (runOpticalFlow, :76-92) on the ring's last two frames, the only one that
 produces the motion mask.  With ``region_min_area`` set, that mask is labelled into regions on the
 device (BackgroundSubtractor::getMotionContours' recipe: ``region_open`` is its 3x3 opening) and the
 FlowResult carries them as ``regions``; under ``log_contours`` each kept region's rectangle is logged
@@ -76,7 +79,8 @@ def to_rgb8(msg: Image) -> np.ndarray:
 @dataclass
 class LiveResult:
     """Outputs of the live branch (node.cpp:266-355, :431-434): trajectories, fitSubspace's outliers
-    and, when clustering is on (egomotion and a distance_threshold), their clusters and rectangles."""
+    and, when clustering is on (egomotion and a distance_threshold), their clusters and rectangles;
+    without egomotion and with both thresholds, getClusters' clusters of the flow vectors instead."""
     num_vectors: int
     optical_flow_vectors: np.ndarray     # (h, w, 4) Vec4d image (runOpticalFlowTrajectory :97-99)
     trajectories: list                   # complete trajectories, (T, 2) each
@@ -85,6 +89,7 @@ class LiveResult:
     clusters: list = field(default_factory=list)     # clusterEuclidean's kept clusters, (n_k, 2) float32 each
     rectangles: list = field(default_factory=list)   # their (x, y, width, height), as cv::Rect
     frame_number: int = 0                # global_frame_count_ of this callback (the log's frame column)
+    vector_clusters: list = field(default_factory=list)   # getClusters' kept clusters, (n_k, 4) float64 each (no egomotion)
 
 
 class MotionDetectionNode:
@@ -97,6 +102,9 @@ class MotionDetectionNode:
                        # clustering: distance_threshold has no default in the reference (node.cpp:34;
                        # the launch files set it) -- None leaves the stage off; log_contours false (:39), log_path "" (:42)
                        "distance_threshold": None, "log_contours": False, "log_path": "",
+                       # getClusters (no egomotion, :375): angular_threshold has no default either -- None
+                       # leaves the stage off; abs_int: the angular distance truncated (int abs)
+                       "angular_threshold": None, "abs_int": False,
                        # the pair path's mask labelled into regions (getMotionContours' recipe):
                        # region_min_area None leaves the stage off; region_open is the 3x3 opening
                        "region_min_area": None, "region_open": True}
@@ -172,8 +180,25 @@ class MotionDetectionNode:
                     self.logger = MotionLogger(self.params["log_path"])
                 for k, rect in enumerate(rectangles):
                     self.logger.writeBoundingBox(rect, self.global_frame_count, k)
+        vector_clusters: list = []
+        athr = self.params.get("angular_threshold")
+        if trajectories and not self.params["egomotion"] and thr is not None and athr is not None:
+            from .flow_clusterer import FlowClusterer, bounding_rects
+            if self.fc is None:
+                self.fc = FlowClusterer(device=self._device)
+            vector_clusters = self.fc.getClusters(vec, int(self.params["pixel_step"]), float(thr), float(athr),
+                                                  bool(self.params.get("abs_int", False)))          # :375
+            clusters = [c[:, :2].astype(np.float32) for c in vector_clusters]                         # :376-386
+            rectangles = bounding_rects(clusters)                                                     # :395
+            if self.params.get("log_contours") and self.params.get("log_path"):                       # :431-434
+                if self.logger is None:
+                    from .formats import MotionLogger
+                    self.logger = MotionLogger(self.params["log_path"])
+                for k, rect in enumerate(rectangles):
+                    self.logger.writeBoundingBox(rect, self.global_frame_count, k)
         self.frames_processed += 1
-        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters, rectangles, self.global_frame_count)
+        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters, rectangles, self.global_frame_count,
+                         vector_clusters)
         if self.on_result is not None:
             self.on_result(res)
         return res
