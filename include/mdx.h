@@ -157,7 +157,8 @@ int mdx_input_ready(mdx_ctx* ctx, void* hip_event);
 
 /*
  * Synchronous host-buffer entry: the direct replacement of calculateOpticalFlow.
- *   img1, img2  w x h frames, row pitch `stride` bytes, format `fmt`.
+ *   img1, img2  w x h frames, row pitch `stride` bytes, format `fmt`.  Only w * channels bytes
+ *               of the last row are read: a pitched view (a cv::Mat ROI) may end with its last pixel.
  *   next_pts    [2*npts] float  LK output positions (x-major grid order)        or NULL
  *   status      [npts]   uint8  LK status                                       or NULL
  *   vectors     [4*npts] double the reference's Vec4d per grid point:
@@ -249,7 +250,8 @@ int mdx_band_fit_warp_dev(mdx_ctx* ctx, int nrec, const mdx_band_cand* d_cands, 
  * Trajectory tracking: replaces OpticalFlowCalculator::calculateOpticalFlowTrajectory
  * (optical_flow_calculator.h:20-21, optical_flow_calculator.cpp:133-257), the node's live caller
  * (motion_detection_node.cpp:94-110 over 2*num_motions+1 frames, :241).  Synchronous.
- *   imgs        nimg >= 2 host frames, each w x h, row pitch `stride`, format `fmt`.
+ *   imgs        nimg >= 2 host frames, each w x h, row pitch `stride`, format `fmt`.  Only
+ *               w * channels bytes of a frame's last row are read (as in mdx_flow_warp_diff).
  * The pixel_step grid is tracked through the nimg-1 consecutive pairs; each pass starts from the
  * points the previous one left (a point moves only when tracked and strictly inside the 10-px
  * border, :207-216).  Outputs (any may be NULL; npts = mdx_grid_count(w, h, pixel_step)):
@@ -293,7 +295,8 @@ size_t mdx_trajectory_layout(int npts, int nimg, size_t offsets[4]);
  *   mdx_ring_reset       empty the ring.
  * mdx_ring_push only queues the upload and the pyramid on the context's stream: the frame's host
  * memory (page-locked memory is read by DMA after the call returns) must stay unchanged until the
- * next mdx_ring_trajectory or mdx_sync returns.
+ * next mdx_ring_trajectory or mdx_sync returns.  Only w * channels bytes of the frame's last row
+ * are read (as in mdx_flow_warp_diff).
  */
 int mdx_ring_push(mdx_ctx* ctx, const uint8_t* img, int w, int h, int stride, int fmt, int keep);
 int mdx_ring_trajectory(mdx_ctx* ctx, float* traj, int32_t* traj_len, float* start_pts, double* vectors,

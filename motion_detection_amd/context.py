@@ -18,6 +18,30 @@ def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _frame_view(img) -> np.ndarray:
+    """A uint8 frame as the C-ABI reads it.  A row-pitched view (pixels and channels adjacent, a
+    positive row stride of at least one row's bytes, e.g. a crop of a larger image) is kept as it is
+    and goes down with its pitch; anything else is copied to a packed array."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8:
+        a = a.astype(np.uint8)
+    if a.ndim not in (2, 3) or a.shape[0] == 0 or a.shape[1] == 0:
+        return np.ascontiguousarray(a)
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    inner = a.strides[1] == ch and (a.ndim == 2 or a.strides[2] == 1)
+    if inner and a.strides[0] >= a.shape[1] * ch:
+        return a
+    return np.ascontiguousarray(a)
+
+
+def _frame_views(images) -> list:
+    """_frame_view of each frame; frames of different pitches are all packed (the entries take one)."""
+    views = [_frame_view(im) for im in images]
+    if any(v.strides[0] != views[0].strides[0] for v in views if v.shape == views[0].shape):
+        views = [np.ascontiguousarray(v) for v in views]
+    return views
+
+
 def grid_count(w: int, h: int, pixel_step: int) -> int:
     return lib().mdx_grid_count(w, h, pixel_step)
 
@@ -161,8 +185,7 @@ class Context:
     # -- host entry (drop-in for calculateOpticalFlow)
     def flow_warp_diff(self, img1: np.ndarray, img2: np.ndarray, fmt: int | None = None, want_mask: bool = True,
                        H_external: np.ndarray | None = None) -> FlowResult:
-        img1 = np.ascontiguousarray(img1, dtype=np.uint8)
-        img2 = np.ascontiguousarray(img2, dtype=np.uint8)
+        img1, img2 = _frame_views([img1, img2])
         if img1.shape != img2.shape:
             raise ValueError("frames must have the same shape")
         h, w = img1.shape[:2]
@@ -184,7 +207,7 @@ class Context:
 
     # -- trajectory tracking (drop-in for calculateOpticalFlowTrajectory)
     def flow_trajectory(self, images, fmt: int | None = None) -> "TrajectoryResult":
-        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        imgs = _frame_views(images)
         if len(imgs) < 2 or any(im.shape != imgs[0].shape for im in imgs):
             raise ValueError("need >= 2 frames of one shape")
         h, w = imgs[0].shape[:2]
@@ -206,7 +229,7 @@ class Context:
     def ring_push(self, image: np.ndarray, keep: int, fmt: int | None = None) -> int:
         """Append one frame (pyramided once, on the device) and keep at most `keep` frames.
         Returns the number of frames held."""
-        im = np.ascontiguousarray(image, dtype=np.uint8)
+        im = _frame_view(image)
         h, w = im.shape[:2]
         if fmt is None:
             fmt = _lib.FMT_GRAY8 if im.ndim == 2 else _lib.FMT_RGB8

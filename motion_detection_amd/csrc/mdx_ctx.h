@@ -217,13 +217,21 @@ inline int ensure_all(mdx_ctx* c, std::initializer_list<std::pair<DevBuf*, size_
     return MDX_OK;
 }
 
+// Guard bytes kept free after the last pyramid slab of an allocation (one row of the last level).
+// The lowest row an LK window reads is iny + kWin <= h - 1 + kWin, the level's last padding row
+// (DESIGN.md §3.1): k_lk's plain loads of the next frame's window end exactly with the last level
+// of the last slab, with no margin.  The guard keeps a window one row lower -- a bound off by one --
+// inside the allocation instead of past it.  (k_lk_iter's J rows go through a range-checked
+// descriptor as well.)
+inline size_t slab_slack_bytes(const Geometry& g) { return ((size_t)g.lv[g.nlev - 1].pitch + 255) / 256 * 256; }
+
 // With call pipelining the pyramid slabs hold two halves (ensure_workspace(.., two = true) makes the
 // slab at least twice one call's pyramids); other users take the slab from its start.
 inline size_t pyr_half_bytes(const DevBuf& b) { return b.cap / 2 / 256 * 256; }
 
 inline int ensure_workspace(mdx_ctx* c, const Geometry& g, int batch, bool two)
 {
-    const size_t half = ((size_t)g.img_bytes * batch + 255) / 256 * 256;
+    const size_t half = ((size_t)g.img_bytes * batch + 255) / 256 * 256 + slab_slack_bytes(g);
     return ensure_all(c, {{&c->pyr1, two ? 2 * half : half}, {&c->pyr2, two ? 2 * half : half},
                           {&c->der, (size_t)g.der_words * 4 * batch}, {&c->fits, sizeof(PairFit) * (size_t)batch}});
 }
@@ -239,6 +247,15 @@ inline int check_frame(mdx_ctx* c, const char* who, int w, int h, int stride, in
     const int cn = fmt == MDX_FMT_GRAY8 ? 1 : 3;
     if (stride < w * cn) return set_err(c, MDX_EINVAL, "%s%sstride %d < w*channels %d", who, sep, stride, w * cn);
     return MDX_OK;
+}
+
+// Bytes of a caller's host frame that are the caller's to read: h - 1 whole pitches and the last
+// row's w * channels pixels.  A pitched view (a cv::Mat ROI) ends there, so the host entries copy
+// this much; their device slots stay stride * h apart.
+inline size_t frame_copy_bytes(int w, int h, int stride, int fmt)
+{
+    const int cn = fmt == MDX_FMT_GRAY8 ? 1 : 3;
+    return (size_t)stride * (size_t)(h - 1) + (size_t)w * cn;
 }
 
 // The LkArgs fields every LK of a w x h frame shares: geometry, the full grid and the clamped

@@ -167,7 +167,8 @@ __global__ __launch_bounds__(256) void k_front(FrontArgs a)
         const int spr = nc0 + 1, nslot = NR * spr;
         const float rs = 1.f / (float)spr;
         const uint8_t* rbase = FRAME ? src : slab + a.L0.img_off;
-        const long long rbytes = FRAME ? (long long)h * a.stride : (long long)a.L0.rows * a.L0.pitch;
+        // a mono8 frame ends with its last row's w pixels (a pitched view owns no byte past them)
+        const long long rbytes = FRAME ? (long long)(h - 1) * a.stride + w : (long long)a.L0.rows * a.L0.pitch;
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<uint8_t*>(rbase), (short)0, (int)min(rbytes, (long long)0x7fffffff), 0x00020000);
         const int wave = tid >> 6, wl = tid & 63;

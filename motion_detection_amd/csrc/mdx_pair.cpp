@@ -493,7 +493,8 @@ extern "C" int mdx_flow_warp_diff(mdx_ctx* c, const uint8_t* img1, const uint8_t
     if (c->prm.fit_mode == MDX_FIT_EXTERNAL && !H_external)
         return set_err(c, MDX_EINVAL, "fit_mode EXTERNAL needs H_external");
     HIP_OR_RETURN(c, hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)stride * h;
+    const size_t in_bytes = (size_t)stride * h;                    // device slot
+    const size_t copy_bytes = frame_copy_bytes(w, h, stride, fmt);   // what the caller's frame holds
     const int npts = mdx_grid_count(w, h, c->prm.pixel_step);
     const size_t pts = (size_t)(npts > 0 ? npts : 1);
     if ((rc = ensure_all(c, {{&c->in1, in_bytes}, {&c->in2, in_bytes}, {&c->np, pts * 8}, {&c->st, pts},
@@ -502,8 +503,8 @@ extern "C" int mdx_flow_warp_diff(mdx_ctx* c, const uint8_t* img1, const uint8_t
         return rc;
 
     hipStream_t s = c->stream;
-    HIP_OR_RETURN(c, hipMemcpyAsync(c->in1.p, img1, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_OR_RETURN(c, hipMemcpyAsync(c->in2.p, img2, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->in1.p, img1, copy_bytes, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->in2.p, img2, copy_bytes, hipMemcpyHostToDevice, s));
     if (H_external) HIP_OR_RETURN(c, hipMemcpyAsync(c->Hext.p, H_external, 72, hipMemcpyHostToDevice, s));
     rc = run_pipeline(c, 1, c->in1.as<uint8_t>(), c->in2.as<uint8_t>(), w, h, stride, in_bytes, fmt, c->np.as<float>(),
                       c->st.as<uint8_t>(), vectors ? c->vec.as<double>() : nullptr,

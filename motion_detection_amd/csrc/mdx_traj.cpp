@@ -155,12 +155,13 @@ extern "C" int mdx_flow_trajectory(mdx_ctx* c, const uint8_t* const* imgs, int n
     const Geometry g = make_geometry(w, h, c->prm.max_level);
     if ((rc = ensure_workspace(c, g, npairs, false)) != MDX_OK) return rc;
     c->band_w = c->band_h = 0;   // the slabs are rebuilt: a pending band fit/warp has nothing to read
-    const size_t fbytes = (size_t)stride * h;
+    const size_t fbytes = (size_t)stride * h;                        // device slot
+    const size_t copy_bytes = frame_copy_bytes(w, h, stride, fmt);   // what each caller's frame holds
     if ((rc = ensure(c, c->tin, fbytes * nimg)) != MDX_OK) return rc;
     hipStream_t s = c->stream;
     uint8_t* din = c->tin.as<uint8_t>();
     for (int i = 0; i < nimg; i++)
-        HIP_OR_RETURN(c, hipMemcpyAsync(din + fbytes * i, imgs[i], fbytes, hipMemcpyHostToDevice, s));
+        HIP_OR_RETURN(c, hipMemcpyAsync(din + fbytes * i, imgs[i], copy_bytes, hipMemcpyHostToDevice, s));
     uint8_t* pyr1 = c->pyr1.as<uint8_t>();
     uint8_t* pyr2 = c->pyr2.as<uint8_t>();
     uint32_t* der = c->der.as<uint32_t>();
@@ -188,7 +189,7 @@ static int ring_grow(mdx_ctx* c, const Geometry& g, int cap)
     if (cap <= c->ring_cap) return MDX_OK;
     DevBuf np, nd;   // freed again on any failure exit
     auto fail = [&](const char* what) { return set_err(c, MDX_ENOMEM, "mdx_ring_push: %s", what); };
-    if (!np.alloc((size_t)g.img_bytes * cap)) return fail("hipMalloc(pyramids)");
+    if (!np.alloc((size_t)g.img_bytes * cap + slab_slack_bytes(g))) return fail("hipMalloc(pyramids)");
     if (!nd.alloc((size_t)g.der_words * 4 * cap)) return fail("hipMalloc(derivatives)");
     // the held frames move to slots 0 .. n-1, in order; the context's state changes only once
     // every copy has landed (a failed copy leaves the old ring intact and frees the new buffers)
@@ -249,7 +250,7 @@ extern "C" int mdx_ring_push(mdx_ctx* c, const uint8_t* img, int w, int h, int s
     const size_t fbytes = (size_t)stride * h;
     if ((rc = ensure(c, c->rin, fbytes)) != MDX_OK) return rc;
     hipStream_t s = c->stream;
-    HIP_OR_RETURN(c, hipMemcpyAsync(c->rin.p, img, fbytes, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->rin.p, img, frame_copy_bytes(w, h, stride, fmt), hipMemcpyHostToDevice, s));
     uint8_t* pyr = c->ring_pyr.as<uint8_t>() + (size_t)g.img_bytes * slot;
     uint32_t* der = c->ring_der.as<uint32_t>() + (size_t)g.der_words * slot;
     HIP_OR_RETURN(c, launch_front(s, 1, c->rin.as<uint8_t>(), c->rin.as<uint8_t>(), w, h, stride, (long long)fbytes, fmt,

@@ -156,7 +156,9 @@ int ora_build_pyramid(const uint8_t* gray, int w, int h, int win, int max_level,
     int level;
     for (level = 0; level <= max_level && level < ORA_MAX_LEVELS; level++) {
         int pitch = sw + 2 * win;
-        uint8_t* buf = (uint8_t*)calloc((size_t)pitch * (sh + 2 * win), 1);
+        /* + one guard row and byte, zeroed: a window at inx == w-1 or iny == h-1 (ORA_WHY_TAINT)
+         * ends exactly on the last padding column / row, so the buffer has no margin without it */
+        uint8_t* buf = (uint8_t*)calloc((size_t)pitch * (sh + 2 * win + 1) + 1, 1);
         uint8_t* core = buf + (size_t)win * pitch + win;
         if (level == 0) {
             for (int y = 0; y < sh; y++) memcpy(core + (size_t)y * pitch, gray + (size_t)y * w, (size_t)sw);
@@ -170,7 +172,7 @@ int ora_build_pyramid(const uint8_t* gray, int w, int h, int win, int max_level,
         out->w[level] = sw;
         out->h[level] = sh;
         if (with_deriv) {
-            int16_t* d = (int16_t*)calloc((size_t)pitch * (sh + 2 * win) * 2, sizeof(int16_t));
+            int16_t* d = (int16_t*)calloc(((size_t)pitch * (sh + 2 * win + 1) + 1) * 2, sizeof(int16_t));
             ora_scharr(core, sw, sh, pitch, d + ((size_t)win * pitch + win) * 2, pitch * 2);
             out->deriv[level] = d;  /* border stays 0: BORDER_CONSTANT */
         }
@@ -208,6 +210,7 @@ typedef struct {
     uint8_t* status;
     const ora_params* prm;
     int begin, end;
+    uint16_t* why;   /* optional ORA_WHY_* bits per point, OR-ed in; NULL = off */
 } lk_job;
 
 /*
@@ -244,6 +247,8 @@ static void lk_level_range(const lk_job* jb)
     int16_t* dIwin = (int16_t*)malloc(sizeof(int16_t) * (size_t)win * win * 2);
 
     for (int ptidx = jb->begin; ptidx < jb->end; ptidx++) {
+        uint16_t why = 0;
+#define LK_WHY(bits) do { if (jb->why) jb->why[ptidx] |= (uint16_t)(why | (bits)); } while (0)
         float scale = (float)(1. / (1 << level));
         float px = jb->prev_pts[2 * ptidx] * scale, py = jb->prev_pts[2 * ptidx + 1] * scale;
         float nx, ny;
@@ -256,8 +261,10 @@ static void lk_level_range(const lk_job* jb)
         int ipx = cv_floor_f(px), ipy = cv_floor_f(py);
         if (ipx < -win || ipx >= Iw || ipy < -win || ipy >= Ih) {
             if (level == 0) jb->status[ptidx] = 0;
+            LK_WHY(ORA_WHY_PREV_OOR);
             continue;
         }
+        if (ipx == Iw - 1 || ipy == Ih - 1) why |= ORA_WHY_TAINT;
         float a = px - (float)ipx, b = py - (float)ipy;
         int iw00 = cv_round_f((1.f - a) * (1.f - b) * (float)(1 << W_BITS));
         int iw01 = cv_round_f(a * (1.f - b) * (float)(1 << W_BITS));
@@ -301,18 +308,22 @@ static void lk_level_range(const lk_job* jb)
                        (float)(2 * win * win);
         if (minEig < minEigThr || D < FLT_EPSILON) {
             if (level == 0) jb->status[ptidx] = 0;
+            LK_WHY(ORA_WHY_MIN_EIG);
             continue;
         }
         D = 1.f / D;
 
         nx -= halfw; ny -= halfw;
         float pdx = 0.f, pdy = 0.f;
-        for (int j = 0; j < maxCount; j++) {
+        int j;
+        for (j = 0; j < maxCount; j++) {
             int inx = cv_floor_f(nx), iny = cv_floor_f(ny);
             if (inx < -win || inx >= Jw || iny < -win || iny >= Jh) {
                 if (level == 0) jb->status[ptidx] = 0;
+                why |= j == 0 ? ORA_WHY_NEXT_OOR_FIRST : ORA_WHY_NEXT_OOR_ITER;
                 break;
             }
+            if (inx == Jw - 1 || iny == Jh - 1) why |= ORA_WHY_TAINT;
             a = nx - (float)inx;
             b = ny - (float)iny;
             iw00 = cv_round_f((1.f - a) * (1.f - b) * (float)(1 << W_BITS));
@@ -345,23 +356,27 @@ static void lk_level_range(const lk_job* jb)
             ny += dy;
             jb->next_pts[2 * ptidx] = nx + halfw;
             jb->next_pts[2 * ptidx + 1] = ny + halfw;
-            if ((double)dx * dx + (double)dy * dy <= eps2) break;
+            if ((double)dx * dx + (double)dy * dy <= eps2) { why |= ORA_WHY_EPS; break; }
             if (j > 0 && fabs((double)fabsf(dx + pdx)) < 0.01 && fabs((double)fabsf(dy + pdy)) < 0.01) {
                 jb->next_pts[2 * ptidx] -= dx * 0.5f;
                 jb->next_pts[2 * ptidx + 1] -= dy * 0.5f;
+                why |= ORA_WHY_OSCILLATION;
                 break;
             }
             pdx = dx;
             pdy = dy;
         }
+        if (j == maxCount) why |= ORA_WHY_ITER_CAP;
 
         /* err pass (err is requested at :71): only its final bounds check is observable. */
         if (jb->status[ptidx] && level == 0) {
             float fx = jb->next_pts[2 * ptidx] - halfw, fy = jb->next_pts[2 * ptidx + 1] - halfw;
             int ix = cv_floor_f(fx), iy = cv_floor_f(fy);
-            if (ix < -win || ix >= Jw || iy < -win || iy >= Jh) jb->status[ptidx] = 0;
+            if (ix < -win || ix >= Jw || iy < -win || iy >= Jh) { jb->status[ptidx] = 0; why |= ORA_WHY_FINAL_OOR; }
         }
+        LK_WHY(0);
     }
+#undef LK_WHY
     free(Iwin);
     free(dIwin);
 }
@@ -376,6 +391,13 @@ void ora_lk(const ora_pyramid* prev, const ora_pyramid* next, int max_level,
             const float* prev_pts, float* next_pts, uint8_t* status, int npts,
             const ora_params* prm, int nthreads)
 {
+    ora_lk_why(prev, next, max_level, prev_pts, next_pts, status, npts, prm, nthreads, NULL);
+}
+
+void ora_lk_why(const ora_pyramid* prev, const ora_pyramid* next, int max_level,
+                const float* prev_pts, float* next_pts, uint8_t* status, int npts,
+                const ora_params* prm, int nthreads, uint16_t* why)
+{
     if (nthreads < 1) nthreads = 1;
     for (int i = 0; i < npts; i++) status[i] = 1;
     lk_job* jobs = (lk_job*)malloc(sizeof(lk_job) * (size_t)nthreads);
@@ -385,6 +407,7 @@ void ora_lk(const ora_pyramid* prev, const ora_pyramid* next, int max_level,
             lk_job* jb = &jobs[t];
             jb->prev = prev; jb->next = next; jb->level = level; jb->max_level = max_level;
             jb->prev_pts = prev_pts; jb->next_pts = next_pts; jb->status = status; jb->prm = prm;
+            jb->why = why;
             jb->begin = (int)((long long)npts * t / nthreads);
             jb->end = (int)((long long)npts * (t + 1) / nthreads);
         }
@@ -894,6 +917,15 @@ int ora_calculate_optical_flow(const uint8_t* img1, const uint8_t* img2, int w, 
                                float* next_pts_out, uint8_t* status_out, double* vectors,
                                uint8_t* mask, double* H, double* Hinv, int* fit_status)
 {
+    return ora_calculate_optical_flow_why(img1, img2, w, h, stride, fmt, prm, nthreads, next_pts_out, status_out,
+                                          vectors, mask, H, Hinv, fit_status, NULL);
+}
+
+int ora_calculate_optical_flow_why(const uint8_t* img1, const uint8_t* img2, int w, int h, int stride,
+                                   int fmt, const ora_params* prm, int nthreads,
+                                   float* next_pts_out, uint8_t* status_out, double* vectors,
+                                   uint8_t* mask, double* H, double* Hinv, int* fit_status, uint16_t* why)
+{
     uint8_t* g1 = (uint8_t*)malloc((size_t)w * h);
     uint8_t* g2 = (uint8_t*)malloc((size_t)w * h);
     ora_to_gray(img1, w, h, stride, fmt, g1);
@@ -908,7 +940,8 @@ int ora_calculate_optical_flow(const uint8_t* img1, const uint8_t* img2, int w, 
     ora_pyramid P1, P2;
     int ml = ora_build_pyramid(g1, w, h, prm->win, prm->max_level, 1, &P1);
     ml = ora_build_pyramid(g2, w, h, prm->win, ml, 0, &P2);
-    ora_lk(&P1, &P2, ml, pts1, pts2, st, npts, prm, nthreads);
+    if (why) memset(why, 0, sizeof(uint16_t) * (size_t)npts);
+    ora_lk_why(&P1, &P2, ml, pts1, pts2, st, npts, prm, nthreads, why);
 
     int num = 0;
     float src4[8], dst4[8];
@@ -984,6 +1017,14 @@ int ora_flow_trajectory(const uint8_t* const* imgs, int nimg, int w, int h, int 
                         const ora_params* prm, int nthreads, float* traj, int* traj_len,
                         float* start_pts, double* vectors)
 {
+    return ora_flow_trajectory_why(imgs, nimg, w, h, stride, fmt, prm, nthreads, traj, traj_len, start_pts, vectors,
+                                   NULL);
+}
+
+int ora_flow_trajectory_why(const uint8_t* const* imgs, int nimg, int w, int h, int stride, int fmt,
+                            const ora_params* prm, int nthreads, float* traj, int* traj_len,
+                            float* start_pts, double* vectors, uint16_t* why)
+{
     const int npts = ora_grid_count(w, h, prm->pixel_step);
     const size_t np1 = (size_t)(npts > 0 ? npts : 1);
     float* cur = (float*)malloc(sizeof(float) * 2 * np1);
@@ -993,6 +1034,7 @@ int ora_flow_trajectory(const uint8_t* const* imgs, int nimg, int w, int h, int 
     uint8_t* g1 = (uint8_t*)malloc((size_t)w * h);
     uint8_t* g2 = (uint8_t*)malloc((size_t)w * h);
     ora_grid_points(w, h, prm->pixel_step, cur);
+    if (why) memset(why, 0, sizeof(uint16_t) * (size_t)npts);   /* accumulates over every pass */
     for (int i = 0; i < npts; i++) {
         len[i] = 1;
         if (traj) { traj[(size_t)i * nimg * 2] = cur[2 * i]; traj[(size_t)i * nimg * 2 + 1] = cur[2 * i + 1]; }
@@ -1005,7 +1047,7 @@ int ora_flow_trajectory(const uint8_t* const* imgs, int nimg, int w, int h, int 
         ora_pyramid P1, P2;
         int ml = ora_build_pyramid(g1, w, h, prm->win, prm->max_level, 1, &P1);
         ml = ora_build_pyramid(g2, w, h, prm->win, ml, 0, &P2);
-        ora_lk(&P1, &P2, ml, cur, nxt, st, npts, prm, nthreads);
+        ora_lk_why(&P1, &P2, ml, cur, nxt, st, npts, prm, nthreads, why);
         ora_free_pyramid(&P1);
         ora_free_pyramid(&P2);
         for (int i = 0; i < npts; i++) {

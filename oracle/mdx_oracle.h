@@ -76,6 +76,32 @@ void ora_lk(const ora_pyramid* prev, const ora_pyramid* next, int max_level,
             const float* prev_pts, float* next_pts, uint8_t* status, int npts,
             const ora_params* prm, int nthreads);
 
+/*
+ * Why each point stopped (optional, test diagnostics; every other output is unchanged by it).
+ * `why` is one uint16 per point, OR-ed into over the levels (ora_lk_why does not clear it; the
+ * whole-path entries clear it once, so a trajectory accumulates over its passes).  One bit per way
+ * a level can end, plus ORA_WHY_TAINT: some window the point read sat at ix == w-1 or iy == h-1 of
+ * its level, the last position the bounds test admits.  Its bilinear footprint (x+1, y+1 over a
+ * win x win window) ends on column ix + win = w + win - 1 or row iy + win = h + win - 1: the last
+ * column / row of the win-pixel padding, the very edge of the buffer (one more
+ * pixel in the bounds test, or one fewer in the padding, and the read would leave it).
+ * ora_build_pyramid keeps a zeroed guard row behind each level.  Sticky: the bit is never cleared.
+ */
+enum {
+    ORA_WHY_PREV_OOR = 1 << 0,        /* previous window out of range */
+    ORA_WHY_MIN_EIG = 1 << 1,         /* minEig / determinant reject */
+    ORA_WHY_NEXT_OOR_FIRST = 1 << 2,  /* next window out of range before the first iteration */
+    ORA_WHY_NEXT_OOR_ITER = 1 << 3,   /* the same in mid-iteration */
+    ORA_WHY_EPS = 1 << 4,             /* step below eps */
+    ORA_WHY_OSCILLATION = 1 << 5,     /* oscillation break */
+    ORA_WHY_ITER_CAP = 1 << 6,        /* iteration cap */
+    ORA_WHY_FINAL_OOR = 1 << 7,       /* the level-0 final bounds check cleared the status */
+    ORA_WHY_TAINT = 1 << 8            /* read a window ending on the last padding column / row */
+};
+void ora_lk_why(const ora_pyramid* prev, const ora_pyramid* next, int max_level,
+                const float* prev_pts, float* next_pts, uint8_t* status, int npts,
+                const ora_params* prm, int nthreads, uint16_t* why);
+
 /* 1: JacobiSVDImpl_ with SSE2 VBLAS dot/givensx partial sums (see mdx_oracle.c); 0: scalar (default) */
 void ora_set_svd_vblas(int on);
 /* 1: the LK window / iteration sums and the warp's interior bilinear run the SSE2-intrinsics
@@ -126,6 +152,12 @@ int ora_calculate_optical_flow(const uint8_t* img1, const uint8_t* img2, int w, 
                                float* next_pts, uint8_t* status, double* vectors,
                                uint8_t* mask, double* H, double* Hinv, int* fit_status);
 
+/* The same, with the ORA_WHY_* bits of every point in why[npts] (NULL: off). */
+int ora_calculate_optical_flow_why(const uint8_t* img1, const uint8_t* img2, int w, int h, int stride,
+                                   int fmt, const ora_params* prm, int nthreads,
+                                   float* next_pts, uint8_t* status, double* vectors,
+                                   uint8_t* mask, double* H, double* Hinv, int* fit_status, uint16_t* why);
+
 /*
  * Trajectory tracking (OpticalFlowCalculator::calculateOpticalFlowTrajectory,
  * optical_flow_calculator.cpp:133-257) over nimg >= 2 frames.  Outputs (any may be NULL):
@@ -139,6 +171,10 @@ int ora_calculate_optical_flow(const uint8_t* img1, const uint8_t* img2, int w, 
 int ora_flow_trajectory(const uint8_t* const* imgs, int nimg, int w, int h, int stride, int fmt,
                         const ora_params* prm, int nthreads, float* traj, int* traj_len,
                         float* start_pts, double* vectors);
+/* The same, with the ORA_WHY_* bits of every point accumulated over all passes in why[npts]. */
+int ora_flow_trajectory_why(const uint8_t* const* imgs, int nimg, int w, int h, int stride, int fmt,
+                            const ora_params* prm, int nthreads, float* traj, int* traj_len,
+                            float* start_pts, double* vectors, uint16_t* why);
 
 /*
  * Trajectory subspace RANSAC (OutlierDetector::fitSubspace, outlier_detector.cpp:236-331).

@@ -17,6 +17,14 @@ _lib = None
 
 FMT_GRAY8, FMT_RGB8, FMT_BGR8 = 0, 1, 2
 
+# ORA_WHY_*: why an LK point stopped, one bit per exit, OR-ed over levels and passes (mdx_oracle.h)
+WHY_PREV_OOR, WHY_MIN_EIG, WHY_NEXT_OOR_FIRST, WHY_NEXT_OOR_ITER = 1, 2, 4, 8
+WHY_EPS, WHY_OSCILLATION, WHY_ITER_CAP, WHY_FINAL_OOR, WHY_TAINT = 16, 32, 64, 128, 256
+WHY_OUT_OF_RANGE = WHY_PREV_OOR | WHY_NEXT_OOR_FIRST | WHY_NEXT_OOR_ITER | WHY_FINAL_OOR
+WHY_NAMES = {WHY_PREV_OOR: "prev_oor", WHY_MIN_EIG: "min_eig", WHY_NEXT_OOR_FIRST: "next_oor_first",
+             WHY_NEXT_OOR_ITER: "next_oor_iter", WHY_EPS: "eps", WHY_OSCILLATION: "oscillation",
+             WHY_ITER_CAP: "iter_cap", WHY_FINAL_OOR: "final_oor", WHY_TAINT: "taint"}
+
 
 class OraParams(C.Structure):
     _fields_ = [("win", C.c_int), ("max_level", C.c_int), ("max_iters", C.c_int),
@@ -61,6 +69,8 @@ def lib():
         L.ora_free_pyramid.argtypes = [C.POINTER(OraPyramid)]
         L.ora_lk.argtypes = [C.POINTER(OraPyramid), C.POINTER(OraPyramid), C.c_int, f32p, f32p, u8p,
                              C.c_int, C.POINTER(OraParams), C.c_int]
+        u16p = C.POINTER(C.c_uint16)
+        L.ora_lk_why.argtypes = L.ora_lk.argtypes + [u16p]
         L.ora_get_perspective_transform.argtypes = [f32p, f32p, f64p]
         L.ora_set_svd_vblas.argtypes = [C.c_int]
         L.ora_set_svd_vblas.restype = None
@@ -78,9 +88,13 @@ def lib():
                                                  C.POINTER(OraParams), C.c_int, f32p, u8p, f64p, u8p,
                                                  f64p, f64p, C.POINTER(C.c_int)]
         L.ora_calculate_optical_flow.restype = C.c_int
+        L.ora_calculate_optical_flow_why.argtypes = L.ora_calculate_optical_flow.argtypes + [u16p]
+        L.ora_calculate_optical_flow_why.restype = C.c_int
         L.ora_flow_trajectory.argtypes = [C.POINTER(u8p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(OraParams), C.c_int, f32p, C.POINTER(C.c_int), f32p, f64p]
         L.ora_flow_trajectory.restype = C.c_int
+        L.ora_flow_trajectory_why.argtypes = L.ora_flow_trajectory.argtypes + [u16p]
+        L.ora_flow_trajectory_why.restype = C.c_int
         L.ora_srand.argtypes = [C.POINTER(OraRandState), C.c_uint32]
         L.ora_srand.restype = None
         L.ora_rand.argtypes = [C.POINTER(OraRandState)]
@@ -202,9 +216,10 @@ def set_simd(on: bool) -> None:
 
 
 def calculate_optical_flow(img1: np.ndarray, img2: np.ndarray, fmt: int | None = None, nthreads: int = 1,
-                           want_mask: bool = True, simd: bool = False, **kw):
+                           want_mask: bool = True, simd: bool = False, why: bool = False, **kw):
     """Whole reference path.  Returns dict like motion_detection_amd's result.  simd: run the LK
-    sums and the warp's bilinear through the SSE2 restatement (same results, CPU-baseline speed)."""
+    sums and the warp's bilinear through the SSE2 restatement (same results, CPU-baseline speed).
+    why: also return "why", the (npts,) uint16 WHY_* bits of every point."""
     img1 = np.ascontiguousarray(img1)
     img2 = np.ascontiguousarray(img2)
     h, w = img1.shape[:2]
@@ -219,22 +234,30 @@ def calculate_optical_flow(img1: np.ndarray, img2: np.ndarray, fmt: int | None =
     H = np.zeros(9)
     Hinv = np.zeros(9)
     fs = C.c_int(0)
-    lib().ora_set_simd(1 if simd else 0)
-    try:
-        num = lib().ora_calculate_optical_flow(
-            _p(img1, C.c_uint8), _p(img2, C.c_uint8), w, h, img1.strides[0], fmt, C.byref(prm), nthreads,
+    args = (_p(img1, C.c_uint8), _p(img2, C.c_uint8), w, h, img1.strides[0], fmt, C.byref(prm), nthreads,
             _p(nextp, C.c_float), _p(status, C.c_uint8), _p(vec, C.c_double),
             _p(mask, C.c_uint8) if mask is not None else None, _p(H, C.c_double), _p(Hinv, C.c_double), C.byref(fs))
+    lib().ora_set_simd(1 if simd else 0)
+    try:
+        if why:
+            bits = np.zeros(max(n, 1), np.uint16)
+            num = lib().ora_calculate_optical_flow_why(*args, _p(bits, C.c_uint16))
+        else:
+            num = lib().ora_calculate_optical_flow(*args)
     finally:
         lib().ora_set_simd(0)
-    return dict(num_vectors=num, next_pts=nextp, status=status, vectors=vec, mask=mask,
-                H=H.reshape(3, 3), Hinv=Hinv.reshape(3, 3), fit_status=fs.value)
+    out = dict(num_vectors=num, next_pts=nextp, status=status, vectors=vec, mask=mask,
+               H=H.reshape(3, 3), Hinv=Hinv.reshape(3, 3), fit_status=fs.value)
+    if why:
+        out["why"] = bits[:n]
+    return out
 
 
-def flow_trajectory(images, fmt: int | None = None, nthreads: int = 1, **kw):
+def flow_trajectory(images, fmt: int | None = None, nthreads: int = 1, why: bool = False, **kw):
     """calculateOpticalFlowTrajectory (optical_flow_calculator.cpp:133-257) over a list of frames.
     Returns dict(num_vectors, traj (npts, nimg, 2), traj_len (npts,), start_pts (npts, 2),
-    vectors (npts, 4), trajectories = [traj[i] for complete i] as the reference reports them)."""
+    vectors (npts, 4), trajectories = [traj[i] for complete i] as the reference reports them).
+    why: also return "why", the (npts,) uint16 WHY_* bits accumulated over every pass."""
     imgs = [np.ascontiguousarray(im) for im in images]
     nimg = len(imgs)
     h, w = imgs[0].shape[:2]
@@ -247,16 +270,25 @@ def flow_trajectory(images, fmt: int | None = None, nthreads: int = 1, **kw):
     start = np.zeros((n, 2), np.float32)
     vec = np.zeros((n, 4), np.float64)
     arr = (C.POINTER(C.c_uint8) * nimg)(*[_p(im, C.c_uint8) for im in imgs])
-    num = lib().ora_flow_trajectory(arr, nimg, w, h, imgs[0].strides[0], fmt, C.byref(prm), nthreads,
-                                    _p(traj, C.c_float), tlen.ctypes.data_as(C.POINTER(C.c_int)),
-                                    _p(start, C.c_float), _p(vec, C.c_double))
+    args = (arr, nimg, w, h, imgs[0].strides[0], fmt, C.byref(prm), nthreads,
+            _p(traj, C.c_float), tlen.ctypes.data_as(C.POINTER(C.c_int)),
+            _p(start, C.c_float), _p(vec, C.c_double))
+    if why:
+        bits = np.zeros(max(n, 1), np.uint16)
+        num = lib().ora_flow_trajectory_why(*args, _p(bits, C.c_uint16))
+    else:
+        num = lib().ora_flow_trajectory(*args)
     full = [traj[i] for i in range(n) if tlen[i] == nimg]
-    return dict(num_vectors=num, traj=traj, traj_len=tlen, start_pts=start, vectors=vec, trajectories=full)
+    out = dict(num_vectors=num, traj=traj, traj_len=tlen, start_pts=start, vectors=vec, trajectories=full)
+    if why:
+        out["why"] = bits[:n]
+    return out
 
 
-def lk(gray1: np.ndarray, gray2: np.ndarray, prev_pts: np.ndarray, nthreads: int = 1, **kw):
+def lk(gray1: np.ndarray, gray2: np.ndarray, prev_pts: np.ndarray, nthreads: int = 1, why: bool = False, **kw):
     """calcOpticalFlowPyrLK(buildOpticalFlowPyramid(gray1), gray2, prev_pts, ...) with the
-    reference's arguments (optical_flow_calculator.cpp:67-71 / :170-172).  Returns (next_pts, status)."""
+    reference's arguments (optical_flow_calculator.cpp:67-71 / :170-172).  Returns (next_pts, status),
+    or (next_pts, status, why bits) when why is set."""
     gray1 = np.ascontiguousarray(gray1)
     gray2 = np.ascontiguousarray(gray2)
     h, w = gray1.shape
@@ -269,11 +301,12 @@ def lk(gray1: np.ndarray, gray2: np.ndarray, prev_pts: np.ndarray, nthreads: int
     L = lib()
     ml = L.ora_build_pyramid(_p(gray1, C.c_uint8), w, h, prm.win, prm.max_level, 1, C.byref(P1))
     ml = L.ora_build_pyramid(_p(gray2, C.c_uint8), w, h, prm.win, ml, 0, C.byref(P2))
-    L.ora_lk(C.byref(P1), C.byref(P2), ml, _p(pts, C.c_float), _p(nxt, C.c_float), _p(st, C.c_uint8), n,
-             C.byref(prm), nthreads)
+    bits = np.zeros(max(n, 1), np.uint16)
+    L.ora_lk_why(C.byref(P1), C.byref(P2), ml, _p(pts, C.c_float), _p(nxt, C.c_float), _p(st, C.c_uint8), n,
+                 C.byref(prm), nthreads, _p(bits, C.c_uint16) if why else None)
     L.ora_free_pyramid(C.byref(P1))
     L.ora_free_pyramid(C.byref(P2))
-    return nxt[:n], st[:n]
+    return (nxt[:n], st[:n], bits[:n]) if why else (nxt[:n], st[:n])
 
 
 def rand_state(seed: int) -> OraRandState:

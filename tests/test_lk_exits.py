@@ -1,0 +1,345 @@
+"""Every way a Lucas-Kanade point can stop, on frames that make it happen (tests/hostile_frames.py).
+
+The ordinary test frames never drive a point out of the frame: on mdx_synth_pair every level ends
+by eps, the oscillation break, the iteration cap or a minEig reject (pinned below).  The hostile
+pairs make the next window leave the level before the first iteration and in mid-iteration, fire
+the final level-0 bounds check, reject a finer level after a coarser one iterated, and never
+converge.  The oracle reports why each point stopped (pyoracle ... why=True, ORA_WHY_* bits).
+
+CPU part: from the oracle alone, each case does the job it was chosen for.  Some points are
+*tainted* -- read a window at ix == w-1 or iy == h-1 of a level, whose bilinear footprint ends on
+the last column / row of the 40-px padding (the very edge of the buffer, not past
+it); the cases must reach that edge and keep it under 5 % of a grid.
+GPU part (-m gpu): host entry, batched device entry, trajectories and the band path equal the oracle
+bit for bit on every point, tainted ones included; H and the mask are compared in every case.
+"""
+import numpy as np
+import pytest
+
+import hostile_frames as hf
+
+# (w, h, pixel_step, channels): three levels; two; one (k_gray_pad); odd sizes; rgb; the batch shape
+HOST_SHAPES = [(330, 250, 10, 1), (165, 125, 5, 1), (64, 48, 4, 1), (333, 241, 7, 1), (320, 240, 10, 3)]
+BATCH_SHAPE = (320, 240, 10, 1)
+SHAPES = HOST_SHAPES + [BATCH_SHAPE]
+
+# What each case was chosen for, and how many points of each shape (SHAPES order) showed that exit
+# when these numbers were counted with the committed oracle on the committed generators.  The test
+# asks for at least half of each.
+COUNTED = {
+    "bright+30": {"next_oor_iter": (101, 163, 25, 156, 83, 99), "iter_cap": (69, 75, 2, 168, 40, 66)},
+    "bright-30": {"next_oor_iter": (27, 136, 14, 67, 12, 12), "iter_cap": (115, 203, 17, 239, 82, 118)},
+    "bright+60": {"next_oor_first": (62, 123, 0, 118, 41, 63), "next_oor_iter": (359, 536, 31, 681, 278, 349),
+                  "iter_cap": (416, 188, 0, 823, 391, 409)},
+    "bright-40": {"next_oor_iter": (96, 324, 29, 215, 86, 108), "final_oor": (20, 4, 0, 13, 6, 13)},
+    "phase1.5": {"next_oor_first": (8, 18, 0, 16, 4, 8), "next_oor_iter": (5, 12, 11, 6, 5, 5)},
+    "noise2": {"iter_cap": (825, 815, 190, 1679, 768, 768)},
+    "inverse": {"iter_cap": (825, 820, 192, 1680, 768, 768)},
+    "checker8": {"oscillation": (171, 0, 0, 310, 178, 154), "iter_cap": (518, 104, 163, 1223, 492, 515)},
+    "checker1": {"min_eig": (825, 825, 192, 1680, 768, 768)},
+    "halfflat": {"min_eig": (350, 302, 36, 735, 336, 336), "eps": (624, 622, 155, 1225, 576, 576)},
+    "lowcontrast": {"min_eig": (825, 825, 192, 1680, 768, 768)},
+}
+CASES = list(hf.PAIRS)
+TAINT_CAP = 0.05          # of the grid, per case: a condition on the cases, not a measurement
+
+_refs = {}                # (case, shape) -> oracle result, computed once and left unchanged
+
+
+def _bit(oracle, name):
+    return next(b for b, n in oracle.WHY_NAMES.items() if n == name)
+
+
+def _ref(oracle, name, shape):
+    if (name, shape) not in _refs:
+        w, h, ps, ch = shape
+        a, b = hf.pair(name, w, h, ch)
+        r = oracle.calculate_optical_flow(a, b, nthreads=8, pixel_step=ps, min_vector_size=1.0, why=True)
+        _refs[(name, shape)] = (a, b, r)
+    return _refs[(name, shape)]
+
+
+def _accepted(vec):
+    """Accepted vectors: (x, y, dx, dy) with |dx| or |dy| above min_vector_size, so not both zero."""
+    return (vec[:, 2] != 0) | (vec[:, 3] != 0)
+
+
+# ------------------------------------------------------------------------------------ CPU
+@pytest.mark.parametrize("name", CASES)
+def test_case_does_its_job(oracle, name):
+    for si, shape in enumerate(SHAPES):
+        _, _, r = _ref(oracle, name, shape)
+        why = r["why"]
+        for exit_name, counted in COUNTED[name].items():
+            got = int(((why & _bit(oracle, exit_name)) != 0).sum())
+            print(f"{name} {shape}: {exit_name} {got} (counted {counted[si]})")
+            assert 2 * got >= counted[si], (name, shape, exit_name, got, counted[si])
+        tainted = int(((why & oracle.WHY_TAINT) != 0).sum())
+        print(f"{name} {shape}: {why.size} points compared, {tainted} of them tainted, H and mask compared")
+        assert tainted <= TAINT_CAP * why.size, (name, shape, tainted)
+        assert np.all(why != 0)        # every point has a reason
+
+
+def test_every_exit_is_seen(oracle):
+    """Over the hostile set every exit bit occurs.  The previous window can only be out of range for
+    a start point outside the frame; the pair path's grid and a trajectory's points (strictly inside
+    the 10-px border) never are, so that bit is shown on pyoracle.lk with such points."""
+    seen = 0
+    for name in CASES:
+        for shape in SHAPES:
+            seen |= int(np.bitwise_or.reduce(_ref(oracle, name, shape)[2]["why"]))
+    everything = int(np.bitwise_or.reduce(np.array(list(oracle.WHY_NAMES), np.int64)))
+    assert seen == everything & ~oracle.WHY_PREV_OOR, [n for b, n in oracle.WHY_NAMES.items() if not seen & b]
+    a, b = hf.pair("noise2", 165, 125)
+    pts = np.array([[-30.0, 50.0], [80.0, 60.0], [80.0, 200.0], [164.0, 124.0]], np.float32)
+    nxt, st, why = oracle.lk(a, b, pts, why=True)
+    assert why[0] & oracle.WHY_PREV_OOR and why[2] & oracle.WHY_PREV_OOR and st[0] == 0 and st[2] == 0
+    assert not why[1] & oracle.WHY_PREV_OOR and not why[3] & oracle.WHY_PREV_OOR
+    # the default output is unchanged by asking for the reasons
+    nxt0, st0 = oracle.lk(a, b, pts)
+    assert np.array_equal(nxt0.view(np.uint32), nxt.view(np.uint32)) and np.array_equal(st0, st)
+
+
+def test_carried_point_after_finer_reject(oracle):
+    """A coarser level iterates, a finer one fails minEig: the carried point is doubled and passed
+    on, and the point ends with status 0 and the coarser level's position times two."""
+    _, _, r = _ref(oracle, "bright+60", SHAPES[0])
+    why = r["why"]
+    both = ((why & oracle.WHY_MIN_EIG) != 0) & ((why & (oracle.WHY_EPS | oracle.WHY_ITER_CAP)) != 0)
+    assert both.sum() >= 244          # counted 488
+    assert not r["status"][both].any()
+    grid = np.array([(x, y) for x in range(0, 330, 10) for y in range(0, 250, 10)], np.float32)
+    assert (np.abs(r["next_pts"][both] - grid[both]).max(axis=1) > 1.0).sum() >= 100   # counted 291: they moved
+
+
+def test_every_level_rejects(oracle):
+    for shape in SHAPES:
+        _, _, r = _ref(oracle, "checker1", shape)
+        assert np.all(r["why"] == oracle.WHY_MIN_EIG) and not r["status"].any() and r["num_vectors"] == 0
+
+
+def test_fit_compared_on_every_shape(oracle):
+    """H and the mask are compared in every GPU case; on every shape some cases have a real fit
+    (four accepted vectors, none of the first four a tainted point's) and some have none."""
+    for shape in SHAPES:
+        fitted = 0
+        for n in CASES:
+            r = _ref(oracle, n, shape)[2]
+            acc = np.nonzero(_accepted(r["vectors"]))[0]
+            fitted += acc.size >= 4 and not (r["why"][acc[:4]] & oracle.WHY_TAINT).any()
+        assert 5 <= fitted < len(CASES), (shape, fitted)      # counted 9 of 11 (7 at 64 x 48)
+
+
+def test_cases_reach_the_padding_edge(oracle):
+    """Windows on a level's last row or column do occur: counted 136 points over the host shapes."""
+    total = sum(int(((_ref(oracle, n, s)[2]["why"] & oracle.WHY_TAINT) != 0).sum()) for n in CASES for s in HOST_SHAPES)
+    print("tainted points over the host shapes:", total)
+    assert total >= 68
+
+
+def test_old_family_never_leaves_the_frame(mdx, oracle):
+    """Today's state: on the suite's ordinary frames no out-of-range exit occurs (nor taint)."""
+    a, b, _ = mdx.synth_pair(20141105, 640, 480)
+    r = oracle.calculate_optical_flow(a, b, nthreads=8, pixel_step=10, min_vector_size=1.0, why=True)
+    assert not (r["why"] & (oracle.WHY_OUT_OF_RANGE | oracle.WHY_TAINT)).any()
+    assert np.all(r["why"] != 0)
+
+
+def test_why_leaves_outputs_unchanged(oracle):
+    a, b = hf.pair("bright-40", 165, 125)
+    r0 = oracle.calculate_optical_flow(a, b, pixel_step=5)
+    r1 = oracle.calculate_optical_flow(a, b, pixel_step=5, why=True)
+    for k in ("next_pts", "status", "vectors", "mask", "H"):
+        assert np.array_equal(r0[k], r1[k], equal_nan=True), k
+    assert r0["num_vectors"] == r1["num_vectors"] and "why" not in r0
+    fr = hf.traj_frames(165, 125, 3)
+    t0, t1 = oracle.flow_trajectory(fr, pixel_step=5), oracle.flow_trajectory(fr, pixel_step=5, why=True)
+    for k in ("traj", "traj_len", "start_pts", "vectors"):
+        assert np.array_equal(t0[k], t1[k]), k
+
+
+# (w, h, nimg, pixel_step, channels) -> counted points with: next_oor_first, next_oor_iter, final_oor
+TRAJ_CASES = {
+    (330, 250, 4, 10, 1): (17, 115, 4),
+    (330, 250, 4, 10, 3): (10, 92, 5),
+    (200, 150, 16, 10, 1): (18, 161, 2),
+    (200, 150, 18, 10, 1): (18, 161, 2),
+}
+_traj_refs = {}
+
+
+def _traj_ref(oracle, key):
+    if key not in _traj_refs:
+        w, h, n, ps, ch = key
+        frames = hf.traj_frames(w, h, n, ch)
+        _traj_refs[key] = (frames, oracle.flow_trajectory(frames, nthreads=8, pixel_step=ps, why=True))
+    return _traj_refs[key]
+
+
+@pytest.mark.parametrize("key", list(TRAJ_CASES))
+def test_trajectory_case_does_its_job(oracle, key):
+    _, r = _traj_ref(oracle, key)
+    why = r["why"]
+    for exit_name, counted in zip(("next_oor_first", "next_oor_iter", "final_oor"), TRAJ_CASES[key]):
+        got = int(((why & _bit(oracle, exit_name)) != 0).sum())
+        print(f"traj {key}: {exit_name} {got} (counted {counted})")
+        assert 2 * got >= counted, (key, exit_name, got, counted)
+    tainted = int(((why & oracle.WHY_TAINT) != 0).sum())
+    print(f"traj {key}: {why.size} points compared, {tainted} of them tainted")
+    assert tainted <= TAINT_CAP * why.size
+
+
+# ------------------------------------------------------------------------------------ GPU
+def _compare_pair(got, ref, label):
+    """got: dict(num, status, next_pts, vectors, H, mask) of one pair; everything bit for bit."""
+    assert int(got["num"]) == ref["num_vectors"], label
+    np.testing.assert_array_equal(got["status"], ref["status"], err_msg=label)
+    bad = np.nonzero((got["next_pts"].view(np.uint32) != ref["next_pts"].view(np.uint32)).any(axis=1))[0]
+    assert bad.size == 0, f"{label}: {bad.size} LK points differ, first {bad[:5]}: " \
+                          f"{got['next_pts'][bad[:3]]} vs {ref['next_pts'][bad[:3]]} why {ref['why'][bad[:3]]}"
+    np.testing.assert_array_equal(got["vectors"].view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
+    np.testing.assert_array_equal(got["H"].reshape(3, 3).view(np.uint64), ref["H"].view(np.uint64), err_msg=label)
+    nbad = int((got["mask"] != ref["mask"]).sum())
+    assert nbad == 0, f"{label}: {nbad} mask pixels differ"
+
+
+def _compare_traj(res, ref, label):
+    assert res.num_vectors == ref["num_vectors"], label
+    np.testing.assert_array_equal(res.traj_len, ref["traj_len"], err_msg=label)
+    for i in range(len(res.traj_len)):
+        k = int(ref["traj_len"][i])
+        a, b = res.traj[i, :k].view(np.uint32), ref["traj"][i, :k].view(np.uint32)
+        assert np.array_equal(a, b), f"{label}: point {i}: {res.traj[i, :k]} vs {ref['traj'][i, :k]}"
+    np.testing.assert_array_equal(res.start_pts.view(np.uint32), ref["start_pts"].view(np.uint32), err_msg=label)
+    np.testing.assert_array_equal(res.vectors.view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", HOST_SHAPES, ids=lambda s: "%dx%d_ps%d_ch%d" % s)
+@pytest.mark.parametrize("name", CASES)
+def test_host_entry_hostile(mdx, ctx, oracle, name, shape):
+    w, h, ps, ch = shape
+    a, b, ref = _ref(oracle, name, shape)
+    ctx.set_params(pixel_step=ps, min_vector_size=1.0, fit_mode=mdx.FIT_FIRST4)
+    try:
+        res = ctx.flow_warp_diff(a, b)
+    finally:
+        ctx.set_params(pixel_step=10)
+    got = dict(num=res.num_vectors, status=res.status, next_pts=res.next_pts, vectors=res.vectors, H=res.H,
+               mask=res.mask)
+    _compare_pair(got, ref, f"{name} {shape}")
+
+
+def _run_batch(mdx, g1, g2, w, h, ps):
+    B = len(g1)
+    n = mdx.grid_count(w, h, ps)
+    g1 = np.stack(g1)
+    g2 = np.stack(g2)
+    with mdx.Context(0, w, h, B) as c:
+        c.set_params(pixel_step=ps, min_vector_size=1.0)
+        bufs = {k: c.dev_alloc(s) for k, s in dict(i1=g1.nbytes, i2=g2.nbytes, np=B * n * 8, st=B * n,
+                                                    vec=B * n * 32, mask=B * w * h, H=B * 72, num=B * 4).items()}
+        try:
+            c.h2d(bufs["i1"], g1)
+            c.h2d(bufs["i2"], g2)
+            c.flow_warp_diff_batch_dev(B, bufs["i1"], bufs["i2"], w, h, w, w * h, mdx.FMT_GRAY8, bufs["np"],
+                                       bufs["st"], bufs["vec"], bufs["mask"], bufs["H"], 0, bufs["num"])
+            c.sync()
+            out = dict(np=np.empty((B, n, 2), np.float32), st=np.empty((B, n), np.uint8), vec=np.empty((B, n, 4)),
+                       mask=np.empty((B, h, w), np.uint8), H=np.empty((B, 3, 3)), num=np.empty(B, np.int32))
+            for k, arr in out.items():
+                c.d2h(arr, bufs[k])
+        finally:
+            for p in bufs.values():
+                c.dev_free(p)
+    return [dict(num=out["num"][i], status=out["st"][i], next_pts=out["np"][i], vectors=out["vec"][i], H=out["H"][i],
+                 mask=out["mask"][i]) for i in range(B)]
+
+
+# hostile pairs in the even slots (the 1-px checkerboard among the first eight), ordinary ones between
+_BATCH_ORDER = ["bright+60", "checker1", "bright-40", "noise2", "checker8", "bright+30", "inverse", "halfflat"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,env,shape", [
+    (16, {}, BATCH_SHAPE),                       # the dataflow path
+    (16, {"MDX_LK_FLOW": "0"}, BATCH_SHAPE),
+    (11, {"MDX_LK_G": "4"}, BATCH_SHAPE),
+    (11, {"MDX_LK_G": "8"}, BATCH_SHAPE),
+    (3, {"MDX_LK_IMPL": "1"}, SHAPES[0]),        # k_lk<64> over a batch
+], ids=["B16_dataflow", "B16_flow0", "B11_G4", "B11_G8", "B3_impl1"])
+def test_batch_dev_hostile(mdx, oracle, monkeypatch, B, env, shape):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    w, h, ps, _ = shape
+    assert B < 16 or mdx.grid_count(w, h, ps) % 16 == 0
+    g1, g2, refs = [], [], []
+    for i in range(B):
+        if i % 2 == 0:
+            a, b, ref = _ref(oracle, _BATCH_ORDER[(i // 2) % len(_BATCH_ORDER)], shape)
+        else:
+            key = ("synth", 300 + i, shape)
+            if key not in _refs:
+                a, b, _ = mdx.synth_pair(300 + i, w, h, 1)
+                _refs[key] = (a, b, oracle.calculate_optical_flow(a, b, nthreads=8, pixel_step=ps,
+                                                                  min_vector_size=1.0, why=True))
+            a, b, ref = _refs[key]
+        g1.append(a); g2.append(b); refs.append(ref)
+    for i, got in enumerate(_run_batch(mdx, g1, g2, w, h, ps)):
+        _compare_pair(got, refs[i], f"pair {i} of {B} {env}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key,env", [
+    ((330, 250, 4, 10, 1), {"MDX_TRAJ_PPW": "1"}),
+    ((330, 250, 4, 10, 1), {"MDX_TRAJ_PPW": "2"}),
+    ((330, 250, 4, 10, 1), {"MDX_TRAJ_PPW": "4"}),
+    ((330, 250, 4, 10, 1), {"MDX_TRAJ_CHAIN": "0"}),
+    ((330, 250, 4, 10, 3), {}),
+    ((200, 150, 16, 10, 1), {}),                 # the chained launch's limit
+    ((200, 150, 18, 10, 1), {}),                 # past it: per-pass launches
+], ids=["ppw1", "ppw2", "ppw4", "chain0", "rgb", "16_frames", "18_frames"])
+def test_trajectory_hostile(mdx, oracle, monkeypatch, key, env):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    w, h, n, ps, ch = key
+    frames, ref = _traj_ref(oracle, key)
+    with mdx.Context(0, w, h, 1) as c:
+        c.set_params(pixel_step=ps, min_vector_size=1.0)
+        res = c.flow_trajectory(frames)
+    _compare_traj(res, ref, f"{key} {env}")
+
+
+@pytest.mark.gpu
+def test_band_path_hostile(mdx, oracle):
+    """One hostile pair through the row-band entries with 3 bands: equal to the full path."""
+    from motion_detection_amd import rowtile
+    shape = SHAPES[0]
+    w, h, ps, _ = shape
+    nb = 3
+    a, b, ref = _ref(oracle, "bright+60", shape)
+    n = mdx.grid_count(w, h, ps)
+    with mdx.Context(0, w, h, 1, pixel_step=ps, min_vector_size=1.0) as c:
+        d = {k: c.dev_alloc(sz) for k, sz in dict(i1=a.nbytes, i2=b.nbytes, np=n * 8, st=n, vec=n * 32,
+                                                   cand=nb * 96, mask=w * h, H=72, num=4).items()}
+        try:
+            c.h2d(d["i1"], a); c.h2d(d["i2"], b)
+            c.h2d(d["vec"], np.zeros(n * 32, np.uint8))
+            for r in range(nb):
+                y0, y1 = rowtile.band_rows(h, nb, r)
+                c.band_flow_dev(d["i1"], d["i2"], w, h, w, mdx.FMT_GRAY8, y0, y1, d["np"], d["st"], d["cand"] + 96 * r,
+                                d["vec"])
+            c.sync()
+            for r in range(nb):
+                y0, y1 = rowtile.band_rows(h, nb, r)
+                c.band_fit_warp_dev(nb, d["cand"], y0, y1, d["mask"] + y0 * w, d["H"], d["num"])
+            c.sync()
+            out = dict(np=np.empty((n, 2), np.float32), st=np.empty(n, np.uint8), vec=np.empty((n, 4)),
+                       mask=np.empty((h, w), np.uint8), H=np.empty((3, 3)), num=np.empty(1, np.int32))
+            for k, arr in out.items():
+                c.d2h(arr, d[k])
+        finally:
+            for p in d.values():
+                c.dev_free(p)
+    got = dict(num=out["num"][0], status=out["st"], next_pts=out["np"], vectors=out["vec"], H=out["H"], mask=out["mask"])
+    _compare_pair(got, ref, "3 bands")
