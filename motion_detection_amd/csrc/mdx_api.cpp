@@ -80,29 +80,22 @@ static LkTuning read_tuning()
     t.lk_impl = num("MDX_LK_IMPL", 2) == 1 ? 1 : 2;
     t.lk_g = num("MDX_LK_G", 0);
     t.lk_sub = num("MDX_LK_SUB", 0);
-    t.lk_arows = num("MDX_LK_AROWS", 1) != 0;
     t.lk_astrip = std::max(0, std::min(num("MDX_LK_ASTRIP", 0), 64));
-    t.lk_pflow = num("MDX_LK_PFLOW", 0);
     t.lk_debug = num("MDX_LK_DEBUG", 0) != 0;
     t.traj_chain = num("MDX_TRAJ_CHAIN", 1) != 0;
     const int ppw = num("MDX_TRAJ_PPW", 4);
     t.traj_ppw = ppw == 1 ? 1 : ppw == 2 ? 2 : 4;
     t.lk_aux = num("MDX_LK_AUX", 1) != 0;
-    t.aux_prio = num("MDX_AUX_PRIO", 0) != 0;
     t.lk_flow = num("MDX_LK_FLOW", 1) != 0;
     t.lk_cap = std::min(std::max(num("MDX_LK_CAP", 75), 10), 100);
     t.spin_max = num("MDX_LK_SPIN_MAX", kLkSpinDefault);
-    t.lk_xcall = num("MDX_LK_XCALL", 0) != 0;
     return t;
 }
 
 // Streams and events are created through these, so that mdx_destroy finds every one in the lists.
-static bool new_stream(mdx_ctx* c, hipStream_t* s, bool top_priority = false)
+static bool new_stream(mdx_ctx* c, hipStream_t* s)
 {
-    int least = 0, greatest = 0;
-    const bool prio = top_priority && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-    if ((prio ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest)
-              : hipStreamCreateWithFlags(s, hipStreamNonBlocking)) != hipSuccess) {
+    if (hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) {
         *s = nullptr;
         return false;
     }
@@ -146,7 +139,7 @@ extern "C" mdx_ctx* mdx_create(int device, int max_w, int max_h, int max_batch, 
     };
     if (!new_stream(c, &c->stream)) return fail("hipStreamCreate failed");
     if (c->lk_aux) {
-        bool ok = new_stream(c, &c->aux, c->aux_prio) && new_events(c, c->lkev, kMaxLevels + 2);
+        bool ok = new_stream(c, &c->aux) && new_events(c, c->lkev, kMaxLevels + 2);
         if (ok && c->lk_flow)
             ok = new_stream(c, &c->iter2) && new_events(c, c->flowev, 2) && new_events(c, c->redo_ev, kMaxLevels);
         // call pipelining's events (mdx_params.call_pipelining may be switched on at any call)

@@ -46,25 +46,17 @@ struct LkTuning {
     int lk_impl = 2;          // MDX_LK_IMPL: 1 = single-kernel LK (k_lk), 2 = class planes
     int lk_g = 0;             // MDX_LK_G: LK group size, 0 = per level, 4 or 8
     int lk_sub = 0;           // MDX_LK_SUB: > 0: LK sub-batch cap (tests)
-    bool lk_arows = true;     // MDX_LK_AROWS=0: A sums per group, not per row strip where the plan allows
     int lk_astrip = 0;        // MDX_LK_ASTRIP: grid rows per A-sum strip (0: kAStripRows)
-    // MDX_LK_PFLOW: 1 per-point dataflow wherever the per-pair form does not apply (small batches,
-    // row bands), 2 everywhere; 0 (default) never -- measured slower for row bands
-    int lk_pflow = 0;
     bool lk_debug = false;    // MDX_LK_DEBUG=1: per-level trace
     bool traj_chain = true;   // MDX_TRAJ_CHAIN=0: trajectory passes one launch per pass, not chained
     int traj_ppw = 4;         // MDX_TRAJ_PPW: trajectory LK points per wave (1, 2 or 4)
     bool lk_aux = true;       // MDX_LK_AUX=0: no aux stream (LK class / A kernels do not run ahead)
-    bool aux_prio = false;    // MDX_AUX_PRIO=1: the aux stream gets the greatest dispatch priority
     bool lk_flow = true;      // MDX_LK_FLOW=0: no LK dataflow (no second iteration stream)
     // MDX_LK_CAP: dataflow launch share of the resident waves (%).  75: the aux stream's next-level
     // class planes and A sums pace the level hand-offs (round 6, profiles/r06_ab_lk_w5_cap.txt: 60 -3%,
     // 70 / 80 / 85 within 1%, 75 best and steadiest, 95 -1.2%)
     int lk_cap = 75;
     int spin_max = mdx::kLkSpinDefault;   // MDX_LK_SPIN_MAX (debug: < 0 injects timeouts)
-    // MDX_LK_XCALL=1: pipelined calls alternate the LK stream parity, so the next call's first level
-    // need not queue behind this call's fit / warp.  +0.5% (noise), and it moves the LK stage events: off
-    bool lk_xcall = false;
 };
 
 struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
@@ -106,7 +98,6 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     int* err_host = nullptr;                 // pinned readback
     int* tcnt_host = nullptr;                // pinned readback of the trajectory counts
     long long lk_fallback[3] = {0, 0, 0};
-    int lk_parity = 0;                       // the next pipelined call's LK stream parity
     mdx_params prm{};
     int max_w = 0, max_h = 0, max_batch = 0;
     DevBuf pyr1, pyr2, der, fits;            // pyramid / derivative / fit workspace
@@ -131,9 +122,7 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf rsc;                              // MDX_FIT_RANSAC scratch (list, hypotheses, counts)
     std::vector<int> ring_order;             // held slots, oldest first
     int ring_cap = 0, ring_w = 0, ring_h = 0, ring_ml = -1;
-    int lk_epoch = 0;                        // per-point dataflow: the last call's epoch
-    void* pflag_mem = nullptr;               // the Abuf allocation and layout whose per-point flags were zeroed
-    size_t pflag_at = 0, pflag_bytes = 0, pflag_per = 0;
+    std::array<size_t, 4> lk_scratch_key{{0, 0, 0, 0}};      // (Abuf, levels, batch, points) of the last LK's scratch layout
     std::array<int, 6> plan_key{{-1, -1, -1, -1, -1, -1}};   // (w, h, pixel_step, levels, gy0, gy1) of `plan`
     int band_w = 0, band_h = 0;              // frame of the last mdx_band_flow_dev (its pyramids are live)
     mdx::ClassPlan plan{};
@@ -287,7 +276,7 @@ inline void release_pyr_all(mdx_ctx* c)
 
 // mdx_pair.cpp: the LK of a batch of pairs on the context's stream (the per-pass trajectory LK too)
 int run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int h, int gy0, int gy1, bool have_scharr,
-           hipEvent_t prev_ready = nullptr, int parity = -1, hipEvent_t out_free = nullptr);
+           hipEvent_t prev_ready = nullptr);
 bool host_block_holds(const void* p, size_t bytes);   // mdx_api.cpp: inside one mdx_host_alloc block
 
 }  // namespace mdx

@@ -4,7 +4,10 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "mdx.h"
 
@@ -71,6 +74,17 @@ struct ClassLevel {
 };
 constexpr int kAStripRows = 16;
 
+// Floor of the LK window origin of grid index gi (column or row) at a level: the reference's
+// prevPt * 2^-level - 19.5 in float.  The host plan (which plane rows and columns exist) and the
+// kernels (which are read) must agree on it bit for bit: floorf of the same float operands.
+__host__ __device__ inline int lk_win_origin(int gi, int pixel_step, int level)
+{
+    return (int)floorf((float)(gi * pixel_step) * (float)(1. / (1 << level)) - 19.5f);
+}
+// First class-plane row of the window with origin row ipy: planes carry kPad rows above the level,
+// and a window is clamped into the UH plane rows.
+__host__ __device__ inline int lk_win_row0(int ipy, int UH) { return std::min(std::max(ipy + kPad, 0), UH - kWin); }
+
 // (G, UW) shapes of the LK level kernels (mdx_lk.hip instantiates these; the host plan picks the
 // smallest UW >= a level's union span among the shapes of its G)
 #define LK_SHAPES LK_CASE(4, 48) LK_CASE(4, 56) LK_CASE(4, 64) LK_CASE(4, 72) LK_CASE(4, 80) LK_CASE(4, 96) \
@@ -120,13 +134,6 @@ struct LkArgs {
                              // the level launches run one after another
     int done_stride;
     int dep_groups;          // > 0: groups per pair of the coarser level, which a group waits for
-    int dep_points;          // 1: per-point dataflow -- a group waits only for its own points' coarser
-                             // level results (pflags), not for the whole pair's level (small batches)
-    int* pflags;             // per-point dataflow: [level][batch][npts] epoch of each point's last
-                             // retirement at that level (this sub-batch's first pair)
-    long long pf_lstride;    // ints between two levels of pflags
-    int epoch;               // this call's epoch (> every earlier call's)
-    int pflow_force;         // 1: per-point dataflow even where the per-pair form applies (MDX_LK_PFLOW)
     int* err;                // dataflow statistics, read and cleared at the context's sync points:
                              // [0] group waits and [1] gate waits that gave up, [2] levels recomputed
     int* lflags;             // dataflow: the call's per-level flags (kLkFlag* below, zeroed with
@@ -260,17 +267,11 @@ struct LkLaunch {
     // on it instead of on everything enqueued on s so far (the second frames' pyramids may still be
     // in flight on s)
     hipEvent_t prev_ready = nullptr;
-    hipEvent_t out_free = nullptr;   // (may be null) the previous call's outputs have been read
-    int parity = 0;
 };
 // Dataflow (s2, flow_ev and done non-null): the level launches alternate between s and s2, so level
 // L-1 starts in level L's tail; its groups wait for their pair's level-L groups (done counters).
 // Used when every XCD's work range holds two or more whole pairs (batch a multiple of 8, at least
 // 16) and pairs' next_pts do not share 128-B lines (npts % 16 == 0).
-// Cross-call overlap (call pipelining): parity 1 swaps which of s / s2 carries the even levels, so
-// the next call's first level can start on the other stream while this call's classify / fit / warp
-// run on s; qctr and done must then be the parity's own counters and a.carry non-null, and out_free
-// is waited for before level 0 writes next_pts / status.
 // Dataflow fallback: a group whose wait gives up (the coarser level's launch was not dispatched in
 // time: a preempted, shared or serialized device) abandons its level, which then drains without
 // computing; right behind each level's launch, on its stream and after the coarser level's (redo_ev),

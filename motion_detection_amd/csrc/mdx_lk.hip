@@ -140,22 +140,15 @@ __device__ __forceinline__ void wave_lds_fence()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// k_lk_iter: 5 waves/SIMD (<= 102 VGPRs; measured 3% faster than 6 at <= 80)
-#ifndef MDX_LK_WPE
-#define MDX_LK_WPE 4
-#endif
-#ifndef MDX_LK_NB
-#define MDX_LK_NB 2
-#endif
+// k_lk_iter: tuned for 5 waves/SIMD (<= 102 VGPRs; measured 3% faster than 6 at <= 80).  The
+// constant is amdgpu_waves_per_eu's minimum, the floor the compiler must keep, not that target.
+constexpr int kLkIterWavesPerEU = 4;
 // Dataflow waits are bounded (LkArgs::spin_max s_sleep(8) polls, ~0.1 s by default): past that a
 // group proceeds regardless and its wave stops waiting, so the launch drains instead of hanging.
 // Every such give-up is counted in LkArgs::err, which the host reads at its next sync point and
 // turns into MDX_EHIP: a timed-out hand-off is never a silent wrong result.
-#ifndef MDX_LK_RFIRST
-#define MDX_LK_RFIRST 0
-#endif
-constexpr int kLkIterWavesPerEU = MDX_LK_WPE;
 typedef __attribute__((address_space(3))) void* lds_ptr;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 // volatile LDS views: each access stays one ds_read_b64 / ds_read_b128 (never merged into a
 // half-rate read2 or narrowed)
@@ -380,6 +373,7 @@ __global__ __launch_bounds__(256) void k_lk_class_fused(const uint8_t* __restric
 // beyond the union is moved.
 template <int G, int UW>
 struct LkShape {
+    static constexpr int UWIDTH = UW;                         // union columns per slot
     static constexpr int LPS = 4 * G;                         // lanes per slot
     static constexpr int S = 64 / LPS;                        // slots per wave
     static constexpr int NP = (UW + 2 * LPS - 1) / (2 * LPS); // A pass: 16-B (2-pair) loads per lane and row
@@ -412,124 +406,74 @@ __device__ __forceinline__ GroupGeom group_geom(const LkArgs& a, const ClassLeve
     r.valid = gxv >= 0;
     r.gx = r.valid ? gxv : 0;
     r.gy = yo[row];
-    const float scale = (float)(1. / (1 << level));
-    r.ipx = (int)floorf((float)(r.gx * a.pixel_step) * scale - 19.5f);
-    r.ipy = (int)floorf((float)(r.gy * a.pixel_step) * scale - 19.5f);
+    r.ipx = lk_win_origin(r.gx, a.pixel_step, level);
+    r.ipy = lk_win_origin(r.gy, a.pixel_step, level);
     // a group's first entry is a real point (runs start at multiples of G, padding at their ends)
     // and its leftmost one (runs sorted by x)
     const int gx0 = has ? xo[e0] : 0;
-    const int ipx0 = (int)floorf((float)(gx0 * a.pixel_step) * scale - 19.5f);
+    const int ipx0 = lk_win_origin(gx0, a.pixel_step, level);
     const int m = (1 << level) - 1;
     const int cx = class_of(a.cmap, level, 0, (gx0 * a.pixel_step) & m);
     const int cy = class_of(a.cmap, level, 1, (r.gy * a.pixel_step) & m);
     const int ub = min(max(ipx0 + kPad, 0), C.PW - UW);            // union start column
     r.off = min(max(r.ipx + kPad - ub, 0), UW - kWin);
-    r.v0 = min(max(r.ipy + kPad, 0), C.UH - kWin);
+    r.v0 = lk_win_row0(r.ipy, C.UH);
     r.ubase = (uint32_t)(C.off + (long long)(cy * C.nrx + cx) * C.class_bytes) + 8u * (uint32_t)ub;
     return r;
 }
 
-// ---- A pass.  grid: x -> wave (S static groups), y -> pair (XCD-remapped as one range).  Each
-// lane loads 2 (D, C) pairs per 16-B load and stages the two D words; the chain reads are D only.
-template <int G, int UW>
-__global__ __launch_bounds__(64) void k_lk_A(LkArgs a, const uint8_t* __restrict__ cls, float4* __restrict__ Ab,
-                                             int* __restrict__ qctr, int level, int ngroups)
+// Union-row staging.  Lane `lane` of 1-KiB LDS-DMA piece c fills bytes 1024c + 16 lane of the wave's
+// [slot][UW][D, C] row image, i.e. slot sp's union bytes wb: its source is that slot's union row
+// (`mine`: this lane's slot's byte offset in the class slab, uniform over the slot) plus wb.  The last
+// piece may reach past the image (sp >= S): those lanes get some slot's offset, and the caller keeps
+// them from fetching it (k_lk_iter masks them at the DMA, the A kernels: LkRowImages::mask_past).
+template <typename Sh>
+__device__ __forceinline__ void lk_piece_offsets(uint32_t mine, int lane, uint32_t (&uoff)[Sh::ND])
 {
-    using Sh = LkShape<G, UW>;
-    constexpr int LPS = Sh::LPS, S = Sh::S, ND = Sh::ND;
-    constexpr int NB = 3;                                          // row images: NB - 1 rows in flight ahead
-    constexpr float FLT_SCALE = 1.f / (1 << 20);
-    // [slot][UW][D, C]: the wave's union row images, filled by LDS-DMA like k_lk_iter's; one
-    // __shared__ array per buffer, so that no compiler wait ties a row's reads to later rows' DMA
-    __shared__ __attribute__((aligned(16))) uint32_t img0[ND * 256];
-    __shared__ __attribute__((aligned(16))) uint32_t img1[ND * 256];
-    __shared__ __attribute__((aligned(16))) uint32_t img2[ND * 256];
-    static_assert(NB == 3, "three row images");
-
-    const int lane = threadIdx.x, k = lane & 3, slot = lane / LPS, sl = lane % LPS;
-    const int nw = gridDim.x;
-    const int bid = xcd_remap(blockIdx.x + nw * blockIdx.y, nw * gridDim.y);
-    const int pair = bid / nw, w = bid % nw;
-    if (bid == 0 && lane < 8) qctr[(level * 8 + lane) * kCtrPad] = 0;   // k_lk_iter's queue heads
-    const ClassLevel& C = a.plan.lv[level];
-    const Level L = a.g.lv[level];
-    const int g = w * S + slot;
-    const GroupGeom q = group_geom<G, UW>(a, C, level, g < ngroups ? g : -1, sl);
-    bool ok = q.valid && !(q.ipx < -kWin || q.ipx >= L.w || q.ipy < -kWin || q.ipy >= L.h);
-
-    const __amdgpu_buffer_rsrc_t crs = buf_rsrc(cls + (long long)pair * a.plan.bytes_per_pair, a.plan.bytes_per_pair);
-    const uint32_t rowb = (uint32_t)C.PW * 8;
-    // lane L of piece c fills image bytes 1024c + 16L: slot sp's union bytes wb (past the image:
-    // an out-of-range offset, zeros)
-    uint32_t uoff[ND];
-    {
-        const uint32_t mine = q.ubase + (uint32_t)q.v0 * rowb;
 #pragma unroll
-        for (int c = 0; c < ND; c++) {
-            const int P = 1024 * c + 16 * lane;
-            const int sp = P / (8 * UW), wb = P % (8 * UW);
-            const uint32_t src = (uint32_t)__shfl((int)mine, (sp < S ? sp : 0) * LPS) + (uint32_t)wb;
-            uoff[c] = sp < S ? src : 0x80000000u;
-        }
+    for (int c = 0; c < Sh::ND; c++) {
+        const int P = 1024 * c + 16 * lane;
+        const int sp = P / (8 * Sh::UWIDTH), wb = P % (8 * Sh::UWIDTH);
+        uoff[c] = (uint32_t)__shfl((int)mine, sp * Sh::LPS) + (uint32_t)wb;
     }
-    auto ibuf = [&](auto bc) -> uint32_t* {
-        constexpr int bb = decltype(bc)::value;
-        if constexpr (bb == 0) return img0;
-        else if constexpr (bb == 1) return img1;
+}
+
+// The A kernels' three row images, filled by LDS-DMA like k_lk_iter's (two rows in flight ahead of
+// the one being summed).  One __shared__ array per image (the kernel's: img0 .. img2), so that no
+// compiler wait ties a row's reads to later rows' DMA.  uoff: the kernel's lk_piece_offsets of the
+// next row to fetch.
+template <typename Sh>
+struct LkRowImages {
+    lds_u32 *img0, *img1, *img2;  // [slot][UW][D, C]
+    __amdgpu_buffer_rsrc_t crs;   // the pair's class slab
+    uint32_t rowb;                // bytes per plane row
+
+    template <int B>
+    __device__ __forceinline__ lds_u32* ibuf() const
+    {
+        if constexpr (B == 0) return img0;
+        else if constexpr (B == 1) return img1;
         else return img2;
-    };
-    auto dma = [&](auto bc) {
-        uint32_t* I = ibuf(bc);
+    }
+    // lanes past the image fetch from out of the descriptor's range (zeros)
+    __device__ __forceinline__ void mask_past(int lane, uint32_t (&uoff)[Sh::ND]) const
+    {
 #pragma unroll
-        for (int c = 0; c < ND; c++) {
+        for (int c = 0; c < Sh::ND; c++)
+            if (1024 * c + 16 * lane >= Sh::BYTES) uoff[c] = 0x80000000u;
+    }
+    // the next row into image B; the offsets move on to the row after it
+    template <int B>
+    __device__ __forceinline__ void dma(uint32_t (&uoff)[Sh::ND]) const
+    {
+        lds_u32* I = ibuf<B>();
+#pragma unroll
+        for (int c = 0; c < Sh::ND; c++) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(crs, (lds_ptr)(I + 256 * c), 16, (int)uoff[c], 0, 0, 0);
             uoff[c] += rowb;
         }
-    };
-    const int el = 2 * (slot * UW + q.off + k);
-
-    // lane k owns SSE lane k (columns 4g+k), rows in order; ((P0+P1)+P2)+P3 across the quad
-    f2 sd = {0.f, 0.f};
-    float s12 = 0.f;
-    constexpr int PF = NB - 1;                                     // rows in flight ahead
-    dma(std::integral_constant<int, 0>{});
-    dma(std::integral_constant<int, 1>{});
-    static_for<0, kWin>([&](auto yc) {
-        constexpr int y = decltype(yc)::value;
-        // row y has landed once at most the later rows' pieces are outstanding
-        constexpr int later = (y + PF - 1 < kWin - 1 ? y + PF - 1 : kWin - 1) - y;
-        lk_vmcnt<later * ND>();
-        // row y+PF into the image row y-1 used (its reads were consumed last iteration)
-        if constexpr (y + PF < kWin) dma(std::integral_constant<int, (y + PF) % NB>{});
-        __builtin_amdgcn_sched_barrier(0);
-        lds_u2v* lE = (lds_u2v*)(ibuf(std::integral_constant<int, y % NB>{}) + el);
-        uint32_t dw[10];
-#pragma unroll
-        for (int gi = 0; gi < 10; gi++) dw[gi] = lE[4 * gi].x;      // the D word of pair q.off + k + 4 gi
-#pragma unroll
-        for (int gi = 0; gi < 10; gi++) {
-            const uint32_t d = dw[gi];
-            const f2 f = {(float)(int16_t)d, (float)((int)d >> 16)};
-            // the reference rounds each product to float, then adds (_mm_mul_ps, _mm_add_ps).
-            // |Ix|, |Iy| <= 4080 (Scharr of u8, interpolated), so every product is below 2^24 and
-            // exact in float: one fused multiply-add rounds exactly like the two operations
-            sd = __builtin_elementwise_fma(f, f, sd);      // (Ix*Ix, Iy*Iy)
-            s12 = __builtin_fmaf(f.x, f.y, s12);           // Ix*Iy
-        }
-    });
-    const float a11 = ((quad_bcast<0>(sd.x) + quad_bcast<1>(sd.x)) + quad_bcast<2>(sd.x)) + quad_bcast<3>(sd.x);
-    const float a12 = ((quad_bcast<0>(s12) + quad_bcast<1>(s12)) + quad_bcast<2>(s12)) + quad_bcast<3>(s12);
-    const float a22 = ((quad_bcast<0>(sd.y) + quad_bcast<1>(sd.y)) + quad_bcast<2>(sd.y)) + quad_bcast<3>(sd.y);
-    const float A11 = a11 * FLT_SCALE, A12 = a12 * FLT_SCALE, A22 = a22 * FLT_SCALE;
-    float Dinv = 0.f;
-    if (ok) {
-        const float D = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - __builtin_sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
-                             (float)(2 * kWin * kWin);
-        if (!(minEig < a.min_eig || D < FLT_EPSILON)) Dinv = 1.f / D;
     }
-    if (q.valid && k == 0) Ab[(long long)pair * a.npts + q.gx * a.ny + q.gy] = make_float4(A11, A12, A22, Dinv);
-}
+};
 
 // the gradient sums of one window (lane k: SSE lane k's partials) -> (A11, A12, A22, 1/D or 0),
 // the quad combine ((P0+P1)+P2)+P3 and LKTrackerInvoker's minEig / determinant tests
@@ -550,6 +494,71 @@ __device__ __forceinline__ float4 lk_A_result(f2 sd, float s12, bool ok, float m
     return make_float4(A11, A12, A22, Dinv);
 }
 
+// ---- A pass.  grid: x -> wave (S static groups), y -> pair (XCD-remapped as one range).  The
+// chain reads are D only.
+template <int G, int UW>
+__global__ __launch_bounds__(64) void k_lk_A(LkArgs a, const uint8_t* __restrict__ cls, float4* __restrict__ Ab,
+                                             int* __restrict__ qctr, int level, int ngroups)
+{
+    using Sh = LkShape<G, UW>;
+    constexpr int LPS = Sh::LPS, S = Sh::S, ND = Sh::ND;
+    constexpr int NB = 3;                                          // row images: NB - 1 rows in flight ahead
+    __shared__ __attribute__((aligned(16))) uint32_t img0[ND * 256];   // LkRowImages: one array per image
+    __shared__ __attribute__((aligned(16))) uint32_t img1[ND * 256];
+    __shared__ __attribute__((aligned(16))) uint32_t img2[ND * 256];
+
+    const int lane = threadIdx.x, k = lane & 3, slot = lane / LPS, sl = lane % LPS;
+    const int nw = gridDim.x;
+    const int bid = xcd_remap(blockIdx.x + nw * blockIdx.y, nw * gridDim.y);
+    const int pair = bid / nw, w = bid % nw;
+    if (bid == 0 && lane < 8) qctr[(level * 8 + lane) * kCtrPad] = 0;   // k_lk_iter's queue heads
+    const ClassLevel& C = a.plan.lv[level];
+    const Level L = a.g.lv[level];
+    const int g = w * S + slot;
+    const GroupGeom q = group_geom<G, UW>(a, C, level, g < ngroups ? g : -1, sl);
+    bool ok = q.valid && !(q.ipx < -kWin || q.ipx >= L.w || q.ipy < -kWin || q.ipy >= L.h);
+
+    LkRowImages<Sh> im{(lds_u32*)img0, (lds_u32*)img1, (lds_u32*)img2,
+                       buf_rsrc(cls + (long long)pair * a.plan.bytes_per_pair, a.plan.bytes_per_pair),
+                       (uint32_t)C.PW * 8};
+    uint32_t uoff[ND];
+    lk_piece_offsets<Sh>(q.ubase + (uint32_t)q.v0 * im.rowb, lane, uoff);
+    im.mask_past(lane, uoff);
+    const int el = 2 * (slot * UW + q.off + k);
+
+    // lane k owns SSE lane k (columns 4g+k), rows in order; ((P0+P1)+P2)+P3 across the quad
+    f2 sd = {0.f, 0.f};
+    float s12 = 0.f;
+    constexpr int PF = NB - 1;                                     // rows in flight ahead
+    im.template dma<0>(uoff);
+    im.template dma<1>(uoff);
+    static_for<0, kWin>([&](auto yc) {
+        constexpr int y = decltype(yc)::value;
+        // row y has landed once at most the later rows' pieces are outstanding
+        constexpr int later = (y + PF - 1 < kWin - 1 ? y + PF - 1 : kWin - 1) - y;
+        lk_vmcnt<later * ND>();
+        // row y+PF into the image row y-1 used (its reads were consumed last iteration)
+        if constexpr (y + PF < kWin) im.template dma<(y + PF) % NB>(uoff);
+        __builtin_amdgcn_sched_barrier(0);
+        lds_u2v* lE = (lds_u2v*)(im.template ibuf<y % NB>() + el);
+        uint32_t dw[10];
+#pragma unroll
+        for (int gi = 0; gi < 10; gi++) dw[gi] = lE[4 * gi].x;      // the D word of pair q.off + k + 4 gi
+#pragma unroll
+        for (int gi = 0; gi < 10; gi++) {
+            const uint32_t d = dw[gi];
+            const f2 f = {(float)(int16_t)d, (float)((int)d >> 16)};
+            // the reference rounds each product to float, then adds (_mm_mul_ps, _mm_add_ps).
+            // |Ix|, |Iy| <= 4080 (Scharr of u8, interpolated), so every product is below 2^24 and
+            // exact in float: one fused multiply-add rounds exactly like the two operations
+            sd = __builtin_elementwise_fma(f, f, sd);      // (Ix*Ix, Iy*Iy)
+            s12 = __builtin_fmaf(f.x, f.y, s12);           // Ix*Iy
+        }
+    });
+    const float4 r = lk_A_result(sd, s12, ok, a.min_eig);
+    if (q.valid && k == 0) Ab[(long long)pair * a.npts + q.gx * a.ny + q.gy] = r;
+}
+
 // ---- A pass per row strip.  Neighbouring grid rows of one residue class have windows that start
 // `asp` plane rows apart (5 at pixel_step 10 above level 0, 10 at level 0), so every plane row lies
 // in 40 / asp of them: k_lk_A re-reads each plane row that many times.  Here a wave owns S column
@@ -566,7 +575,7 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
 {
     using Sh = LkShape<G, UW>;
     constexpr int LPS = Sh::LPS, S = Sh::S, ND = Sh::ND;
-    __shared__ __attribute__((aligned(16))) uint32_t img0[ND * 256];
+    __shared__ __attribute__((aligned(16))) uint32_t img0[ND * 256];   // LkRowImages: one array per image
     __shared__ __attribute__((aligned(16))) uint32_t img1[ND * 256];
     __shared__ __attribute__((aligned(16))) uint32_t img2[ND * 256];
 
@@ -583,52 +592,29 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
     const int16_t* yo = xo + C.nxp;
     const int r0 = a.ord[C.strip_off + 2 * strip], nr = a.ord[C.strip_off + 2 * strip + 1];
     const int asp = C.asp;
-    const float scale = (float)(1. / (1 << level));
     const int m = (1 << level) - 1;
     // column geometry of this lane quad's point (group_geom's, with the strip's first row)
     const int gx0 = cg < ncg ? xo[cg * G] : -1;
     const int gxv = cg < ncg ? xo[cg * G + (sl >> 2)] : -1;
     const bool valid = gxv >= 0;
     const int gx = valid ? gxv : 0;
-    const int ipx = (int)floorf((float)(gx * a.pixel_step) * scale - 19.5f);
+    const int ipx = lk_win_origin(gx, a.pixel_step, level);
     const int gy0 = yo[r0];
-    const int ipx0 = (int)floorf((float)((gx0 >= 0 ? gx0 : 0) * a.pixel_step) * scale - 19.5f);
+    const int ipx0 = lk_win_origin(gx0 >= 0 ? gx0 : 0, a.pixel_step, level);
     const int cx = class_of(a.cmap, level, 0, ((gx0 >= 0 ? gx0 : 0) * a.pixel_step) & m);
     const int cy = class_of(a.cmap, level, 1, (gy0 * a.pixel_step) & m);
     const int ub = min(max(ipx0 + kPad, 0), C.PW - UW);
     const int off = min(max(ipx + kPad - ub, 0), UW - kWin);
     const uint32_t ubase = (uint32_t)(C.off + (long long)(cy * C.nrx + cx) * C.class_bytes) + 8u * (uint32_t)ub;
-    const int ipy0 = (int)floorf((float)(gy0 * a.pixel_step) * scale - 19.5f);
-    const int v00 = min(max(ipy0 + kPad, 0), C.UH - kWin);
+    const int v00 = lk_win_row0(lk_win_origin(gy0, a.pixel_step, level), C.UH);
     const int R = (nr - 1) * asp + kWin;                           // plane rows of the strip
 
-    const __amdgpu_buffer_rsrc_t crs = buf_rsrc(cls + (long long)pair * a.plan.bytes_per_pair, a.plan.bytes_per_pair);
-    const uint32_t rowb = (uint32_t)C.PW * 8;
+    LkRowImages<Sh> im{(lds_u32*)img0, (lds_u32*)img1, (lds_u32*)img2,
+                       buf_rsrc(cls + (long long)pair * a.plan.bytes_per_pair, a.plan.bytes_per_pair),
+                       (uint32_t)C.PW * 8};
     uint32_t uoff[ND];
-    {
-        const uint32_t mine = ubase + (uint32_t)v00 * rowb;
-#pragma unroll
-        for (int c = 0; c < ND; c++) {
-            const int P = 1024 * c + 16 * lane;
-            const int sp = P / (8 * UW), wb = P % (8 * UW);
-            const uint32_t src = (uint32_t)__shfl((int)mine, (sp < S ? sp : 0) * LPS) + (uint32_t)wb;
-            uoff[c] = sp < S ? src : 0x80000000u;
-        }
-    }
-    auto ibuf = [&](auto bc) -> uint32_t* {
-        constexpr int bb = decltype(bc)::value;
-        if constexpr (bb == 0) return img0;
-        else if constexpr (bb == 1) return img1;
-        else return img2;
-    };
-    auto dma = [&](auto bc) {
-        uint32_t* I = ibuf(bc);
-#pragma unroll
-        for (int c = 0; c < ND; c++) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(crs, (lds_ptr)(I + 256 * c), 16, (int)uoff[c], 0, 0, 0);
-            uoff[c] += rowb;
-        }
-    };
+    lk_piece_offsets<Sh>(ubase + (uint32_t)v00 * im.rowb, lane, uoff);
+    im.mask_past(lane, uoff);
     const int el = 2 * (slot * UW + off + k);
 
     // window slots: rin[s] = rows the slot's window has summed (-1: idle), jw[s] = its strip row
@@ -645,7 +631,7 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
     int nextj = 0;
     auto finish = [&](int j, f2 sdv, float s12v) {
         const int gy = yo[r0 + j];
-        const int ipy = (int)floorf((float)(gy * a.pixel_step) * scale - 19.5f);
+        const int ipy = lk_win_origin(gy, a.pixel_step, level);
         const bool ok = valid && !(ipx < -kWin || ipx >= L.w || ipy < -kWin || ipy >= L.h);
         const float4 r = lk_A_result(sdv, s12v, ok, a.min_eig);
         if (valid && k == 0) Ab[(long long)pair * a.npts + gx * a.ny + gy] = r;
@@ -655,9 +641,10 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
         // row t has landed once only row t + 1's pieces may be outstanding
         if (t + 1 < R) lk_vmcnt<ND>();
         else lk_vmcnt0();
-        if (t + 2 < R) dma(std::integral_constant<int, (decltype(bc)::value + 2) % 3>{});
+        constexpr int B = decltype(bc)::value;
+        if (t + 2 < R) im.template dma<(B + 2) % 3>(uoff);
         __builtin_amdgcn_sched_barrier(0);
-        lds_u2v* lE = (lds_u2v*)(ibuf(bc) + el);
+        lds_u2v* lE = (lds_u2v*)(im.template ibuf<B>() + el);
         uint32_t dw[10];
 #pragma unroll
         for (int gi = 0; gi < 10; gi++) dw[gi] = lE[4 * gi].x;
@@ -692,8 +679,8 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
             }
         });
     };
-    dma(std::integral_constant<int, 0>{});
-    if (R > 1) dma(std::integral_constant<int, 1>{});
+    im.template dma<0>(uoff);
+    if (R > 1) im.template dma<1>(uoff);
 #pragma unroll 1
     for (int t = 0; t < R; t += 3) {
         row(t, std::integral_constant<int, 0>{});
@@ -710,7 +697,7 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
 // separate launches from maxLevel down to 0; the position carried between them is next_pts (the
 // reference's nextPts[ptidx], stored every level).
 //
-// Rows arrive by LDS-DMA (buffer_load ... lds), NB - 1 rows ahead, retired by an explicit vmcnt
+// Rows arrive by LDS-DMA (buffer_load ... lds), one row ahead, retired by an explicit vmcnt
 // at the top of each row (the compiler does not track LDS-DMA completion; it only orders LDS
 // reads after DMA into the same __shared__ object, hence one array per row buffer):
 //  * the union rows of all S slots: ND pieces of 1 KiB.  A piece's LDS destination is fixed
@@ -731,19 +718,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
     constexpr float HALFW = 19.5f;
     constexpr float FLT_SCALE = 1.f / (1 << 20);
     constexpr int UB = S * UW;                                    // (D, C) pairs per union buffer
-    // Row buffers: window rows are fetched NB - 1 ahead of the row being summed.  One __shared__
-    // array per buffer, so that the compiler sees a row's LDS reads and the DMA into another
-    // buffer as disjoint: with one [NB][...] array it put a vmcnt(0) -- a wait for the DMA just
-    // issued -- in front of every read that followed a DMA, and no row overlapped its fetch.
-    constexpr int NB = MDX_LK_NB;
-    static_assert(NB == 2 || NB == 3, "row buffers");
-    static_assert(kWin == 40, "row schedule (20 row pairs; 6 row sextets + 4)");
+    // Row buffers: two, a window row is fetched while the one before it is summed (three measured
+    // slower, profiles/r05_ab_lk_nb3.txt).  One __shared__ array per buffer, so that the compiler
+    // sees a row's LDS reads and the DMA into the other buffer as disjoint: with one [2][...] array
+    // it put a vmcnt(0) -- a wait for the DMA just issued -- in front of every read that followed a
+    // DMA, and no row overlapped its fetch.
+    static_assert(kWin % 2 == 0, "row schedule (row pairs)");
     __shared__ __attribute__((aligned(16))) uint32_t dU0[2 * UB];   // [slot][UW][D, C]
     __shared__ __attribute__((aligned(16))) uint32_t dU1[2 * UB];
-    __shared__ __attribute__((aligned(16))) uint32_t dU2[NB > 2 ? 2 * UB : 4];
     __shared__ __attribute__((aligned(16))) uint32_t dJ0[256];      // [quad][16]
     __shared__ __attribute__((aligned(16))) uint32_t dJ1[256];
-    __shared__ __attribute__((aligned(16))) uint32_t dJ2[NB > 2 ? 256 : 4];
 
     const int lane = threadIdx.x, k = lane & 3, slot = lane / LPS, sl = lane % LPS;
     const unsigned long long smask = ((1ull << LPS) - 1) << (slot * LPS);
@@ -755,7 +739,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
     int* const a_lflags = DF ? a.lflags : nullptr;
     const int a_redo = DF ? a.redo : 0;
     const int dep_groups = DF ? a.dep_groups : 0;
-    const int dep_points = DF ? a.dep_points : 0;
     const long long T = (long long)batch * ngroups;
     const long long cb = T * xcd / 8, ce = T * (xcd + 1) / 8;     // this XCD's range of the work list
     const int p0 = (int)(cb / ngroups);
@@ -826,17 +809,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
         if (a_done && level > 0) {
             // the group's points have their level result: once this wave's stores are done, one
             // lane of the slot counts the group for its pair (MI355X_MICROARCH.md hand-off: sc1
-            // stores, vmcnt(0), agent atomic; the reader polls and loads sc1) -- or, per-point
-            // dataflow, each point's lane stamps the point with the call's epoch
+            // stores, vmcnt(0), agent atomic; the reader polls and loads sc1)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (dep_points) {
-                if (q.valid && k == 0)
-                    __hip_atomic_store(a.pflags + level * a.pf_lstride + po, a.epoch, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            } else if (sl == 0) {
+            if (sl == 0)
                 __hip_atomic_fetch_add(a_done + (level * a.done_stride + pair) * kCtrPad, 1, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
-            }
         }
     };
 
@@ -872,27 +849,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
                     } else {
                         float2 p = make_float2(0.f, 0.f);
                         const float* src = a.carry ? a.carry + (level + 1) * a.carry_lstride : a.next_pts;
-                        const bool wait_pt = dep_points && level < a.maxl;
-                        if (dep_groups || wait_pt) {
+                        if (dep_groups) {
                             // dataflow: the coarser level may still run -- wait until every group of
-                            // this pair has retired there (per-point dataflow: until this lane's
-                            // point has; bounded: the coarser level's waves are resident and drain
-                            // their queue), then read the carried points past L1.  A wait that
-                            // gives up abandons the level (every later wait sees the flag): its
-                            // groups drain without computing, and its recompute launch
-                            // (launch_lk_v2) runs it again once the coarser level is done.
-                            const bool waiter = wait_pt ? (q.valid && k == 0) : (sl == 0);
-                            if (waiter && !gave_up) {
+                            // this pair has retired there (bounded: the coarser level's waves are
+                            // resident and drain their queue), then read the carried points past
+                            // L1.  A wait that gives up abandons the level (every later wait sees
+                            // the flag): its groups drain without computing, and its recompute
+                            // launch (launch_lk_v2) runs it again once the coarser level is done.
+                            if (sl == 0 && !gave_up) {
                                 // polls back off (1 .. 16 sleeps between loads): thousands of
                                 // waiting waves polling one line would load its L2 channel
-                                const int* d = wait_pt ? a.pflags + (level + 1) * a.pf_lstride + po
-                                                       : a_done + ((level + 1) * a.done_stride + pair) * kCtrPad;
-                                const int target = wait_pt ? a.epoch : dep_groups;
+                                const int* d = a_done + ((level + 1) * a.done_stride + pair) * kCtrPad;
                                 int slept = 0, gap = 1;
                                 bool mine = false;
                                 if (a.spin_max < 0) mine = true;   // fault injection (tests)
                                 while (!mine &&
-                                       __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+                                       __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < dep_groups) {
                                     if (slept >= a.spin_max) {
                                         mine = true;
                                         break;
@@ -928,7 +900,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
                     }
                     act = Dinv > 0.f;   // real point, window inside, eigenvalue / determinant tests passed
                     // an abandoned level retires its groups at once (its recompute redoes them)
-                    if ((dep_groups || dep_points) && (__ballot(gave_up) & smask)) act = false;
+                    if (dep_groups && (__ballot(gave_up) & smask)) act = false;
                     status = (level == 0 && q.valid && !act) ? 0 : 1;
                     nx = npx - HALFW;
                     ny = npy - HALFW;
@@ -964,28 +936,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
         const unsigned sel = (unsigned)o | 0x0c00u | ((unsigned)(o + 1) << 16) | 0x0c000000u;
         // this lane's 16 J bytes: the quad's first 12 dwords cover every lane's taps
         uint32_t joff = jrel + jbase + (uint32_t)(iny * pitch + (inx & ~3) + 16 * k);
-        // union sources: lane L of piece c fills image bytes 1024c + 16L, i.e. slot sp's pair bytes wb
+        // union sources (the lanes past the image are masked at the DMA)
         uint32_t uoff[ND];
-        {
-            const uint32_t mine = q.ubase + (uint32_t)q.v0 * rowb;
-#pragma unroll
-            for (int c = 0; c < ND; c++) {
-                const int P = 1024 * c + 16 * lane;
-                const int sp = P / (8 * UW), wb = P % (8 * UW);
-                uoff[c] = (uint32_t)__shfl((int)mine, sp * LPS) + (uint32_t)wb;
-            }
-        }
+        lk_piece_offsets<Sh>(q.ubase + (uint32_t)q.v0 * rowb, lane, uoff);
         auto ubuf = [&](auto bc) -> uint32_t* {
-            constexpr int bb = decltype(bc)::value;
-            if constexpr (bb == 0) return dU0;
-            else if constexpr (bb == 1) return dU1;
-            else return dU2;
+            if constexpr (decltype(bc)::value == 0) return dU0;
+            else return dU1;
         };
         auto jbuf = [&](auto bc) -> uint32_t* {
-            constexpr int bb = decltype(bc)::value;
-            if constexpr (bb == 0) return dJ0;
-            else if constexpr (bb == 1) return dJ1;
-            else return dJ2;
+            if constexpr (decltype(bc)::value == 0) return dJ0;
+            else return dJ1;
         };
         // window row yr of the union / J images: the per-lane offsets stay fixed and the row
         // advance moves the descriptor's base (and shrinks its size by as much, so the range check
@@ -1014,53 +974,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
             rj[4] = j1.x; rj[5] = j1.y; rj[6] = j1.z; rj[7] = j1.w;
             rj[8] = j2.x; rj[9] = j2.y; rj[10] = j2.z;
         };
-        // union row r and J row r live in buffer r % NB
-        constexpr int D = NB - 1;
+        // union row r and J row r live in buffer r % 2
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
         // taps of the current window row (pa) are the previous row's lower taps (pb)
         s2 pa[10], pb[10];
         dma_union(I0{}, 0);
         dma_j(I0{}, 0);
         dma_j(I1{}, 1);
-        if constexpr (D == 2) {
-            dma_union(I1{}, 1);
-            dma_j(I2{}, 2);
-        }
-        lk_vmcnt<(D - 1) * (ND + 1)>();
+        lk_vmcnt0();
         {
             uint32_t rj[11];
             read_j(I0{}, rj);
 #pragma unroll
             for (int gi = 0; gi < 10; gi++) pa[gi] = __builtin_bit_cast(s2, __builtin_amdgcn_perm(rj[gi + 1], rj[gi], sel));
         }
-        // row y (y % period = R): wait until union row y and J row y+1 have landed -- the loads
-        // issued for later rows (W of them) may stay in flight -- then fetch union row y+D and J
-        // row y+D+1 into the buffers rows y-1 / y (already summed) used, and sum the row.  An
-        // opaque use of acc pins each row's arithmetic before the next row's wait.
-        auto row = [&](int y, auto Rc, auto Wc, s2 (&up)[10], s2 (&lo)[10]) {
-            constexpr int R = decltype(Rc)::value, W = decltype(Wc)::value;
-            if (y) lk_vmcnt<W>();
-            auto fetch = [&]() {
-                if (y + D < kWin) dma_union(std::integral_constant<int, (R + D) % NB>{}, y + D);
-                if (y + D + 1 <= kWin) dma_j(std::integral_constant<int, (R + D + 1) % NB>{}, y + D + 1);
-                __builtin_amdgcn_sched_barrier(0);
-            };
-#if !MDX_LK_RFIRST
-            fetch();
-#endif
+        // row y (in buffer R = y % 2): wait until union row y and J row y+1 have landed, fetch
+        // union row y+1 and J row y+2 into the buffers rows y-1 / y (already summed) used, and sum
+        // the row.  An opaque use of acc pins each row's arithmetic before the next row's wait.
+        auto row = [&](int y, auto Rc, s2 (&up)[10], s2 (&lo)[10]) {
+            constexpr int R = decltype(Rc)::value;
+            if (y) lk_vmcnt0();
+            if (y + 1 < kWin) dma_union(std::integral_constant<int, 1 - R>{}, y + 1);
+            if (y + 2 <= kWin) dma_j(Rc, y + 2);
+            __builtin_amdgcn_sched_barrier(0);
             // the row's LDS reads back to back (their latencies overlap), then the arithmetic
             uint32_t rj[11];
-            read_j(std::integral_constant<int, (R + 1) % NB>{}, rj);
-            lds_u2v* lE = (lds_u2v*)(ubuf(std::integral_constant<int, R % NB>{}) + el);
+            read_j(std::integral_constant<int, 1 - R>{}, rj);
+            lds_u2v* lE = (lds_u2v*)(ubuf(Rc) + el);
             v2u dcs[10];
 #pragma unroll
             for (int gi = 0; gi < 10; gi++) dcs[gi] = lE[4 * gi];
-#if MDX_LK_RFIRST
-            __builtin_amdgcn_sched_barrier(0);
-            fetch();
-#endif
 #pragma unroll
             for (int gi = 0; gi < 10; gi++) {
                 const v2u dc = dcs[gi];
@@ -1074,28 +1018,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
             }
             asm volatile("" : "+v"(acc));
         };
-        if constexpr (NB == 2) {
-            using W = std::integral_constant<int, 0>;
 #pragma unroll 1
-            for (int y = 0; y < kWin; y += 2) {
-                row(y, I0{}, W{}, pa, pb);
-                row(y + 1, I1{}, W{}, pb, pa);
-            }
-        } else {
-            using W = std::integral_constant<int, ND + 1>;
-#pragma unroll 1
-            for (int y = 0; y < 36; y += 6) {
-                row(y, I0{}, W{}, pa, pb);
-                row(y + 1, I1{}, W{}, pb, pa);
-                row(y + 2, I2{}, W{}, pa, pb);
-                row(y + 3, std::integral_constant<int, 3>{}, W{}, pb, pa);
-                row(y + 4, std::integral_constant<int, 4>{}, W{}, pa, pb);
-                row(y + 5, std::integral_constant<int, 5>{}, W{}, pb, pa);
-            }
-            row(36, I0{}, W{}, pa, pb);
-            row(37, I1{}, W{}, pb, pa);
-            row(38, I2{}, W{}, pa, pb);
-            row(39, std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, pb, pa);
+        for (int y = 0; y < kWin; y += 2) {
+            row(y, I0{}, pa, pb);
+            row(y + 1, I1{}, pb, pa);
         }
         if (!act) acc = f2{0.f, 0.f};
         // b = (P0+P2) + (P1+P3) across the quad; inactive quads compute values they ignore
@@ -1198,17 +1124,14 @@ static int lk_iter_resident()
     return v;
 }
 
-template <int G, int UW>
-static int lk_groups(const LkArgs& a, int l)
-{
-    return (a.plan.lv[l].nxp / G) * a.nyg;
-}
+// groups per pair of level l: its column groups on each of the nyg grid rows
+static int lk_groups(const ClassPlan& plan, int l, int nyg) { return (plan.lv[l].nxp / plan.lv[l].G) * nyg; }
 
 template <int G, int UW>
 static void launch_A(hipStream_t s, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab, int* qctr, int l)
 {
     constexpr int S = LkShape<G, UW>::S;
-    const int ngroups = lk_groups<G, UW>(a, l);
+    const int ngroups = lk_groups(a.plan, l, a.nyg);
     const dim3 grid((ngroups + S - 1) / S, batch);
     hipLaunchKernelGGL((k_lk_A<G, UW>), grid, dim3(64), 0, s, a, cls, Ab, qctr, l, ngroups);
 }
@@ -1231,13 +1154,13 @@ static void launch_iter(hipStream_t s, int batch, const LkArgs& a, const uint8_t
                         int l)
 {
     constexpr int S = LkShape<G, UW>::S;
-    const int ngroups = lk_groups<G, UW>(a, l);
+    const int ngroups = lk_groups(a.plan, l, a.nyg);
     // persistent waves, a multiple of 8 so that every XCD range has waves.  Dataflow: each launch
     // leaves part of the chip free, for the aux stream's class planes and A sums of the next level
     // (which must be done before that level's launch can start) and for the coarser level's
     // launch that this one may wait on
     const int need = (int)std::min<long long>(((long long)batch * ngroups + S - 1) / S, 1 << 30);
-    const bool df = a.done || a.redo || a.lflags || a.dep_groups || a.dep_points;
+    const bool df = a.done || a.redo || a.lflags || a.dep_groups;
     int res = df ? lk_iter_resident<G, UW, true>() : lk_iter_resident<G, UW, false>();
     if (a.done) res = res * std::min(std::max(a.flow_cap, 10), 100) / 100;   // the context's (MDX_LK_CAP)
     int W = std::max(8, std::min((need + 7) / 8, res / 8) * 8);
@@ -1265,9 +1188,123 @@ static bool launch_level(bool iter, hipStream_t st, int batch, const LkArgs& a, 
     }
 }
 
+// One sub-batch (pairs p .. p + nb of the call's batch; b: the call's arguments moved to pair p, bcls
+// / bq: its class planes and queue heads), first half: the flow-independent work on the aux stream
+// sa (the context's, without one) -- per level the Scharr planes, the class planes and the A sums.
+static hipError_t lk_enqueue_planes(const LkLaunch& L, hipStream_t sa, int batch, int p, int nb, const LkArgs& a,
+                                    const LkArgs& b, uint8_t* bcls, int* bq)
+{
+    if (L.aux) {
+        hipEvent_t ready = L.prev_ready;
+        if (!ready || p) {   // later sub-batches follow everything on s (their slabs are reused)
+            if (hipError_t e = hipEventRecord(L.ev[kMaxLevels], L.s)) return e;
+            ready = L.ev[kMaxLevels];
+        }
+        if (hipError_t e = hipStreamWaitEvent(sa, ready, 0)) return e;
+    }
+    for (int l = a.maxl; l >= 0; l--) {
+        const ClassLevel& C = a.plan.lv[l];
+        if (L.aux && L.lvl_done) {   // the previous call's level-l iterations read these planes / sums
+            if (hipError_t e = hipStreamWaitEvent(sa, L.lvl_done[l], 0)) return e;
+        }
+        LkClassArgs ca;
+        ca.g = a.g;
+        ca.plan = a.plan;
+        ca.rlist = a.rlist;
+        ca.level = l;
+        if (C.nrx * C.nry <= 4) {
+            // the finest levels: derivatives computed inside the class kernel, no Scharr planes
+            const dim3 grid(((a.g.lv[l].w + 2 * kPad) / 4 + 63) / 64, C.vhi - C.vlo, nb);
+            hipLaunchKernelGGL(k_lk_class_fused, grid, dim3(64), 0, sa, b.pyr1, bcls, ca);
+        } else {
+            const dim3 grid(((a.g.lv[l].w + 2 * kPad) / 4 + 63) / 64, C.vhi - C.vlo, nb * C.nrx * C.nry);
+            // this level's Scharr planes (the caller left them to us): on the aux stream, so
+            // they too run while the coarser levels iterate
+            // (the derivative rows the class planes read: v, v + 1 for plane rows v in [vlo, vhi))
+            if (hipError_t e = launch_scharr(sa, nb, b.pyr1, const_cast<uint32_t*>(b.der), a.g, l, C.vlo, C.vhi + 1))
+                return e;
+            hipLaunchKernelGGL(k_lk_class, grid, dim3(64), 0, sa, b.pyr1, b.der, bcls, ca);
+        }
+        float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
+        if (!launch_level(false, sa, nb, b, bcls, bA, bq, l)) return hipErrorInvalidValue;
+        if (L.aux) {
+            if (hipError_t e = hipEventRecord(L.ev[l], sa)) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+// Second half: the iteration launches -- per level the gate (dataflow), the level and its recompute
+// (dataflow), on s or alternating between s and s2.
+static hipError_t lk_enqueue_iters(const LkLaunch& L, int batch, int p, int nb, const LkArgs& a, const LkArgs& b,
+                                   uint8_t* bcls, int* bq)
+{
+    // dataflow: every XCD's work range must hold whole pairs (the hand-off stays in one L2) and
+    // no two pairs' carried points may share a 128-B line; with one pair per XCD (batch 8) the
+    // next level can only start once the whole level is done there, and the dataflow measured
+    // 1.5% slower than levels in sequence, so it needs at least two
+    const bool flow_ok = L.aux && L.s2 && L.flow_ev && L.done && L.redo_ev && a.err && b.carry &&
+                         (reinterpret_cast<uintptr_t>(b.carry) & 127) == 0 && (a.carry_lstride % 32) == 0;
+    // groups wait for their pair's whole coarser level
+    const bool flow = flow_ok && nb % 8 == 0 && nb >= 16 && a.npts % 16 == 0 &&
+                      (reinterpret_cast<uintptr_t>(b.next_pts) & 127) == 0;
+    int* lflags = flow ? L.done + (long long)kMaxLevels * nb * kCtrPad : nullptr;
+    if (flow) {
+        if (hipError_t e = hipMemsetAsync(L.done, 0, sizeof(int) * ((long long)kMaxLevels * nb + kLkFlagInts) * kCtrPad, L.s))
+            return e;
+        if (hipError_t e = hipEventRecord(L.flow_ev[0], L.s)) return e;   // counters zeroed, front end done
+        if (hipError_t e = hipStreamWaitEvent(L.s2, L.flow_ev[0], 0)) return e;
+    }
+    for (int l = a.maxl; l >= 0; l--) {
+        // levels alternate between the two streams: level l-1 is enqueued behind level l+1
+        // only, so it starts as level l's waves leave
+        hipStream_t st = flow && ((a.maxl - l) & 1) ? L.s2 : L.s;
+        if (L.aux) {
+            if (hipError_t e = hipStreamWaitEvent(st, L.ev[l], 0)) return e;
+        }
+        LkArgs bl = b;
+        bl.done = flow ? L.done : nullptr;
+        bl.done_stride = nb;
+        bl.dep_groups = 0;
+        bl.lflags = lflags;
+        bl.redo = 0;
+        if (flow && l < a.maxl) {   // start in the coarser level's tail, not beside its whole queue
+            const int ngc = lk_groups(a.plan, l + 1, a.nyg), ng = lk_groups(a.plan, l, a.nyg);
+            bl.dep_groups = ngc;
+            hipLaunchKernelGGL(k_lk_gate, dim3(1), dim3(64), 0, st, bq + (l + 1) * 8 * kCtrPad, (long long)nb * ngc,
+                               L.done + (l + 1) * nb * kCtrPad, bl.dep_groups, ng, (long long)nb * ng, a.err,
+                               a.spin_max, lflags + (kLkFlagGiveup + l) * kCtrPad);
+        }
+        float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
+        if (!launch_level(true, st, nb, bl, bcls, bA, bq, l)) return hipErrorInvalidValue;
+        if (flow) {
+            // the level's recompute, behind it on its stream and behind the coarser level's
+            // (launch and recompute): exits at once unless the level gave up or the coarser
+            // one was recomputed.  The planes / A sums it reads are released (lvl_done) after it.
+            if (l < a.maxl) {
+                if (hipError_t e = hipStreamWaitEvent(st, L.redo_ev[l + 1], 0)) return e;
+                LkArgs br = bl;
+                br.done = nullptr;
+                br.dep_groups = 0;
+                br.redo = 1;
+                br.dbg = nullptr;
+                if (!launch_level(true, st, nb, br, bcls, bA, bq, l)) return hipErrorInvalidValue;
+            }
+            if (hipError_t e = hipEventRecord(L.redo_ev[l], st)) return e;
+        }
+        if (L.lvl_done) {
+            if (hipError_t e = hipEventRecord(L.lvl_done[l], st)) return e;
+        }
+    }
+    if (flow) {   // join: everything after the LK (and the next sub-batch) follows both streams
+        if (hipError_t e = hipEventRecord(L.flow_ev[1], L.s2)) return e;
+        if (hipError_t e = hipStreamWaitEvent(L.s, L.flow_ev[1], 0)) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_lk_v2(const LkLaunch& L, int batch, const LkArgs& a)
 {
-    int parity = L.parity;
     // An XCD range spans at most ceil(n/8) + 1 pairs; its class slabs (and pyramids) must stay
     // addressable by 32-bit buffer offsets, so very large batches of large frames run in
     // sub-batches (the plan already guarantees one pair's slab fits).
@@ -1275,7 +1312,6 @@ hipError_t launch_lk_v2(const LkLaunch& L, int batch, const LkArgs& a)
     int sub = batch;
     while (sub > 1 && ((sub + 7) / 8 + 1) * span > 0x7fff0000LL) sub = std::max(1, sub / 2);
     if (a.max_sub > 0) sub = std::max(1, std::min(sub, a.max_sub));   // MDX_LK_SUB (tests), read at mdx_create
-    if (sub < batch) parity = 0;   // sub-batches follow everything on s (their slabs are reused)
     // Class planes and A sums depend on the previous frame only, not on the flow: with an aux
     // stream they run ahead (level L-1's while level L iterates, filling that kernel's tail);
     // every level has its own class planes, A buffer and queue heads, so nothing is overwritten
@@ -1289,129 +1325,12 @@ hipError_t launch_lk_v2(const LkLaunch& L, int batch, const LkArgs& a)
         b.der = a.der + (long long)p * a.g.der_words;
         b.next_pts = a.next_pts + (long long)p * a.npts * 2;
         b.carry = a.carry ? a.carry + (long long)p * a.npts * 2 : nullptr;   // carry_lstride: whole batch
-        b.pflags = a.pflags ? a.pflags + (long long)p * a.npts : nullptr;      // pf_lstride: whole batch
         b.status = a.status + (long long)p * a.npts;
         if (p) b.dbg = nullptr;   // the trace covers the first sub-batch
         uint8_t* bcls = L.cls + (long long)p * a.plan.bytes_per_pair;
         int* bq = L.qctr + si * kMaxLevels * 8 * kCtrPad;
-        if (L.aux) {
-            hipEvent_t ready = L.prev_ready;
-            if (!ready || p) {   // later sub-batches follow everything on s (their slabs are reused)
-                if (hipError_t e = hipEventRecord(L.ev[kMaxLevels], L.s)) return e;
-                ready = L.ev[kMaxLevels];
-            }
-            if (hipError_t e = hipStreamWaitEvent(sa, ready, 0)) return e;
-        }
-        for (int l = a.maxl; l >= 0; l--) {
-            const ClassLevel& C = a.plan.lv[l];
-            if (L.aux && L.lvl_done) {   // the previous call's level-l iterations read these planes / sums
-                if (hipError_t e = hipStreamWaitEvent(sa, L.lvl_done[l], 0)) return e;
-            }
-            LkClassArgs ca;
-            ca.g = a.g;
-            ca.plan = a.plan;
-            ca.rlist = a.rlist;
-            ca.level = l;
-            if (C.nrx * C.nry <= 4) {
-                // the finest levels: derivatives computed inside the class kernel, no Scharr planes
-                const dim3 grid(((a.g.lv[l].w + 2 * kPad) / 4 + 63) / 64, C.vhi - C.vlo, nb);
-                hipLaunchKernelGGL(k_lk_class_fused, grid, dim3(64), 0, sa, b.pyr1, bcls, ca);
-            } else {
-                const dim3 grid(((a.g.lv[l].w + 2 * kPad) / 4 + 63) / 64, C.vhi - C.vlo, nb * C.nrx * C.nry);
-                // this level's Scharr planes (the caller left them to us): on the aux stream, so
-                // they too run while the coarser levels iterate
-                // (the derivative rows the class planes read: v, v + 1 for plane rows v in [vlo, vhi))
-                if (hipError_t e = launch_scharr(sa, nb, b.pyr1, const_cast<uint32_t*>(b.der), a.g, l, C.vlo, C.vhi + 1))
-                    return e;
-                hipLaunchKernelGGL(k_lk_class, grid, dim3(64), 0, sa, b.pyr1, b.der, bcls, ca);
-            }
-            float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
-            if (!launch_level(false, sa, nb, b, bcls, bA, bq, l)) return hipErrorInvalidValue;
-            if (L.aux) {
-                if (hipError_t e = hipEventRecord(L.ev[l], sa)) return e;
-            }
-        }
-        // dataflow: every XCD's work range must hold whole pairs (the hand-off stays in one L2) and
-        // no two pairs' carried points may share a 128-B line; with one pair per XCD (batch 8) the
-        // next level can only start once the whole level is done there, and the dataflow measured
-        // 1.5% slower than levels in sequence, so it needs at least two
-        const bool flow_ok = L.aux && L.s2 && L.flow_ev && L.done && L.redo_ev && a.err && b.carry &&
-                             (reinterpret_cast<uintptr_t>(b.carry) & 127) == 0 && (a.carry_lstride % 32) == 0;
-        // per pair (groups wait for their pair's whole coarser level) where every XCD range holds
-        // two or more whole pairs; per point (groups wait for their own points) for small batches
-        // -- a single pair's level would otherwise wait for the coarser level's slowest group
-        const bool flow_pair = flow_ok && !a.pflow_force && nb % 8 == 0 && nb >= 16 && a.npts % 16 == 0 &&
-                               (reinterpret_cast<uintptr_t>(b.next_pts) & 127) == 0;
-        const bool flow_pt = flow_ok && !flow_pair && b.pflags;
-        const bool flow = flow_pair || flow_pt;
-        int* lflags = flow ? L.done + (long long)kMaxLevels * nb * kCtrPad : nullptr;
-        // the even levels' stream (the first level's) and the odd levels'; parity 1 swaps them so
-        // that this call's first level does not queue behind the previous call's fit / warp on s
-        const bool swap = flow && parity && b.carry;
-        hipStream_t s0 = swap ? L.s2 : L.s, s1 = swap ? L.s : L.s2;
-        if (flow) {
-            if (hipError_t e = hipMemsetAsync(L.done, 0, sizeof(int) * ((long long)kMaxLevels * nb + kLkFlagInts) * kCtrPad, s0))
-                return e;
-            if (hipError_t e = hipEventRecord(L.flow_ev[0], s0)) return e;   // counters zeroed, front end done
-            if (hipError_t e = hipStreamWaitEvent(s1, L.flow_ev[0], 0)) return e;
-        }
-        for (int l = a.maxl; l >= 0; l--) {
-            const ClassLevel& C = a.plan.lv[l];
-            // levels alternate between the two streams: level l-1 is enqueued behind level l+1
-            // only, so it starts as level l's waves leave
-            hipStream_t st = flow && ((a.maxl - l) & 1) ? s1 : s0;
-            if (L.aux) {
-                if (hipError_t e = hipStreamWaitEvent(st, L.ev[l], 0)) return e;
-            }
-            // level 0 writes next_pts / status: the previous call's readers of them come first
-            if (l == 0 && L.out_free) {
-                if (hipError_t e = hipStreamWaitEvent(st, L.out_free, 0)) return e;
-            }
-            LkArgs bl = b;
-            bl.done = flow ? L.done : nullptr;
-            bl.done_stride = nb;
-            bl.dep_groups = 0;
-            bl.lflags = lflags;
-            bl.redo = 0;
-            bl.dep_points = flow_pt ? 1 : 0;
-            if (flow_pair && l < a.maxl) {
-                const ClassLevel& Cp = a.plan.lv[l + 1];
-                bl.dep_groups = (Cp.nxp / Cp.G) * a.nyg;
-            }
-            if (flow && l < a.maxl) {   // start in the coarser level's tail, not beside its whole queue
-                const ClassLevel& Cp = a.plan.lv[l + 1];
-                const int ngc = (Cp.nxp / Cp.G) * a.nyg, ng = (C.nxp / C.G) * a.nyg;
-                // per point: the coarser queue handed out is the whole condition (dep_groups 0)
-                hipLaunchKernelGGL(k_lk_gate, dim3(1), dim3(64), 0, st, bq + (l + 1) * 8 * kCtrPad, (long long)nb * ngc,
-                                   L.done + (l + 1) * nb * kCtrPad, bl.dep_groups, ng, (long long)nb * ng, a.err,
-                                   a.spin_max, lflags + (kLkFlagGiveup + l) * kCtrPad);
-            }
-            float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
-            if (!launch_level(true, st, nb, bl, bcls, bA, bq, l)) return hipErrorInvalidValue;
-            if (flow) {
-                // the level's recompute, behind it on its stream and behind the coarser level's
-                // (launch and recompute): exits at once unless the level gave up or the coarser
-                // one was recomputed.  The planes / A sums it reads are released (lvl_done) after it.
-                if (l < a.maxl) {
-                    if (hipError_t e = hipStreamWaitEvent(st, L.redo_ev[l + 1], 0)) return e;
-                    LkArgs br = bl;
-                    br.done = nullptr;
-                    br.dep_groups = 0;
-                    br.dep_points = 0;
-                    br.redo = 1;
-                    br.dbg = nullptr;
-                    if (!launch_level(true, st, nb, br, bcls, bA, bq, l)) return hipErrorInvalidValue;
-                }
-                if (hipError_t e = hipEventRecord(L.redo_ev[l], st)) return e;
-            }
-            if (L.lvl_done) {
-                if (hipError_t e = hipEventRecord(L.lvl_done[l], st)) return e;
-            }
-        }
-        if (flow) {   // join: everything after the LK (and the next sub-batch) follows both streams
-            if (hipError_t e = hipEventRecord(L.flow_ev[1], L.s2)) return e;
-            if (hipError_t e = hipStreamWaitEvent(L.s, L.flow_ev[1], 0)) return e;
-        }
+        if (hipError_t e = lk_enqueue_planes(L, sa, batch, p, nb, a, b, bcls, bq)) return e;
+        if (hipError_t e = lk_enqueue_iters(L, batch, p, nb, a, b, bcls, bq)) return e;
     }
     return hipGetLastError();
 }

@@ -51,8 +51,7 @@ static int ensure_class_plan(mdx_ctx* c, const Geometry& g, int w, int h, int ps
             // 4-group's union fits 64 columns (no extra union loads), else 8 (MDX_LK_G forces one)
             C.ord_off = (int)ord.size();
             const int16_t* cmx = cmap + (l * 2 + 0) * 128;
-            const float scale = (float)(1. / (1 << l));
-            auto ipx_of = [&](int gx) { return (int)std::floor((float)(gx * ps) * scale - 19.5f); };
+            auto ipx_of = [&](int gx) { return lk_win_origin(gx, ps, l); };
             std::vector<std::vector<int16_t>> runs(n[0]);
             for (int i = 0; i < nx; i++) runs[cmx[(i * ps) & m]].push_back((int16_t)i);
             auto union_of = [&](int G) {
@@ -101,7 +100,7 @@ static int ensure_class_plan(mdx_ctx* c, const Geometry& g, int w, int h, int ps
             // A-sum strips (k_lk_A_rows): runs of one y-class cut into kAStripRows rows; the first
             // window rows v0 = ipy + 40 of a class's rows must be evenly spaced (asp rows apart)
             const size_t r1 = ord.size();
-            auto v0_row = [&](int gy) { return (int)std::floor((float)(gy * ps) * scale - 19.5f) + kPad; };
+            auto v0_row = [&](int gy) { return lk_win_origin(gy, ps, l) + kPad; };
             int asp = 0;
             bool uniform = true;
             std::vector<int16_t> strips;
@@ -127,7 +126,7 @@ static int ensure_class_plan(mdx_ctx* c, const Geometry& g, int w, int h, int ps
                 i = e;
             }
             if (asp == 0) asp = kWin;   // one row per class: windows never overlap
-            C.asp = uniform && asp >= 5 && c->lk_arows ? asp : 0;
+            C.asp = uniform && asp >= 5 ? asp : 0;
             C.nstrip = (int)strips.size() / 2;
             C.strip_off = (int)ord.size();
             ord.insert(ord.end(), strips.begin(), strips.end());
@@ -138,15 +137,10 @@ static int ensure_class_plan(mdx_ctx* c, const Geometry& g, int w, int h, int ps
             ClassLevel& C = P.lv[l];
             C.UH = g.lv[l].h + 79;
             C.PW = (g.lv[l].w + kPad + std::max(C.UW, 64) + 3) & ~3;
-            // plane rows the band's windows read: first rows v0 = clamp(ipy + 40, 0, UH - 40) of
-            // its first and last grid rows (ipy is monotone in gy), 40 rows each
-            const float scale = (float)(1. / (1 << l));
-            auto v0_of = [&](int gy) {
-                const int ipy = (int)std::floor((float)(gy * ps) * scale - 19.5f);
-                return std::min(std::max(ipy + kPad, 0), C.UH - kWin);
-            };
-            C.vlo = v0_of(gy0);
-            C.vhi = v0_of(gy1 - 1) + kWin;
+            // plane rows the band's windows read: the first rows (lk_win_row0) of its first and
+            // last grid rows (the window origin is monotone in gy), 40 rows each
+            C.vlo = lk_win_row0(lk_win_origin(gy0, ps, l), C.UH);
+            C.vhi = lk_win_row0(lk_win_origin(gy1 - 1, ps, l), C.UH) + kWin;
             C.class_bytes = (long long)C.UH * C.PW * 8;
             C.off = off;
             off += (long long)C.nrx * C.nry * C.class_bytes;
@@ -189,12 +183,31 @@ static inline void mark(mdx_ctx* c, int i, hipStream_t st = nullptr)
     if (c->cur >= 0) (void)hipEventRecord(c->ev[c->cur * 7 + i], st ? st : c->stream);
 }
 
+// The class-plane LK's scratch (mdx_ctx::Abuf), byte offsets: the A sums ([level][pair][point] float4,
+// from 0), the queue heads ([sub-batch][level][XCD] counters), the dataflow counters and flags
+// ([level][pair] + kLkFlagInts counters) and the points carried between levels (per level a
+// [pair][point] float2 array of carry_level bytes, a multiple of 128: with the counter regions whole
+// 128-B lines and npts a multiple of 16 the arrays start on 128-B lines, which the dataflow requires).
+struct LkScratch {
+    size_t qctr, done, carry, carry_level, bytes;
+};
+static LkScratch lk_scratch(int nlev, int batch, int npts)
+{
+    LkScratch s;
+    s.qctr = (size_t)nlev * batch * npts * sizeof(float4);
+    s.done = s.qctr + (size_t)batch * kMaxLevels * 8 * kCtrPad * sizeof(int);
+    s.carry = s.done + ((size_t)kMaxLevels * batch + kLkFlagInts) * kCtrPad * sizeof(int);
+    s.carry_level = ((size_t)batch * npts * 8 + 127) / 128 * 128;
+    s.bytes = s.carry + s.carry_level * nlev;
+    return s;
+}
+
 // The LK of a batch of pairs on the context's stream.  Grid start points (a.prev_pts null) on a
 // dense enough grid take the class-plane kernels, which launch each level's Scharr planes
 // themselves; otherwise the single kernel, after the Scharr planes unless the caller already
 // computed them (have_scharr).  a: every field but the class-plan ones.
 int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int h, int gy0, int gy1, bool have_scharr,
-                hipEvent_t prev_ready, int parity, hipEvent_t out_free)
+                hipEvent_t prev_ready)
 {
     int rc;
     hipStream_t s = c->stream;
@@ -227,60 +240,26 @@ int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int 
         const char* e = std::getenv("MDX_LK_DEBUG_PT");
         a.dbg_pt = e ? std::atoi(e) : -1;
     }
-    // A sums, then per parity (parity < 0: no cross-call overlap, parity 0's) the queue heads
-    // ([sub-batch][level][XCD]), the dataflow counters ([level][pair]) and the points carried
-    // between levels ([pair][point]; cross-call overlap only: the next call's coarse levels then
-    // never touch the next_pts this call's classify still reads)
-    const size_t abytes = (size_t)g.nlev * batch * npts * sizeof(float4);
-    const size_t qbytes = (size_t)batch * kMaxLevels * 8 * kCtrPad * sizeof(int);
-    const size_t dbytes = ((size_t)kMaxLevels * batch + kLkFlagInts) * kCtrPad * sizeof(int);
-    const size_t lbytes = ((size_t)batch * npts * 8 + 127) / 128 * 128;   // one level's carried points
-    const size_t cbytes = lbytes * g.nlev;
-    // per-point dataflow flags: [level][pair][point] epochs, per parity (zeroed once per allocation;
-    // every call's epoch exceeds the earlier ones', so stale stamps never satisfy a wait)
-    const size_t fbytes = ((size_t)batch * npts * 4 + 127) / 128 * 128;
-    const size_t pbytes = fbytes * g.nlev;
-    const size_t per = qbytes + dbytes + cbytes + pbytes;
-    if ((rc = ensure(c, c->Abuf, abytes + 2 * per)) != MDX_OK) return rc;
-    // (re)zeroed whenever the flags move: stale bytes of another layout (A sums, carried points)
-    // could read as large epochs
-    const size_t pf_at = abytes + qbytes + dbytes + cbytes;
-    if (c->lk_epoch >= (1 << 30)) {   // epochs wrap: start again from zeroed flags
-        c->lk_epoch = 0;
-        c->pflag_mem = nullptr;
-    }
-    if (c->pflag_mem != c->Abuf.p || c->pflag_at != pf_at || c->pflag_bytes != pbytes || c->pflag_per != per) {
-        // only the flag regions: the aux stream may already write the A sums of this allocation;
-        // the flags' writers and readers (the iteration launches) follow c->stream
-        for (int q = 0; q < 2; q++)
-            HIP_OR_RETURN(c, hipMemsetAsync(c->Abuf.as<uint8_t>() + abytes + q * per + qbytes + dbytes + cbytes, 0,
-                                            pbytes, c->stream));
-        // the coarsest level may run on the second iteration stream (MDX_LK_XCALL, parity 1), which
-        // does not follow c->stream: finish the zeroing before any launch reads the flags (this runs
-        // only when the flag regions move, i.e. on a reallocation or a layout change)
+    const LkScratch sc = lk_scratch(g.nlev, batch, npts);
+    if ((rc = ensure(c, c->Abuf, sc.bytes)) != MDX_OK) return rc;
+    // A pipelined call's aux work waits for the previous call's iterations level by level (lvl_done),
+    // which keeps the two calls apart only while both put a level's A sums and queue heads in the
+    // same place: when the layout moves, everything enqueued so far finishes first
+    const std::array<size_t, 4> lay = {reinterpret_cast<size_t>(c->Abuf.p), (size_t)g.nlev, (size_t)batch, (size_t)npts};
+    if (c->lk_scratch_key != lay) {
         HIP_OR_RETURN(c, hipStreamSynchronize(c->stream));
-        c->pflag_mem = c->Abuf.p;
-        c->pflag_at = pf_at;
-        c->pflag_bytes = pbytes;
-        c->pflag_per = per;
+        c->lk_scratch_key = lay;
     }
-    const int par = parity < 0 ? 0 : parity;
-    uint8_t* base = c->Abuf.as<uint8_t>() + abytes + par * per;
-    a.carry = reinterpret_cast<float*>(base + qbytes + dbytes);
-    a.carry_lstride = (long long)(lbytes / sizeof(float));
-    a.pflags = c->lk_pflow <= 0 ? nullptr : reinterpret_cast<int*>(base + qbytes + dbytes + cbytes);
-    a.pf_lstride = (long long)(fbytes / sizeof(int));
-    a.epoch = ++c->lk_epoch;
-    a.pflow_force = c->lk_pflow > 1 ? 1 : 0;
+    uint8_t* base = c->Abuf.as<uint8_t>();
+    a.carry = reinterpret_cast<float*>(base + sc.carry);
+    a.carry_lstride = (long long)(sc.carry_level / sizeof(float));
     LkLaunch L = c->lk;
     L.cls = c->cls.as<uint8_t>();
     L.Ab = c->Abuf.as<float4>();
-    L.qctr = reinterpret_cast<int*>(base);
-    L.done = reinterpret_cast<int*>(base + qbytes);
+    L.qctr = reinterpret_cast<int*>(base + sc.qctr);
+    L.done = reinterpret_cast<int*>(base + sc.done);
     L.lvl_done = c->prm.call_pipelining ? c->lvl_done : nullptr;
     L.prev_ready = prev_ready;
-    L.out_free = out_free;
-    L.parity = par;
     HIP_OR_RETURN(c, launch_lk_v2(L, batch, a));
     return MDX_OK;
 }
@@ -414,17 +393,7 @@ static int run_pipeline(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint
         a.nyg = nyb;
         a.next_pts = d_np;
         a.status = d_st;
-        // pipelined calls alternate the LK's stream parity (cross-call overlap: this call's first
-        // level need not wait for the previous call's classify / fit / warp on the context stream);
-        // level 0 waits for the previous call's warp (pyr_free of its half) before writing outputs
-        int parity = -1;
-        hipEvent_t out_free = nullptr;
-        if (pipe && c->lk_xcall) {
-            parity = c->lk_parity;
-            c->lk_parity ^= 1;
-            out_free = c->pyr_free[half ^ 1];
-        }
-        if ((rc = run_lk(c, g, a, batch, w, h, gy0, gy1, false, prev_ready, parity, out_free)) != MDX_OK) return rc;
+        if ((rc = run_lk(c, g, a, batch, w, h, gy0, gy1, false, prev_ready)) != MDX_OK) return rc;
     }
     mark(c, 4);
     if ((rc = ensure(c, c->csum, classify_scratch_bytes(batch, npts))) != MDX_OK) return rc;

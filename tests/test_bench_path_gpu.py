@@ -73,15 +73,11 @@ def _call(c, batch, d1, d2, o, w, h):
                                d_vectors=o.get("vec", 0), d_mask=o["mask"], d_H=o["H"], d_num_vectors=o["num"])
 
 
-@pytest.mark.parametrize("xcall", ["0", "1"])
-def test_benchmarked_path_1080p_x32_pipelined(mdx, oracle, monkeypatch, xcall):
+def test_benchmarked_path_1080p_x32_pipelined(mdx, oracle):
     """bench.py's timed step, twice back to back on different inputs (16 distinct pairs, 8 per call,
     each in 4 of the 32 slots), call pipelining on, one sync at the end: every pair's next_pts
     (float32 bits), status, H (float64 bits), mask and num_vectors -- and the Vec4d of the second
-    call -- equal the oracle's.  xcall "1": the same with MDX_LK_XCALL=1 (read at mdx_create; off by
-    default), whose consecutive calls alternate the LK streams and counter sets so that one call's
-    level 0 overlaps the next call's coarse levels."""
-    monkeypatch.setenv("MDX_LK_XCALL", xcall)
+    call -- equal the oracle's."""
     seeds_a = [20141105 + i for i in range(8)]
     seeds_b = [20141205 + i for i in range(8)]
     pairs = _pairs(mdx, seeds_a + seeds_b, W, H)
@@ -170,14 +166,13 @@ def test_dataflow_fallback_is_bit_exact(mdx, oracle, monkeypatch, spin):
             _check_slot(got[j], i, refs[s], f"spin {spin} call {j} slot {i} seed {s}")
 
 
-@pytest.mark.parametrize("mode,spin,w,h,batch", [("1", None, 1920, 1080, 1), ("1", None, 640, 480, 4),
-                                                  ("2", None, 1920, 1080, 16), ("1", "-1", 640, 480, 4)])
-def test_per_point_dataflow_bit_exact(mdx, oracle, monkeypatch, mode, spin, w, h, batch):
-    """The opt-in per-point level dataflow (MDX_LK_PFLOW=1: batches the per-pair form does not take;
-    2: every batch): a group waits only for its own points' coarser-level results, stamped with the
-    call's epoch.  Two calls back to back (epochs 1 and 2, flags not cleared in between), pipelined;
-    with MDX_LK_SPIN_MAX=-1 every wait gives up and the levels are recomputed.  Bit-exact."""
-    monkeypatch.setenv("MDX_LK_PFLOW", mode)
+@pytest.mark.parametrize("spin,w,h,batch", [(None, 1920, 1080, 1), (None, 640, 480, 4), (None, 1920, 1080, 16),
+                                             ("-1", 640, 480, 4)])
+def test_small_batches_pipelined_back_to_back(mdx, oracle, monkeypatch, spin, w, h, batch):
+    """Two pipelined calls back to back at small batches: 1 and 4 pairs, which the level dataflow
+    does not take (it needs a multiple of 8 and at least 16 -- their levels run in sequence, so no
+    hand-off can give up: the fallback counts stay 0), and 16, the smallest it does.  Also 4 pairs
+    with MDX_LK_SPIN_MAX=-1, which must change nothing where no dataflow runs.  Bit-exact."""
     if spin:
         monkeypatch.setenv("MDX_LK_SPIN_MAX", spin)
     seeds = [31000 + i for i in range(min(batch, 4))]
@@ -201,11 +196,52 @@ def test_per_point_dataflow_bit_exact(mdx, oracle, monkeypatch, mode, spin, w, h
                 c.dev_free(p)
         c.dev_free(d1)
         c.dev_free(d2)
-    if spin:
-        assert fb["levels_recomputed"] > 0
+    if not spin and batch < 16:
+        assert fb == {"group_giveups": 0, "gate_giveups": 0, "levels_recomputed": 0}
     for j in range(2):
         for i, sd in enumerate(slots):
-            _check_slot(got[j], i, refs[sd], f"pflow {mode} call {j} slot {i}")
+            _check_slot(got[j], i, refs[sd], f"{w}x{h} x{batch} spin {spin} call {j} slot {i}")
+
+
+def test_smaller_batch_behind_larger_pipelined(mdx, oracle):
+    """A pipelined call of 8 pairs right behind one of 32 on the same context and frame size, one
+    sync at the end.  The LK scratch is laid out by batch ([level][pair][point] A sums, the queue
+    heads behind them), so the second call's aux-stream writes of one level fall into regions the
+    first call's other levels still read -- with 8 pairs its level 1..3 A sums cover the first
+    call's level-0 sums of pairs 8..31, and they wait only for the first call's levels 1..3: the
+    layout change must let the first call finish first.  Every slot of both calls against the
+    oracle, bit for bit."""
+    w, h, b1, b2 = W, H, B, 8
+    seeds = [32000 + i for i in range(8)]
+    pairs = _pairs(mdx, seeds, w, h)
+    refs = _oracle_refs(oracle, pairs)
+    slots = [[seeds[i % 8] for i in range(b1)], [seeds[(3 * i + 5) % 8] for i in range(b2)]]
+    n = mdx.grid_count(w, h, PS)
+    with mdx.Context(0, w, h, b1, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c:
+        ins, outs = [], []
+        for b, sl in zip((b1, b2), slots):
+            g1, g2 = _stack(pairs, sl)
+            d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
+            c.h2d(d1, g1)
+            c.h2d(d2, g2)
+            ins.append((d1, d2))
+            outs.append(_alloc_out(c, n, w, h, b, vectors=True))
+        # a warm-up call at the larger batch, so that the checked calls find every buffer allocated
+        _call(c, b1, *ins[0], outs[0], w, h)
+        c.sync()
+        _call(c, b1, *ins[0], outs[0], w, h)
+        _call(c, b2, *ins[1], outs[1], w, h)
+        c.sync()
+        got = [_read_out(c, o, n, w, h, b) for o, b in zip(outs, (b1, b2))]
+        for o in outs:
+            for p in o.values():
+                c.dev_free(p)
+        for d1, d2 in ins:
+            c.dev_free(d1)
+            c.dev_free(d2)
+    for j, sl in enumerate(slots):
+        for i, s in enumerate(sl):
+            _check_slot(got[j], i, refs[s], f"call {j} slot {i} seed {s}")
 
 
 def test_default_run_fallbacks_are_recovered(mdx, monkeypatch):

@@ -206,6 +206,53 @@ def test_batch_dev_matches_host_path(mdx, oracle, monkeypatch, B, env, wh):
         np.testing.assert_array_equal(out["H"][i], ref["H"])
 
 
+@pytest.mark.parametrize("h,ps,env,nlev", [(72, 3, {}, 1), (72, 3, {"MDX_LK_SUB": "1"}, 1), (72, 10, {}, 1),
+                                            (88, 3, {}, 2)])
+def test_both_a_sum_kernels(mdx, oracle, monkeypatch, h, ps, env, nlev):
+    """The two gradient-sum kernels, chosen by the plan alone.  A 96x72 frame has one pyramid level
+    (its half, 48x36, is not above the 40-px window, where buildOpticalFlowPyramid stops), so level 0
+    is the whole LK.  At pixel_step 3 neighbouring grid rows' windows start 3 plane rows apart,
+    below the 5 the row-strip kernel needs: k_lk_A (static groups), over two pairs in one launch and
+    in sub-batches of one.  At pixel_step 10 they start 10 apart: k_lk_A_rows (4 window slots).
+    96x88 has two levels (48x44); at pixel_step 3 level 1's two row classes (even and odd grid rows)
+    each have windows 3 plane rows apart as well, so k_lk_A runs both levels with two classes per
+    axis at the coarser one.  (Rows of one residue class are always evenly spaced -- consecutive
+    members lie a whole number of level pixels apart -- so the spacing below 5 is the only way the
+    plan reaches k_lk_A.)  Every output of every pair against the oracle, bit for bit."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    w, B = 96, 2
+    levels, lw, lh = 1, (w + 1) // 2, (h + 1) // 2              # buildOpticalFlowPyramid's rule, max_level 4
+    while levels <= 4 and lw > 40 and lh > 40:
+        levels, lw, lh = levels + 1, (lw + 1) // 2, (lh + 1) // 2
+    assert levels == nlev
+    pairs = [mdx.synth_pair(4100 + i, w, h, 1) for i in range(B)]
+    g1 = np.stack([p[0] for p in pairs]); g2 = np.stack([p[1] for p in pairs])
+    n = mdx.grid_count(w, h, ps)
+    with mdx.Context(0, w, h, B, pixel_step=ps, min_vector_size=1.0) as c:
+        bufs = {k: c.dev_alloc(s) for k, s in dict(i1=g1.nbytes, i2=g2.nbytes, np=B * n * 8, st=B * n,
+                                                    vec=B * n * 32, mask=B * w * h, H=B * 72, num=B * 4).items()}
+        c.h2d(bufs["i1"], g1); c.h2d(bufs["i2"], g2)
+        c.flow_warp_diff_batch_dev(B, bufs["i1"], bufs["i2"], w, h, w, w * h, mdx.FMT_GRAY8, bufs["np"], bufs["st"],
+                                   bufs["vec"], bufs["mask"], bufs["H"], 0, bufs["num"])
+        c.sync()
+        out = dict(np=np.empty((B, n, 2), np.float32), st=np.empty((B, n), np.uint8), vec=np.empty((B, n, 4)),
+                   mask=np.empty((B, h, w), np.uint8), H=np.empty((B, 3, 3)), num=np.empty(B, np.int32))
+        for k, arr in out.items():
+            c.d2h(arr, bufs[k])
+        for p in bufs.values():
+            c.dev_free(p)
+    for i in range(B):
+        ref = oracle.calculate_optical_flow(g1[i], g2[i], pixel_step=ps, min_vector_size=1.0)
+        label = f"ps {ps} {env} pair {i}"
+        assert out["num"][i] == ref["num_vectors"], label
+        np.testing.assert_array_equal(out["st"][i], ref["status"], err_msg=label)
+        np.testing.assert_array_equal(out["np"][i].view(np.uint32), ref["next_pts"].view(np.uint32), err_msg=label)
+        np.testing.assert_array_equal(out["vec"][i], ref["vectors"], err_msg=label)
+        np.testing.assert_array_equal(out["H"][i].view(np.uint64), ref["H"].view(np.uint64), err_msg=label)
+        assert int((out["mask"][i] != ref["mask"]).sum()) == 0, label
+
+
 @pytest.mark.parametrize("w,h", [(320, 240), (640, 480)])
 def test_batch_with_unfit_pair(mdx, oracle, w, h):
     """A pair with no fit (flat frames) between fitted pairs of one batch: its mask is written all
