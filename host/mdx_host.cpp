@@ -139,6 +139,40 @@ void MotionDetectionNode::run_pair(const Image& a, const Image& b, FrameResult* 
     }
     publish(kTopicFlowMarkers, flow_image(a, r->vector_image, ps, p_.min_vector_size));   // (not :83-85's arrows)
     publish(kTopicMask, mask_image(r->mask, w, h));
+    r->outlier_flags.clear();
+    r->outlier_stats = mdx_outlier_stats{};
+    r->num_clusters = 0;
+    r->cluster_labels.clear();
+    r->kept_clusters.clear();
+    r->rectangles.clear();
+    r->num_active_vectors = 0;
+    if (p_.detect_outliers && p_.distance_threshold > 0 && p_.angular_threshold > 0) {
+        // detectOutliers (node.cpp:112-160): findOutliers (:114), getOutlierVectors (:121) and getClusters
+        // (:127) on the Vec4d image's grid in its visiting order, rows outer
+        std::vector<double> grid;
+        for (int y = 0; y < h; y += ps)
+            for (int x = 0; x < w; x += ps) {
+                const double* e = &r->vector_image[((size_t)y * w + x) * 4];
+                grid.insert(grid.end(), e, e + 4);
+            }
+        const int n = (int)(grid.size() / 4), max_kept = n / 6;   // a kept cluster has more than 5 vectors
+        std::vector<double> outl(grid.size());
+        r->outlier_flags.assign(n, 0);
+        const int orc = mdx_find_outliers(ctx_, grid.data(), 1, n, p_.include_zeros ? MDX_OUTLIERS_INCLUDE_ZEROS : 0,
+                                          r->outlier_flags.data(), outl.data(), &r->outlier_stats);
+        if (orc < 0) throw std::runtime_error(std::string("mdx_find_outliers: ") + mdx_last_error(ctx_));
+        int nkept = 0;
+        r->cluster_labels.assign(n, 0);
+        r->kept_clusters.assign(max_kept, 0);
+        r->rectangles.assign((size_t)4 * max_kept, 0);
+        const int vrc = mdx_cluster_vectors(ctx_, outl.data(), n, p_.distance_threshold, p_.angular_threshold, 5,
+                                            p_.abs_int ? MDX_VCLUSTER_ABS_INT : 0, r->cluster_labels.data(),
+                                            &r->num_active_vectors, &r->num_clusters, r->kept_clusters.data(),
+                                            r->rectangles.data(), max_kept, &nkept);
+        if (vrc < 0) throw std::runtime_error(std::string("mdx_cluster_vectors: ") + mdx_last_error(ctx_));
+        r->kept_clusters.resize(nkept);
+        r->rectangles.resize((size_t)4 * nkept);
+    }
     r->num_regions_all = 0;
     r->regions.clear();
     if (p_.region_min_area <= 0) return;

@@ -68,6 +68,12 @@ struct Params {
     // 3x3 opening
     int region_min_area = 0;
     bool region_open = true;
+    // the pair path's detector (MotionDetectionNode::detectOutliers, node.cpp:112-160; off: the reference's
+    // call at :405 is commented out): with live_path false and both thresholds > 0, findOutliers ->
+    // getOutlierVectors -> getClusters on the pair's Vec4d field (mdx_find_outliers, mdx_cluster_vectors;
+    // DESIGN.md §7h).  include_zeros: findOutliers' argument
+    bool detect_outliers = false;
+    bool include_zeros = false;
 };
 
 // One processed frame's outputs (what the node hands to its publishers / logs).
@@ -84,6 +90,12 @@ struct FrameResult {
     int rc = 0;                                // MDX_OK or MDX_EDEGENERATE
     int num_regions_all = 0;                   // region_min_area > 0: every component of the (opened) mask
     std::vector<int32_t> regions;              // x, y, width, height, area, seed_x, seed_y, id of each kept one
+    // detect_outliers: the grid vectors' flags (bit 0 angle, bit 1 magnitude; image rows outer) and their
+    // statistics; the clusters of the outlier vectors fill num_clusters, cluster_labels (per grid vector,
+    // -1 for a vector that is no outlier or has no flow), kept_clusters, rectangles and
+    // num_active_vectors below, as getClusters does on the live path
+    std::vector<uint8_t> outlier_flags;
+    mdx_outlier_stats outlier_stats{};
     // live path
     std::vector<std::vector<float>> trajectories;   // complete ones, (x, y) * traj_size each
     std::vector<float> outlier_points;              // fitSubspace's outlier_points, (x, y) each

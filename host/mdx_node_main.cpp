@@ -11,6 +11,9 @@
 //            [log_contours=0]
 //            [region_min_area=0]      (pair path: label the mask into regions of at least this area; 0: off)
 //            [region_open=1]          (the 3x3 opening in front of the labelling)
+//            [detect_outliers=0]      (pair path with both thresholds > 0: flag the flow vectors' median / MAD
+//                                      outliers and cluster them by distance and angle)
+//            [include_zeros=0]        (findOutliers: vectors without flow take part in the statistics)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -30,6 +33,14 @@
 //                                 grid of the node's vector image as getClusters visits it); i32 labels[n]
 //                                 (-1: no flow); i32 kept[num_kept]; i32 rects[num_kept][4] (x, y, width,
 //                                 height); with log_contours=1 each rectangle goes to motion.log too
+//   outliers_<k>.bin              pair path with detect_outliers=1 and both thresholds > 0: i32 n (grid vectors,
+//                                 image rows outer), selected, flagged_angle, flagged_magnitude, outliers,
+//                                 num_active (outlier vectors with a flow), num_all, num_kept; f64
+//                                 median_angle, mad_angle, median_magnitude, mad_magnitude; f64
+//                                 vectors[n][4] (the grid of the node's vector image); u8 flags[n] (bit 0
+//                                 angle, bit 1 magnitude); i32 labels[n] (getClusters on the outlier vectors;
+//                                 -1: no outlier, or no flow); i32 kept[num_kept]; i32 rects[num_kept][4] (x,
+//                                 y, width, height); with log_contours=1 each rectangle goes to motion.log too
 //   regions_<k>.bin               pair path with region_min_area > 0: i32 num_all, num_kept; i32
 //                                 records[num_kept][8] (x, y, width, height, area, seed_x, seed_y, id);
 //                                 with log_contours=1 each record's rectangle goes to motion.log too
@@ -117,6 +128,8 @@ int main(int argc, char** argv)
         p.log_contours = std::atoi(get("log_contours", "0").c_str()) != 0;
         p.region_min_area = std::atoi(get("region_min_area", "0").c_str());
         p.region_open = std::atoi(get("region_open", "1").c_str()) != 0;
+        p.detect_outliers = std::atoi(get("detect_outliers", "0").c_str()) != 0;
+        p.include_zeros = std::atoi(get("include_zeros", "0").c_str()) != 0;
         const int device = std::atoi(get("device", "0").c_str());
         const std::string out = argv[2];
         const std::vector<Image> frames = read_frames(argv[1]);
@@ -131,6 +144,7 @@ int main(int argc, char** argv)
         if (p.log_contours) ml.reset(new MotionLogger(out + "/motion.log"));
         const bool clustering = p.live_path && p.egomotion && p.distance_threshold > 0;
         const bool vclustering = p.live_path && !p.egomotion && p.distance_threshold > 0 && p.angular_threshold > 0;
+        const bool outliers = !p.live_path && p.detect_outliers && p.distance_threshold > 0 && p.angular_threshold > 0;
         for (size_t fi = 0; fi < frames.size(); fi++) {
             FrameResult r;
             if (!node.image_callback(frames[fi], &r)) continue;
@@ -195,6 +209,28 @@ int main(int argc, char** argv)
                     for (size_t i = 0; i < r.regions.size() / 8; i++)
                         ml->write_bounding_box(r.regions[8 * i], r.regions[8 * i + 1], r.regions[8 * i + 2],
                                                r.regions[8 * i + 3], frame, (int)i);
+            }
+            if (outliers) {
+                const int32_t n = (int32_t)r.outlier_flags.size();
+                const mdx_outlier_stats& st = r.outlier_stats;
+                const int32_t ohdr[8] = {n, st.selected, st.flagged_angle, st.flagged_magnitude, st.outliers,
+                                         r.num_active_vectors, r.num_clusters, (int32_t)r.kept_clusters.size()};
+                const double osta[4] = {st.median_angle, st.mad_angle, st.median_magnitude, st.mad_magnitude};
+                std::vector<uint8_t> ob((const uint8_t*)ohdr, (const uint8_t*)ohdr + sizeof(ohdr));
+                auto oput = [&](const void* q, size_t len) { ob.insert(ob.end(), (const uint8_t*)q, (const uint8_t*)q + len); };
+                oput(osta, sizeof(osta));
+                for (int y = 0; y < r.h; y += p.pixel_step)
+                    for (int x = 0; x < r.w; x += p.pixel_step) oput(&r.vector_image[((size_t)y * r.w + x) * 4], 32);
+                oput(r.outlier_flags.data(), r.outlier_flags.size());
+                oput(r.cluster_labels.data(), r.cluster_labels.size() * 4);
+                oput(r.kept_clusters.data(), r.kept_clusters.size() * 4);
+                oput(r.rectangles.data(), r.rectangles.size() * 4);
+                write_bytes(out + "/outliers_" + std::to_string(k) + ".bin", ob.data(), ob.size());
+                const int frame = (int)node.global_frame_count() - 1;
+                if (ml)
+                    for (size_t i = 0; i < r.kept_clusters.size(); i++)
+                        ml->write_bounding_box(r.rectangles[4 * i], r.rectangles[4 * i + 1], r.rectangles[4 * i + 2],
+                                               r.rectangles[4 * i + 3], frame, (int)i);
             }
             write_bytes(out + "/res_" + std::to_string(k) + ".bin", buf.data(), buf.size());
             write_flow(r.vector_image, r.w, r.h, p.pixel_step, out + "/flow_" + std::to_string(k));

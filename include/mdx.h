@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 8    /* 2: mdx_params.call_pipelining, mdx_input_ready.
+#define MDX_ABI_VERSION 9    /* 2: mdx_params.call_pipelining, mdx_input_ready.
                                 3: mdx_lk_fallbacks; mdx_params grew ransac_iters, ransac_thresh and
                                    ransac_seed (16 more bytes: a caller built against ABI 2 passes a
                                    shorter struct); mdx_sync / mdx_device_sync return MDX_OK after an
@@ -36,7 +36,9 @@ extern "C" {
                                 6: mdx_cluster_euclidean (a new entry; mdx_params is unchanged, 80 bytes).
                                 7: mdx_mask_regions_dev and mdx_mask_regions (new entries; mdx_params is
                                    unchanged, 80 bytes).
-                                8: mdx_cluster_vectors (a new entry; mdx_params is unchanged, 80 bytes). */
+                                8: mdx_cluster_vectors (a new entry; mdx_params is unchanged, 80 bytes).
+                                9: mdx_find_outliers and mdx_outlier_stats (a new entry; mdx_params is
+                                   unchanged, 80 bytes). */
 
 /* Return codes */
 #define MDX_OK           0
@@ -413,6 +415,53 @@ int mdx_cluster_vectors(mdx_ctx* ctx, const double* vectors, int n, double dista
                         double angular_threshold, int min_size /* reference: 5 */, int flags, int32_t* labels,
                         int* num_active, int* num_all, int32_t* kept, int32_t* rects, int max_kept,
                         int* num_kept);
+
+/*
+ * Flow-vector outliers by median and median absolute deviation: replaces
+ * OutlierDetector::findOutliers and getOutlierVectors (common/src/outlier_detector.cpp:37-186), the
+ * pair path's detector, which the node would run on calculateOpticalFlow's Vec4d image in front of
+ * getClusters (MotionDetectionNode::detectOutliers, motion_detection_node.cpp:112-160).  Restated
+ * from the source; unpinned against a real build.
+ *   vectors [batch][n][4] double host, (x, y, dx, dy) each, one per grid point.  The statistics do not
+ *   depend on the order; pass the order getClusters visits (image rows outer) so that the flags line
+ *   up with what mdx_cluster_vectors is given next.
+ *   Selected set S: every vector under MDX_OUTLIERS_INCLUDE_ZEROS (:130-133), else the vectors with
+ *   fabs(dx) > 0 || fabs(dy) > 0 (:134).  m = |S|.
+ *   Channels (:73-95): the angle atan2(dy, dx), not wrapped (vectors pointing near +pi and -pi are far
+ *   apart: the reference's quirk, kept), by the host's libm; the magnitude sqrt(dy*dy + dx*dx), every
+ *   operation rounded, none fused.
+ *   Per channel (createMask, :120-186): the median of S's values (getMedian, :97-119: the element at
+ *   (m-1)/2 of the sorted values for odd m, (v[m/2-1] + v[m/2]) / 2.0 for even m); diff = fabs(value -
+ *   median); MAD = the same median of the diffs; a vector of S is flagged iff
+ *   fabs(0.6745 * diff / MAD) > 3.5, evaluated left to right (a rounded multiply, then an IEEE
+ *   division).  MAD = 0: a positive diff gives +inf and is flagged, a zero diff gives NaN and is not.
+ *   m == 0: nothing is flagged (:140-143).  Vectors outside S are never flagged.
+ *   A vector is an outlier iff either channel flags it.
+ * Outputs (any may be NULL):
+ *   out_flags       [batch][n] bit 0: flagged by the angle, bit 1: by the magnitude (kept apart so that
+ *                   a wrong channel cannot hide behind the other one's flag)
+ *   outlier_vectors [batch][n][4] getOutlierVectors (:55-71): the input with every non-outlier
+ *                   replaced by (0, 0, 0, 0)
+ *   stats           [batch] counts and the four order statistics; all 0 when m == 0.  std::sort leaves
+ *                   the order of -0.0 and +0.0 open, so a median that is zero is specified as a value,
+ *                   not by the sign of its zero; no flag depends on that sign.
+ * Given the host's angles every output is exact: the squares, their sum, the root, all four
+ * selections, the diffs, the z-score and the compare run on the device with explicitly rounded
+ * operations, denormals kept; one launch for the whole batch, one workgroup per field.
+ * n == 0 or batch == 0 is MDX_OK.  MDX_EINVAL: a null context; negative batch or n; n >
+ * MDX_OUTLIERS_MAX_POINTS; unknown flag bits; vectors NULL while batch * n > 0; a non-finite component;
+ * |dx| or |dy| >= 1e150 (the square must not overflow: inf - inf would put a NaN into the reference's
+ * sort, which is undefined).  Scratch belongs to the context and only grows.  Synchronous.
+ */
+typedef struct {            /* 48 bytes */
+    int32_t selected;       /* m */
+    int32_t flagged_angle, flagged_magnitude, outliers;
+    double  median_angle, mad_angle, median_magnitude, mad_magnitude;   /* 0 when m == 0 */
+} mdx_outlier_stats;
+#define MDX_OUTLIERS_INCLUDE_ZEROS 1
+#define MDX_OUTLIERS_MAX_POINTS 131072   /* the cap of mdx_cluster_vectors */
+int mdx_find_outliers(mdx_ctx* ctx, const double* vectors, int batch, int n, int flags, uint8_t* out_flags,
+                      double* outlier_vectors, mdx_outlier_stats* stats);
 
 /*
  * The motion mask labelled into regions: the pair path's mask turned into

@@ -30,6 +30,8 @@ CLUSTER_MAX_POINTS = 262144   # include/mdx.h MDX_CLUSTER_MAX_POINTS
 REGIONS_OPEN3 = 1             # include/mdx.h MDX_REGIONS_OPEN3
 VCLUSTER_ABS_INT = 1          # include/mdx.h MDX_VCLUSTER_ABS_INT
 VCLUSTER_MAX_POINTS = 131072  # include/mdx.h MDX_VCLUSTER_MAX_POINTS
+OUTLIERS_INCLUDE_ZEROS = 1    # include/mdx.h MDX_OUTLIERS_INCLUDE_ZEROS
+OUTLIERS_MAX_POINTS = 131072  # include/mdx.h MDX_OUTLIERS_MAX_POINTS
 
 # every symbol include/mdx.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -44,13 +46,14 @@ EXPORTED = [
     "mdx_host_alloc", "mdx_host_free", "mdx_probe_stream3_dev", "mdx_lk_fallbacks",
     "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
     "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions", "mdx_cluster_vectors",
+    "mdx_find_outliers",
 ]
-ABI_VERSION = 8   # include/mdx.h MDX_ABI_VERSION
+ABI_VERSION = 9  # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_internal.h", "mdx_ctx.h", "mdx_dev.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp",
            "mdx_post.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_regions.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -69,7 +72,15 @@ class MdxRegion(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("x", "y", "width", "height", "area", "seed_x", "seed_y", "id")]
 
 
+class MdxOutlierStats(C.Structure):
+    """mdx_outlier_stats (include/mdx.h): one field's counts and order statistics."""
+    _fields_ = [("selected", C.c_int32), ("flagged_angle", C.c_int32), ("flagged_magnitude", C.c_int32),
+                ("outliers", C.c_int32), ("median_angle", C.c_double), ("mad_angle", C.c_double),
+                ("median_magnitude", C.c_double), ("mad_magnitude", C.c_double)]
+
+
 BAND_CAND_BYTES = 96
+assert C.sizeof(MdxOutlierStats) == 48
 assert C.sizeof(MdxRegion) == 32
 assert C.sizeof(MdxBandCand) == BAND_CAND_BYTES
 
@@ -238,6 +249,8 @@ def lib() -> C.CDLL:
     L.mdx_cluster_vectors.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.mdx_cluster_vectors.restype = C.c_int
+    L.mdx_find_outliers.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.mdx_find_outliers.restype = C.c_int
     L.mdx_mask_regions_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp,
                                        C.c_int, vp, vp, vp, vp]
     L.mdx_mask_regions_dev.restype = C.c_int

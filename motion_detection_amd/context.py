@@ -6,7 +6,7 @@ side, raw device pointers (ints) for the zero-copy batched entry; no torch types
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -64,6 +64,11 @@ class FlowResult:
     H: np.ndarray           # (3, 3) float64 (zeros when no fit)
     code: int               # MDX_OK or MDX_EDEGENERATE
     regions: "RegionResult | None" = None   # the mask labelled into regions (the node's region_min_area)
+    # the node's detect_outliers (findOutliers -> getOutlierVectors -> getClusters on `vectors`' image):
+    outlier_flags: np.ndarray | None = None  # (npts,) uint8 per grid vector, image rows outer (mdx_find_outliers)
+    vector_clusters: list = field(default_factory=list)   # getClusters' kept clusters, (n_k, 4) float64 each
+    clusters: list = field(default_factory=list)          # their points, (n_k, 2) float32 each
+    rectangles: list = field(default_factory=list)        # their (x, y, width, height), as cv::Rect
 
 
 @dataclass
@@ -108,6 +113,19 @@ class VectorClusterResult:
     kept: np.ndarray            # (num_kept,) int32: ids of the clusters with size > min_size, ascending
     rects: np.ndarray           # (num_kept, 4) int32: x, y, width, height of each kept cluster (cv::Rect)
     num_kept: int = 0           # all kept clusters, also when max_kept cut kept / rects short
+
+
+@dataclass
+class OutlierResult:
+    """Flow-vector outliers by median / MAD (include/mdx.h mdx_find_outliers).  Shapes are
+    those of the input: (n, ...) for one field, (batch, n, ...) for a batch."""
+    flags: np.ndarray            # (..., n) uint8: bit 0 flagged by the angle, bit 1 by the magnitude
+    outlier_vectors: np.ndarray  # (..., n, 4) float64: getOutlierVectors, non-outliers zeroed
+    stats: np.ndarray            # (batch,) records of _lib.MdxOutlierStats' fields (one record for one field)
+
+    @property
+    def is_outlier(self) -> np.ndarray:
+        return self.flags != 0
 
 
 @dataclass
@@ -333,6 +351,21 @@ class Context:
                                               C.byref(nkept)))
         m = min(nkept.value, cap)
         return VectorClusterResult(labels, nact.value, nall.value, kept[:m].copy(), rects[:m].copy(), nkept.value)
+
+    # -- median / MAD outliers of the flow vectors (drop-in for OutlierDetector::findOutliers + getOutlierVectors)
+    def find_outliers(self, vectors: np.ndarray, include_zeros: bool = False) -> "OutlierResult":
+        """vectors: (n, 4) or (batch, n, 4) float64 (x, y, dx, dy); a batch is one launch."""
+        vec = np.ascontiguousarray(vectors, dtype=np.float64)
+        if vec.ndim not in (2, 3) or vec.shape[-1] != 4:
+            raise ValueError("vectors must be (n, 4) or (batch, n, 4)")
+        batch, n = (1, vec.shape[0]) if vec.ndim == 2 else vec.shape[:2]
+        flags = np.zeros(vec.shape[:-1], np.uint8)
+        out = np.zeros(vec.shape, np.float64)
+        stats = np.zeros(batch, np.dtype(_lib.MdxOutlierStats))
+        self._check(lib().mdx_find_outliers(self._h, _ptr(vec), batch, n,
+                                            _lib.OUTLIERS_INCLUDE_ZEROS if include_zeros else 0, _ptr(flags),
+                                            _ptr(out), _ptr(stats)))
+        return OutlierResult(flags, out, stats)
 
     # -- the motion mask labelled into regions (getMotionContours' recipe: opening, 8-connected blobs, boundingRect)
     def mask_regions(self, mask: np.ndarray, open3: bool = True, min_area: int = 1, max_regions: int | None = None,

@@ -87,6 +87,7 @@ static LkTuning read_tuning()
     t.traj_ppw = ppw == 1 ? 1 : ppw == 2 ? 2 : 4;
     t.lk_aux = num("MDX_LK_AUX", 1) != 0;
     t.lk_flow = num("MDX_LK_FLOW", 1) != 0;
+    t.ol_reg = num("MDX_OL_REG", 1) != 0;
     t.lk_cap = std::min(std::max(num("MDX_LK_CAP", 75), 10), 100);
     t.spin_max = num("MDX_LK_SPIN_MAX", kLkSpinDefault);
     return t;

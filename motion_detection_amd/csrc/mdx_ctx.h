@@ -57,6 +57,7 @@ struct LkTuning {
     // 70 / 80 / 85 within 1%, 75 best and steadiest, 95 -1.2%)
     int lk_cap = 75;
     int spin_max = mdx::kLkSpinDefault;   // MDX_LK_SPIN_MAX (debug: < 0 injects timeouts)
+    bool ol_reg = true;       // MDX_OL_REG=0: findOutliers re-reads its values on every pass at every size
 };
 
 struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
@@ -114,6 +115,9 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     std::vector<double> vc_host;             // its staging of the active vectors' planes: only ever grows
     std::vector<float> vc_pts;               // the active vectors' (x, y) as float, for the rectangles
     std::vector<int32_t> vc_idx;             // active vector -> input index, then the compact labels
+    DevBuf olin, olmag, olout;               // findOutliers: (dx, dy) planes + angles, magnitudes, stats + flags
+    std::vector<double> ol_host;             // its staging of the planes: only ever grows
+    std::vector<uint8_t> ol_flags;           // the flags when the caller takes only the vectors
     DevBuf rgscr;                            // mdx_mask_regions_dev: labels, block counts, component records
     DevBuf rgin, rgout;                      // mdx_mask_regions (host entry): the mask, every output
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)

@@ -1,5 +1,5 @@
 // mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
-// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_regions.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
 // mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
@@ -240,6 +240,14 @@ hipError_t launch_cluster(hipStream_t s, const float* pts, int N, uint32_t slim,
 size_t vcluster_rows_bytes(int nA);
 hipError_t launch_vcluster(hipStream_t s, const double* xyt, int nA, double slim, double athr, int abs_int,
                            uint32_t* rows, uint32_t* qscan, uint32_t* cand, int32_t* root);
+// Flow-vector outliers by median / MAD (findOutliers, mdx_outliers.hip): one workgroup per field, one
+// launch on s.  dxy: [batch][2][n] doubles (dx plane, dy plane); ang: [batch][n] the host's atan2 (the
+// re-reading kernel overwrites the entries outside the selected set with NaN); mag: [batch][n] scratch;
+// flags: [batch][n] bit 0 angle, bit 1 magnitude; stats: [batch].  0 < n <= MDX_OUTLIERS_MAX_POINTS.
+// in_registers: fields of up to 24,576 vectors keep a channel's values in registers (ang and mag are
+// then only read); false: every pass re-reads them, as larger fields always do (MDX_OL_REG=0).
+hipError_t launch_outliers(hipStream_t s, int batch, int n, const double* dxy, double* ang, double* mag,
+                           int include_zeros, uint8_t* flags, mdx_outlier_stats* stats, bool in_registers);
 // Trajectory tracking (calculateOpticalFlowTrajectory): grid init and the per-pass point update.
 hipError_t launch_traj_init(hipStream_t s, int npts, int ny, int pixel_step, int nimg, float* cur, float* traj,
                             int* tlen, int* num, int* flag = nullptr);

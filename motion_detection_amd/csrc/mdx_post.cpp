@@ -1,6 +1,7 @@
 // mdx_post.cpp -- what follows the flow: the reference's random stream, the trajectory subspace
-// fit (OutlierDetector::fitSubspace), Euclidean clustering (FlowClusterer::clusterEuclidean) and the
-// pair path's mask labelled into regions (BackgroundSubtractor::getMotionContours' recipe).
+// fit (OutlierDetector::fitSubspace), Euclidean clustering (FlowClusterer::clusterEuclidean), flow
+// vectors clustered by distance and angle (getClusters), their median / MAD outliers (findOutliers)
+// and the pair path's mask labelled into regions (BackgroundSubtractor::getMotionContours' recipe).
 #include "mdx_ctx.h"
 
 #include <cfloat>
@@ -262,6 +263,69 @@ extern "C" int mdx_cluster_vectors(mdx_ctx* c, const double* vectors, int n, dou
     if (labels)
         for (size_t a = 0; a < N; a++) labels[idx[a]] = lab[a];
     if (num_active) *num_active = (int)N;
+    return MDX_OK;
+}
+
+// findOutliers + getOutlierVectors (outlier_detector.cpp:37-186).  The host checks
+// the input and computes each vector's angle by libm (:80), O(n); the magnitudes, the four order
+// statistics per field and every flag are the device's (mdx_outliers.hip), one launch for the batch.
+extern "C" int mdx_find_outliers(mdx_ctx* c, const double* vectors, int batch, int n, int flags, uint8_t* out_flags,
+                                 double* outlier_vectors, mdx_outlier_stats* stats)
+{
+    if (!c) return MDX_EINVAL;
+    if (batch < 0 || n < 0) return set_err(c, MDX_EINVAL, "mdx_find_outliers: negative batch or n");
+    if (n > MDX_OUTLIERS_MAX_POINTS)
+        return set_err(c, MDX_EINVAL, "mdx_find_outliers: more than %d vectors per field", MDX_OUTLIERS_MAX_POINTS);
+    if (flags & ~MDX_OUTLIERS_INCLUDE_ZEROS) return set_err(c, MDX_EINVAL, "mdx_find_outliers: unknown flag bits 0x%x", flags);
+    const size_t N = (size_t)n, total = (size_t)batch * N;
+    if (total > 0 && !vectors) return set_err(c, MDX_EINVAL, "mdx_find_outliers: vectors is NULL");
+    for (size_t i = 0; i < 4 * total; i++)
+        if (!std::isfinite(vectors[i]))
+            return set_err(c, MDX_EINVAL, "mdx_find_outliers: vector %zu has a non-finite component", i / 4);
+    for (size_t i = 0; i < total; i++)      // dx*dx must not overflow: inf - inf = NaN in the reference's sort
+        if (!(std::fabs(vectors[4 * i + 2]) < 1e150) || !(std::fabs(vectors[4 * i + 3]) < 1e150))
+            return set_err(c, MDX_EINVAL, "mdx_find_outliers: vector %zu has a flow component >= 1e150", i);
+    if (stats && batch > 0) std::memset(stats, 0, sizeof(mdx_outlier_stats) * (size_t)batch);
+    if (total == 0) return MDX_OK;
+    try {
+        if (c->ol_host.size() < 3 * total) c->ol_host.resize(3 * total);
+        if (!out_flags && outlier_vectors && c->ol_flags.size() < total) c->ol_flags.resize(total);
+    } catch (const std::bad_alloc&) {
+        return set_err(c, MDX_ENOMEM, "mdx_find_outliers: no host memory for %zu vectors", total);
+    }
+    double *hxy = c->ol_host.data(), *ha = hxy + 2 * total;
+    for (int b = 0; b < batch; b++) {
+        const double* v = vectors + 4 * (size_t)b * N;
+        double *hx = hxy + 2 * (size_t)b * N, *hy = hx + N;
+        for (size_t i = 0; i < N; i++) {
+            hx[i] = v[4 * i + 2];
+            hy[i] = v[4 * i + 3];
+            ha[(size_t)b * N + i] = std::atan2(v[4 * i + 3], v[4 * i + 2]);   // createAngleMatrix (:80)
+        }
+    }
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const size_t o_flags = (sizeof(mdx_outlier_stats) * (size_t)batch + 255) / 256 * 256;
+    const int rc = ensure_all(c, {{&c->olin, total * 24}, {&c->olmag, total * 8}, {&c->olout, o_flags + total}});
+    if (rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    double* d_in = c->olin.as<double>();
+    char* d_out = c->olout.as<char>();
+    HIP_OR_RETURN(c, hipMemcpyAsync(d_in, hxy, total * 24, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, launch_outliers(s, batch, n, d_in, d_in + 2 * total, c->olmag.as<double>(),
+                                     flags & MDX_OUTLIERS_INCLUDE_ZEROS, reinterpret_cast<uint8_t*>(d_out + o_flags),
+                                     reinterpret_cast<mdx_outlier_stats*>(d_out), c->ol_reg));
+    uint8_t* fl = out_flags ? out_flags : (outlier_vectors ? c->ol_flags.data() : nullptr);
+    if (fl) HIP_OR_RETURN(c, hipMemcpyAsync(fl, d_out + o_flags, total, hipMemcpyDeviceToHost, s));
+    if (stats)
+        HIP_OR_RETURN(c, hipMemcpyAsync(stats, d_out, sizeof(mdx_outlier_stats) * (size_t)batch, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    if (outlier_vectors)                    // getOutlierVectors (:55-71)
+        for (size_t i = 0; i < total; i++) {
+            if (fl[i])
+                std::memcpy(outlier_vectors + 4 * i, vectors + 4 * i, 32);
+            else
+                std::memset(outlier_vectors + 4 * i, 0, 32);
+        }
     return MDX_OK;
 }
 

@@ -31,7 +31,11 @@ angle; ``abs_int`` selects the reference's truncating abs); each
 produces the motion mask.  With ``region_min_area`` set, that mask is labelled into regions on the
 device (BackgroundSubtractor::getMotionContours' recipe: ``region_open`` is its 3x3 opening) and the
 FlowResult carries them as ``regions``; under ``log_contours`` each kept region's rectangle is logged
-like a cluster's.
+like a cluster's.  With ``detect_outliers`` (off by default: the reference's call at :405 is commented
+out) and both thresholds set, the pair callback also runs MotionDetectionNode::detectOutliers
+(:112-160) on the pair's Vec4d image: findOutliers (``include_zeros`` is its parameter) ->
+getOutlierVectors -> getClusters; the FlowResult then carries ``outlier_flags``, ``vector_clusters``,
+``clusters`` and ``rectangles``, and under ``log_contours`` the rectangles are logged.
 """
 from __future__ import annotations
 
@@ -107,7 +111,10 @@ class MotionDetectionNode:
                        "angular_threshold": None, "abs_int": False,
                        # the pair path's mask labelled into regions (getMotionContours' recipe):
                        # region_min_area None leaves the stage off; region_open is the 3x3 opening
-                       "region_min_area": None, "region_open": True}
+                       "region_min_area": None, "region_open": True,
+                       # the pair path's detector (detectOutliers, :112-160): off by default, the
+                       # reference's call (:405) is commented out; include_zeros is findOutliers' argument
+                       "detect_outliers": False, "include_zeros": False}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -203,6 +210,31 @@ class MotionDetectionNode:
             self.on_result(res)
         return res
 
+    def detect_outliers(self, h: int, w: int, res, thr: float, athr: float):
+        """detectOutliers (node.cpp:112-160) on the pair's Vec4d field: findOutliers, getOutlierVectors,
+        getClusters and each kept cluster's rectangle, all on the calculator's context."""
+        from .context import grid_points
+        from .flow_clusterer import FlowClusterer, bounding_rects
+        from .outlier_detector import OutlierDetector
+        ps = int(self.params["pixel_step"])
+        ctx = self.ofc.context
+        od, fc = OutlierDetector(context=ctx), FlowClusterer(context=ctx)
+        vec = np.zeros((h, w, 4))                         # cv::Mat::zeros(rows, cols, CV_32FC4) (:81)
+        pts = grid_points(w, h, ps).astype(np.int64)
+        vec[pts[:, 1], pts[:, 0], :] = res.vectors
+        prob = od.findOutliers(vec, bool(self.params.get("include_zeros", False)), ps)             # :114
+        outlier_vectors = od.getOutlierVectors(vec, prob, ps)                                      # :121
+        res.outlier_flags = od.last_outliers.flags        # per grid vector, image rows outer
+        res.vector_clusters = fc.getClusters(outlier_vectors, ps, thr, athr, bool(self.params.get("abs_int", False)))   # :127
+        res.clusters = [c[:, :2].astype(np.float32) for c in res.vector_clusters]
+        res.rectangles = bounding_rects(res.clusters)
+        if self.params.get("log_contours") and self.params.get("log_path"):
+            if self.logger is None:
+                from .formats import MotionLogger
+                self.logger = MotionLogger(self.params["log_path"])
+            for k, rect in enumerate(res.rectangles):
+                self.logger.writeBoundingBox(rect, self.global_frame_count, k)
+
     def run_optical_flow(self, image1: np.ndarray, image2: np.ndarray):
         """runOpticalFlow (node.cpp:76-92)."""
         res = self.ofc.compute(image1, image2, int(self.params["pixel_step"]), float(self.params["min_vector_size"]),
@@ -218,6 +250,9 @@ class MotionDetectionNode:
                     self.logger = MotionLogger(self.params["log_path"])
                 for k, rect in enumerate(res.regions.rectangles):
                     self.logger.writeBoundingBox(rect, self.global_frame_count, k)
+        thr, athr = self.params.get("distance_threshold"), self.params.get("angular_threshold")
+        if self.params.get("detect_outliers") and thr is not None and athr is not None:
+            self.detect_outliers(image1.shape[0], image1.shape[1], res, float(thr), float(athr))
         self.frames_processed += 1
         if self.on_result is not None:
             self.on_result(res)
