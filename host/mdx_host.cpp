@@ -120,6 +120,7 @@ void MotionDetectionNode::run_pair(const Image& a, const Image& b, FrameResult* 
 {
     const int w = (int)a.width, h = (int)a.height, ps = p_.pixel_step;
     if (b.width != a.width || b.height != a.height) throw std::invalid_argument("frame sizes differ");
+    reset_stages(r);
     const int npts = mdx_grid_count(w, h, ps), ny = (h + ps - 1) / ps;
     r->w = w;
     r->h = h;
@@ -139,53 +140,66 @@ void MotionDetectionNode::run_pair(const Image& a, const Image& b, FrameResult* 
     }
     publish(kTopicFlowMarkers, flow_image(a, r->vector_image, ps, p_.min_vector_size));   // (not :83-85's arrows)
     publish(kTopicMask, mask_image(r->mask, w, h));
-    r->outlier_flags.clear();
-    r->outlier_stats = mdx_outlier_stats{};
-    r->num_clusters = 0;
-    r->cluster_labels.clear();
-    r->kept_clusters.clear();
-    r->rectangles.clear();
-    r->num_active_vectors = 0;
-    if (p_.detect_outliers && p_.distance_threshold > 0 && p_.angular_threshold > 0) {
-        // detectOutliers (node.cpp:112-160): findOutliers (:114), getOutlierVectors (:121) and getClusters
-        // (:127) on the Vec4d image's grid in its visiting order, rows outer
-        std::vector<double> grid;
-        for (int y = 0; y < h; y += ps)
-            for (int x = 0; x < w; x += ps) {
-                const double* e = &r->vector_image[((size_t)y * w + x) * 4];
-                grid.insert(grid.end(), e, e + 4);
-            }
-        const int n = (int)(grid.size() / 4), max_kept = n / 6;   // a kept cluster has more than 5 vectors
-        std::vector<double> outl(grid.size());
-        r->outlier_flags.assign(n, 0);
-        const int orc = mdx_find_outliers(ctx_, grid.data(), 1, n, p_.include_zeros ? MDX_OUTLIERS_INCLUDE_ZEROS : 0,
-                                          r->outlier_flags.data(), outl.data(), &r->outlier_stats);
-        if (orc < 0) throw std::runtime_error(std::string("mdx_find_outliers: ") + mdx_last_error(ctx_));
-        int nkept = 0;
-        r->cluster_labels.assign(n, 0);
-        r->kept_clusters.assign(max_kept, 0);
-        r->rectangles.assign((size_t)4 * max_kept, 0);
-        const int vrc = mdx_cluster_vectors(ctx_, outl.data(), n, p_.distance_threshold, p_.angular_threshold, 5,
-                                            p_.abs_int ? MDX_VCLUSTER_ABS_INT : 0, r->cluster_labels.data(),
-                                            &r->num_active_vectors, &r->num_clusters, r->kept_clusters.data(),
-                                            r->rectangles.data(), max_kept, &nkept);
-        if (vrc < 0) throw std::runtime_error(std::string("mdx_cluster_vectors: ") + mdx_last_error(ctx_));
-        r->kept_clusters.resize(nkept);
-        r->rectangles.resize((size_t)4 * nkept);
-    }
-    r->num_regions_all = 0;
-    r->regions.clear();
-    if (p_.region_min_area <= 0) return;
+    stage_detect_outliers(r);
+    stage_regions(r);
+}
+
+// detectOutliers (node.cpp:112-160): findOutliers (:114), getOutlierVectors (:121) and getClusters (:127)
+// on the Vec4d image's grid
+void MotionDetectionNode::stage_detect_outliers(FrameResult* r)
+{
+    if (!p_.detect_outliers_on()) return;
+    r->grid = grid_vectors(r->vector_image, r->w, r->h, p_.pixel_step);
+    const int n = (int)(r->grid.size() / 4);
+    std::vector<double> outl(r->grid.size());
+    r->outlier_flags.assign(n, 0);
+    const int rc = mdx_find_outliers(ctx_, r->grid.data(), 1, n, p_.include_zeros ? MDX_OUTLIERS_INCLUDE_ZEROS : 0,
+                                     r->outlier_flags.data(), outl.data(), &r->outlier_stats);
+    if (rc < 0) throw std::runtime_error(std::string("mdx_find_outliers: ") + mdx_last_error(ctx_));
+    cluster_vectors(outl, r);
+}
+
+// the mask labelled into regions (getMotionContours' recipe, background_subtractor.cpp:31-35)
+void MotionDetectionNode::stage_regions(FrameResult* r)
+{
+    if (!p_.regions_on()) return;
+    const int w = r->w, h = r->h;
     // a kept region has at least region_min_area pixels
     static_assert(sizeof(mdx_region) == 8 * sizeof(int32_t), "mdx_region is eight int32");
     const int cap = (int)std::min<long long>((long long)w * h / p_.region_min_area, (long long)((w + 1) / 2) * ((h + 1) / 2));
     int nkept = 0;
     r->regions.assign((size_t)8 * cap, 0);
-    const int grc = mdx_mask_regions(ctx_, r->mask.data(), w, h, w, p_.region_open ? MDX_REGIONS_OPEN3 : 0,
-                                     p_.region_min_area, reinterpret_cast<mdx_region*>(r->regions.data()), cap,
-                                     &r->num_regions_all, &nkept, nullptr, nullptr);
-    if (grc < 0) throw std::runtime_error(std::string("mdx_mask_regions: ") + mdx_last_error(ctx_));
+    const int rc = mdx_mask_regions(ctx_, r->mask.data(), w, h, w, p_.region_open ? MDX_REGIONS_OPEN3 : 0,
+                                    p_.region_min_area, reinterpret_cast<mdx_region*>(r->regions.data()), cap,
+                                    &r->num_regions_all, &nkept, nullptr, nullptr);
+    if (rc < 0) throw std::runtime_error(std::string("mdx_mask_regions: ") + mdx_last_error(ctx_));
     r->regions.resize((size_t)8 * std::min(nkept, cap));
+}
+
+// One clustering entry's call and trim: the result vectors sized for n members and max_kept = n / 6 clusters (a
+// kept one has more than 5 members), entry(max_kept, &nkept) called, its error thrown under `name`, then the trim
+template <class Entry> void MotionDetectionNode::cluster_and_trim(const char* name, int n, FrameResult* r, Entry entry)
+{
+    const int max_kept = n / 6;
+    int nkept = 0;
+    r->cluster_labels.assign(n, 0);
+    r->kept_clusters.assign(max_kept, 0);
+    r->rectangles.assign((size_t)4 * max_kept, 0);
+    if (entry(max_kept, &nkept) < 0) throw std::runtime_error(std::string(name) + ": " + mdx_last_error(ctx_));
+    r->kept_clusters.resize(nkept);
+    r->rectangles.resize((size_t)4 * nkept);
+}
+
+// getClusters (flow_clusterer.cpp:178-227) on n x 4 vectors in its visiting order
+void MotionDetectionNode::cluster_vectors(const std::vector<double>& vectors, FrameResult* r)
+{
+    const int n = (int)(vectors.size() / 4);
+    cluster_and_trim("mdx_cluster_vectors", n, r, [&](int max_kept, int* nkept) {
+        return mdx_cluster_vectors(ctx_, vectors.data(), n, p_.distance_threshold, p_.angular_threshold, 5,
+                                   p_.abs_int ? MDX_VCLUSTER_ABS_INT : 0, r->cluster_labels.data(),
+                                   &r->num_active_vectors, &r->num_clusters, r->kept_clusters.data(),
+                                   r->rectangles.data(), max_kept, nkept);
+    });
 }
 
 // runOpticalFlowTrajectory (node.cpp:94-110) over the nimg ring frames already on the device, and,
@@ -195,6 +209,7 @@ void MotionDetectionNode::run_live(int nimg, FrameResult* r)
     const int w = (int)last_rgb_.width, h = (int)last_rgb_.height, ps = p_.pixel_step;
     for (const Image& m : raw_images_)
         if (m.width != last_rgb_.width || m.height != last_rgb_.height) throw std::invalid_argument("frame sizes differ");
+    reset_stages(r);
     const int npts = mdx_grid_count(w, h, ps);
     r->w = w;
     r->h = h;
@@ -215,64 +230,61 @@ void MotionDetectionNode::run_live(int nimg, FrameResult* r)
     for (int k = 0; k < npts; k++)                              // full-length ones only (:244-249)
         if (tlen[k] == nimg) r->trajectories.emplace_back(&traj[(size_t)k * nimg * 2], &traj[(size_t)(k + 1) * nimg * 2]);
     publish(kTopicFlowMarkers, flow_image(last_rgb_, r->vector_image, ps, p_.min_vector_size));   // (not :101-103's arrows)
-    r->outlier_points.clear();
-    r->subspace_columns.clear();
-    r->num_clusters = 0;
-    r->cluster_labels.clear();
-    r->kept_clusters.clear();
-    r->rectangles.clear();
-    r->num_active_vectors = 0;
     if (r->trajectories.empty()) return;                        // :296-318
-    if (!p_.egomotion) {                                        // :357-389
-        if (!(p_.distance_threshold > 0) || !(p_.angular_threshold > 0)) return;
-        // getClusters(optical_flow_vectors, pixel_step, distance_threshold, angular_threshold) (:375):
-        // the Vec4d image's grid in its visiting order, rows outer (flow_clusterer.cpp:180-184)
-        std::vector<double> grid;
-        for (int y = 0; y < h; y += ps)
-            for (int x = 0; x < w; x += ps) {
-                const double* e = &r->vector_image[((size_t)y * w + x) * 4];
-                grid.insert(grid.end(), e, e + 4);
-            }
-        const int n = (int)(grid.size() / 4), max_kept = n / 6;   // a kept cluster has more than 5 vectors
-        int nkept = 0;
-        r->cluster_labels.assign(n, 0);
-        r->kept_clusters.assign(max_kept, 0);
-        r->rectangles.assign((size_t)4 * max_kept, 0);
-        const int vrc = mdx_cluster_vectors(ctx_, grid.data(), n, p_.distance_threshold, p_.angular_threshold, 5,
-                                            p_.abs_int ? MDX_VCLUSTER_ABS_INT : 0, r->cluster_labels.data(),
-                                            &r->num_active_vectors, &r->num_clusters, r->kept_clusters.data(),
-                                            r->rectangles.data(), max_kept, &nkept);
-        if (vrc < 0) throw std::runtime_error(std::string("mdx_cluster_vectors: ") + mdx_last_error(ctx_));
-        r->kept_clusters.resize(nkept);
-        r->rectangles.resize((size_t)4 * nkept);
-        return;
-    }
+    stage_vector_clusters(r);
+    stage_subspace(nimg, r);
+    stage_point_clusters(r);
+}
+
+// without egomotion (:357-389): getClusters(optical_flow_vectors, pixel_step, distance_threshold,
+// angular_threshold) (:375) on the Vec4d image's grid
+void MotionDetectionNode::stage_vector_clusters(FrameResult* r)
+{
+    if (!p_.vector_clusters_on()) return;
+    r->grid = grid_vectors(r->vector_image, r->w, r->h, p_.pixel_step);
+    cluster_vectors(r->grid, r);
+}
+
+// fitSubspace on the complete trajectories (:341-348), one rand() stream across frames
+void MotionDetectionNode::stage_subspace(int nimg, FrameResult* r)
+{
+    if (!p_.subspace_on()) return;
     const int nt = (int)r->trajectories.size(), d = 4 * p_.num_motions;
     std::vector<float> flat((size_t)nt * nimg * 2);
     for (int i = 0; i < nt; i++) std::memcpy(&flat[(size_t)i * nimg * 2], r->trajectories[i].data(), (size_t)nimg * 8);
     std::vector<int> cols(d);
     std::vector<float> outl((size_t)nt * 2);
     int nout = 0;
-    const int frc = mdx_fit_subspace(ctx_, flat.data(), nt, nimg, p_.num_motions, p_.sigma, &rng_, cols.data(), nullptr,
-                                     nullptr, outl.data(), &nout);
-    if (frc < 0) throw std::runtime_error(std::string("mdx_fit_subspace: ") + mdx_last_error(ctx_));
+    const int rc = mdx_fit_subspace(ctx_, flat.data(), nt, nimg, p_.num_motions, p_.sigma, &rng_, cols.data(), nullptr,
+                                    nullptr, outl.data(), &nout);
+    if (rc < 0) throw std::runtime_error(std::string("mdx_fit_subspace: ") + mdx_last_error(ctx_));
     r->outlier_points.assign(outl.begin(), outl.begin() + 2 * nout);
     for (int c : cols)
         if (c >= 0) r->subspace_columns.push_back(c);
-    if (!(p_.distance_threshold > 0)) return;
-    // clusterEuclidean(outlier_points, distance_threshold) (:355) and each kept cluster's
-    // boundingRect (optical_flow_visualizer.cpp:230-236); a kept cluster has more than 5 points
-    const int max_kept = nout / 6;
-    int nkept = 0;
-    r->cluster_labels.assign(nout, 0);
-    r->kept_clusters.assign(max_kept, 0);
-    r->rectangles.assign((size_t)4 * max_kept, 0);
-    const int crc = mdx_cluster_euclidean(ctx_, r->outlier_points.data(), nout, p_.distance_threshold, 5,
-                                          r->cluster_labels.data(), &r->num_clusters, r->kept_clusters.data(),
-                                          r->rectangles.data(), max_kept, &nkept);
-    if (crc < 0) throw std::runtime_error(std::string("mdx_cluster_euclidean: ") + mdx_last_error(ctx_));
-    r->kept_clusters.resize(nkept);
-    r->rectangles.resize((size_t)4 * nkept);
+}
+
+// clusterEuclidean(outlier_points, distance_threshold) (:355) and each kept cluster's boundingRect
+// (optical_flow_visualizer.cpp:230-236)
+void MotionDetectionNode::stage_point_clusters(FrameResult* r)
+{
+    if (!p_.point_clusters_on()) return;
+    const int nout = (int)(r->outlier_points.size() / 2);
+    cluster_and_trim("mdx_cluster_euclidean", nout, r, [&](int max_kept, int* nkept) {
+        return mdx_cluster_euclidean(ctx_, r->outlier_points.data(), nout, p_.distance_threshold, 5,
+                                     r->cluster_labels.data(), &r->num_clusters, r->kept_clusters.data(),
+                                     r->rectangles.data(), max_kept, nkept);
+    });
+}
+
+std::vector<double> grid_vectors(const std::vector<double>& vi, int w, int h, int ps)
+{
+    std::vector<double> grid;
+    for (int y = 0; y < h; y += ps)
+        for (int x = 0; x < w; x += ps) {
+            const double* e = &vi[((size_t)y * w + x) * 4];
+            grid.insert(grid.end(), e, e + 4);
+        }
+    return grid;
 }
 
 Image mask_image(const std::vector<uint8_t>& mask, int w, int h)

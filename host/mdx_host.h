@@ -74,20 +74,23 @@ struct Params {
     // DESIGN.md §7h).  include_zeros: findOutliers' argument
     bool detect_outliers = false;
     bool include_zeros = false;
+
+    // Whether each optional stage runs on a processed frame (the conditions documented above, written
+    // once: the node's stages and mdx_node's output files both ask here)
+    bool both_thresholds() const { return distance_threshold > 0 && angular_threshold > 0; }
+    bool regions_on() const { return !live_path && region_min_area > 0; }
+    bool detect_outliers_on() const { return !live_path && detect_outliers && both_thresholds(); }
+    bool vector_clusters_on() const { return live_path && !egomotion && both_thresholds(); }
+    bool subspace_on() const { return live_path && egomotion; }
+    bool point_clusters_on() const { return subspace_on() && distance_threshold > 0; }
 };
 
-// One processed frame's outputs (what the node hands to its publishers / logs).
-struct FrameResult {
-    int num_vectors = 0;                       // the calculator's return value
-    int w = 0, h = 0, npts = 0;
-    std::vector<double> vector_image;          // h * w * 4: the node's optical_flow_vectors Mat, Vec4d per
-                                               // pixel, zero where no store landed (node.cpp:81 / :98)
+// What the optional stages behind the flow write.  A stage that is off or did not run leaves its fields
+// as they are here; reset_stages() puts them all back, so a field added here is reset with the rest.
+struct StageOutputs {
+    std::vector<double> grid;                  // n x 4: grid_vectors(vector_image), when a stage ran on it
+                                               // (detect_outliers, getClusters)
     // pair path
-    std::vector<float> next_pts;               // 2 * npts
-    std::vector<uint8_t> status;               // npts
-    std::vector<uint8_t> mask;                 // h * w, thresholded |warp(gray1) - gray2|
-    double H[9] = {0};
-    int rc = 0;                                // MDX_OK or MDX_EDEGENERATE
     int num_regions_all = 0;                   // region_min_area > 0: every component of the (opened) mask
     std::vector<int32_t> regions;              // x, y, width, height, area, seed_x, seed_y, id of each kept one
     // detect_outliers: the grid vectors' flags (bit 0 angle, bit 1 magnitude; image rows outer) and their
@@ -97,7 +100,6 @@ struct FrameResult {
     std::vector<uint8_t> outlier_flags;
     mdx_outlier_stats outlier_stats{};
     // live path
-    std::vector<std::vector<float>> trajectories;   // complete ones, (x, y) * traj_size each
     std::vector<float> outlier_points;              // fitSubspace's outlier_points, (x, y) each
     std::vector<int> subspace_columns;              // indices (into trajectories) of the winning sample
     // clusterEuclidean on outlier_points (:355), when egomotion and distance_threshold > 0
@@ -110,6 +112,30 @@ struct FrameResult {
     // visiting order (image rows outer), -1 for a vector without flow
     int num_active_vectors = 0;                     // grid vectors with a non-zero flow
 };
+
+// One processed frame's outputs (what the node hands to its publishers / logs).
+struct FrameResult : StageOutputs {
+    int num_vectors = 0;                       // the calculator's return value
+    int w = 0, h = 0, npts = 0;
+    std::vector<double> vector_image;          // h * w * 4: the node's optical_flow_vectors Mat, Vec4d per
+                                               // pixel, zero where no store landed (node.cpp:81 / :98)
+    // pair path
+    std::vector<float> next_pts;               // 2 * npts
+    std::vector<uint8_t> status;               // npts
+    std::vector<uint8_t> mask;                 // h * w, thresholded |warp(gray1) - gray2|
+    double H[9] = {0};
+    int rc = 0;                                // MDX_OK or MDX_EDEGENERATE
+    // live path
+    std::vector<std::vector<float>> trajectories;   // complete ones, (x, y) * traj_size each
+};
+
+// Both paths call this before any stage runs: a FrameResult reused across frames and paths never
+// carries a previous frame's stage outputs.
+inline void reset_stages(FrameResult* r) { static_cast<StageOutputs&>(*r) = StageOutputs{}; }
+
+// The Vec4d image's grid in getClusters' visiting order (flow_clusterer.cpp:180-184): rows y = 0,
+// pixel_step, .. outer, columns inner, as a flat n x 4 array.
+std::vector<double> grid_vectors(const std::vector<double>& vector_image, int w, int h, int pixel_step);
 
 using Publisher = std::function<void(const std::string& topic, const Image& msg)>;
 
@@ -131,6 +157,14 @@ public:
 private:
     void run_pair(const Image& a, const Image& b, FrameResult* r);
     void run_live(int nimg, FrameResult* r);
+    // the optional stages behind the flow; each returns at once unless its Params::*_on() holds
+    void stage_detect_outliers(FrameResult* r);
+    void stage_regions(FrameResult* r);
+    void stage_vector_clusters(FrameResult* r);
+    void stage_subspace(int nimg, FrameResult* r);
+    void stage_point_clusters(FrameResult* r);
+    void cluster_vectors(const std::vector<double>& vectors, FrameResult* r);
+    template <class Entry> void cluster_and_trim(const char* name, int n, FrameResult* r, Entry entry);
     void publish(const std::string& topic, const Image& img) const;
 
     Params p_;

@@ -95,6 +95,15 @@ static void write_bytes(const std::string& path, const void* p, size_t n)
     std::fclose(f);
 }
 
+// One output file's bytes: its i32 header, raw bytes appended, written to a path.
+struct ByteBuffer {
+    std::vector<uint8_t> bytes;
+    ByteBuffer(std::initializer_list<int32_t> header) { put(header.begin(), header.size() * 4); }
+    void put(const void* q, size_t n) { bytes.insert(bytes.end(), (const uint8_t*)q, (const uint8_t*)q + n); }
+    template <class T> void put(const std::vector<T>& v) { put(v.data(), v.size() * sizeof(T)); }
+    void write(const std::string& path) const { write_bytes(path, bytes.data(), bytes.size()); }
+};
+
 int main(int argc, char** argv)
 {
     if (argc < 3) {
@@ -110,27 +119,29 @@ int main(int argc, char** argv)
         }
         kv[std::string(argv[i], eq - argv[i])] = eq + 1;
     }
-    auto get = [&](const char* k, const char* d) { return kv.count(k) ? kv[k] : std::string(d); };
+    auto geti = [&](const char* k, int d) { return kv.count(k) ? std::atoi(kv[k].c_str()) : d; };
+    auto getd = [&](const char* k, double d) { return kv.count(k) ? std::atof(kv[k].c_str()) : d; };
+    auto getu = [&](const char* k, uint32_t d) { return kv.count(k) ? (uint32_t)std::strtoul(kv[k].c_str(), nullptr, 10) : d; };
     try {
         Params p;
-        p.pixel_step = std::atoi(get("pixel_step", "10").c_str());
-        p.min_vector_size = std::atof(get("min_vector_size", "1.0").c_str());
-        p.skip_frames = std::atoi(get("skip_frames", "1").c_str());
-        p.num_motions = std::atoi(get("num_motions", "2").c_str());
-        p.egomotion = std::atoi(get("egomotion", "1").c_str()) != 0;
-        p.live_path = std::atoi(get("live_path", "1").c_str()) != 0;
-        p.sigma = std::atof(get("sigma", "0.5").c_str());
-        p.seed = (uint32_t)std::strtoul(get("seed", "1").c_str(), nullptr, 10);
-        p.subspace_precision = std::atoi(get("subspace_precision", "0").c_str());
-        p.distance_threshold = std::atof(get("distance_threshold", "0").c_str());
-        p.angular_threshold = std::atof(get("angular_threshold", "0").c_str());
-        p.abs_int = std::atoi(get("abs_int", "0").c_str()) != 0;
-        p.log_contours = std::atoi(get("log_contours", "0").c_str()) != 0;
-        p.region_min_area = std::atoi(get("region_min_area", "0").c_str());
-        p.region_open = std::atoi(get("region_open", "1").c_str()) != 0;
-        p.detect_outliers = std::atoi(get("detect_outliers", "0").c_str()) != 0;
-        p.include_zeros = std::atoi(get("include_zeros", "0").c_str()) != 0;
-        const int device = std::atoi(get("device", "0").c_str());
+        p.pixel_step = geti("pixel_step", 10);
+        p.min_vector_size = getd("min_vector_size", 1.0);
+        p.skip_frames = geti("skip_frames", 1);
+        p.num_motions = geti("num_motions", 2);
+        p.egomotion = geti("egomotion", 1) != 0;
+        p.live_path = geti("live_path", 1) != 0;
+        p.sigma = getd("sigma", 0.5);
+        p.seed = getu("seed", 1);
+        p.subspace_precision = geti("subspace_precision", 0);
+        p.distance_threshold = getd("distance_threshold", 0);
+        p.angular_threshold = getd("angular_threshold", 0);
+        p.abs_int = geti("abs_int", 0) != 0;
+        p.log_contours = geti("log_contours", 0) != 0;
+        p.region_min_area = geti("region_min_area", 0);
+        p.region_open = geti("region_open", 1) != 0;
+        p.detect_outliers = geti("detect_outliers", 0) != 0;
+        p.include_zeros = geti("include_zeros", 0) != 0;
+        const int device = geti("device", 0);
         const std::string out = argv[2];
         const std::vector<Image> frames = read_frames(argv[1]);
         if (frames.empty()) throw std::runtime_error("no frames");
@@ -142,97 +153,75 @@ int main(int argc, char** argv)
         MotionDetectionNode node(p, device, (int)frames[0].width, (int)frames[0].height, pub);
         std::unique_ptr<MotionLogger> ml;
         if (p.log_contours) ml.reset(new MotionLogger(out + "/motion.log"));
-        const bool clustering = p.live_path && p.egomotion && p.distance_threshold > 0;
-        const bool vclustering = p.live_path && !p.egomotion && p.distance_threshold > 0 && p.angular_threshold > 0;
-        const bool outliers = !p.live_path && p.detect_outliers && p.distance_threshold > 0 && p.angular_threshold > 0;
+        // MotionLogger::writeBoundingBox of `count` rectangles (x, y, width, height at the head of every
+        // `stride` ints); the frame is the callback's global_frame_count_ (node.cpp:433), before its closing
+        // increment (:454)
+        auto log_rectangles = [&](const int32_t* rects, int stride, size_t count) {
+            if (!ml) return;
+            const int frame = (int)node.global_frame_count() - 1;
+            for (size_t i = 0; i < count; i++) {
+                const int32_t* q = rects + stride * i;
+                ml->write_bounding_box(q[0], q[1], q[2], q[3], frame, (int)i);
+            }
+        };
         for (size_t fi = 0; fi < frames.size(); fi++) {
             FrameResult r;
             if (!node.image_callback(frames[fi], &r)) continue;
+            const std::string sfx = "_" + std::to_string(k) + ".bin";
+            const int32_t num_kept = (int32_t)r.kept_clusters.size();
+            // labels, kept ids and rectangles: the tail of every cluster file, then the rectangles' log lines
+            auto put_clusters = [&](ByteBuffer& b) {
+                b.put(r.cluster_labels);
+                b.put(r.kept_clusters);
+                b.put(r.rectangles);
+                log_rectangles(r.rectangles.data(), 4, r.kept_clusters.size());
+            };
             const int traj_len = r.trajectories.empty() ? 0 : (int)r.trajectories[0].size() / 2;
-            int32_t hdr[8] = {r.num_vectors, r.rc, r.w, r.h, r.npts, (int32_t)r.trajectories.size(), traj_len,
-                              (int32_t)(r.outlier_points.size() / 2)};
-            std::vector<uint8_t> buf((uint8_t*)hdr, (uint8_t*)hdr + sizeof(hdr));
-            auto put = [&](const void* q, size_t n) { buf.insert(buf.end(), (const uint8_t*)q, (const uint8_t*)q + n); };
-            put(r.H, sizeof(r.H));
+            ByteBuffer res{r.num_vectors, r.rc, r.w, r.h, r.npts, (int32_t)r.trajectories.size(), traj_len,
+                           (int32_t)(r.outlier_points.size() / 2)};
+            res.put(r.H, sizeof(r.H));
             if (!p.live_path) {
-                put(r.next_pts.data(), r.next_pts.size() * 4);
-                put(r.status.data(), r.status.size());
-                put(r.mask.data(), r.mask.size());
+                res.put(r.next_pts);
+                res.put(r.status);
+                res.put(r.mask);
             } else {
-                for (const auto& t : r.trajectories) put(t.data(), t.size() * 4);
-                put(r.outlier_points.data(), r.outlier_points.size() * 4);
+                for (const auto& t : r.trajectories) res.put(t);
+                res.put(r.outlier_points);
                 const int32_t nc = (int32_t)r.subspace_columns.size();
-                put(&nc, 4);
-                put(r.subspace_columns.data(), r.subspace_columns.size() * 4);
+                res.put(&nc, 4);
+                res.put(r.subspace_columns);
                 write_trajectories(r.trajectories, out + "/traj_" + std::to_string(k));
             }
-            if (clustering) {
-                const int32_t chdr[2] = {r.num_clusters, (int32_t)r.kept_clusters.size()};
-                std::vector<uint8_t> cb((const uint8_t*)chdr, (const uint8_t*)chdr + sizeof(chdr));
-                auto cput = [&](const void* q, size_t n) { cb.insert(cb.end(), (const uint8_t*)q, (const uint8_t*)q + n); };
-                cput(r.cluster_labels.data(), r.cluster_labels.size() * 4);
-                cput(r.kept_clusters.data(), r.kept_clusters.size() * 4);
-                cput(r.rectangles.data(), r.rectangles.size() * 4);
-                write_bytes(out + "/clusters_" + std::to_string(k) + ".bin", cb.data(), cb.size());
-                // the callback's global_frame_count_ (node.cpp:433), before its closing increment (:454)
-                const int frame = (int)node.global_frame_count() - 1;
-                if (ml)
-                    for (size_t i = 0; i < r.kept_clusters.size(); i++)
-                        ml->write_bounding_box(r.rectangles[4 * i], r.rectangles[4 * i + 1], r.rectangles[4 * i + 2],
-                                               r.rectangles[4 * i + 3], frame, (int)i);
+            if (p.point_clusters_on()) {
+                ByteBuffer b{r.num_clusters, num_kept};
+                put_clusters(b);
+                b.write(out + "/clusters" + sfx);
             }
-            if (vclustering) {
-                const int32_t n = (int32_t)r.cluster_labels.size();
-                const int32_t vhdr[4] = {n, r.num_active_vectors, r.num_clusters, (int32_t)r.kept_clusters.size()};
-                std::vector<uint8_t> vb((const uint8_t*)vhdr, (const uint8_t*)vhdr + sizeof(vhdr));
-                auto vput = [&](const void* q, size_t len) { vb.insert(vb.end(), (const uint8_t*)q, (const uint8_t*)q + len); };
-                if (n > 0)                                      // (no trajectory survived: no grid, n = 0)
-                    for (int y = 0; y < r.h; y += p.pixel_step)
-                        for (int x = 0; x < r.w; x += p.pixel_step) vput(&r.vector_image[((size_t)y * r.w + x) * 4], 32);
-                vput(r.cluster_labels.data(), r.cluster_labels.size() * 4);
-                vput(r.kept_clusters.data(), r.kept_clusters.size() * 4);
-                vput(r.rectangles.data(), r.rectangles.size() * 4);
-                write_bytes(out + "/vclusters_" + std::to_string(k) + ".bin", vb.data(), vb.size());
-                const int frame = (int)node.global_frame_count() - 1;
-                if (ml)
-                    for (size_t i = 0; i < r.kept_clusters.size(); i++)
-                        ml->write_bounding_box(r.rectangles[4 * i], r.rectangles[4 * i + 1], r.rectangles[4 * i + 2],
-                                               r.rectangles[4 * i + 3], frame, (int)i);
+            if (p.vector_clusters_on()) {
+                // (no trajectory survived: the stage did not run, no grid, n = 0)
+                ByteBuffer b{(int32_t)r.cluster_labels.size(), r.num_active_vectors, r.num_clusters, num_kept};
+                b.put(r.grid);
+                put_clusters(b);
+                b.write(out + "/vclusters" + sfx);
             }
-            if (!p.live_path && p.region_min_area > 0) {
-                const int32_t ghdr[2] = {r.num_regions_all, (int32_t)(r.regions.size() / 8)};
-                std::vector<uint8_t> gb((const uint8_t*)ghdr, (const uint8_t*)ghdr + sizeof(ghdr));
-                gb.insert(gb.end(), (const uint8_t*)r.regions.data(), (const uint8_t*)(r.regions.data() + r.regions.size()));
-                write_bytes(out + "/regions_" + std::to_string(k) + ".bin", gb.data(), gb.size());
-                const int frame = (int)node.global_frame_count() - 1;
-                if (ml)
-                    for (size_t i = 0; i < r.regions.size() / 8; i++)
-                        ml->write_bounding_box(r.regions[8 * i], r.regions[8 * i + 1], r.regions[8 * i + 2],
-                                               r.regions[8 * i + 3], frame, (int)i);
+            if (p.regions_on()) {
+                ByteBuffer b{r.num_regions_all, (int32_t)(r.regions.size() / 8)};
+                b.put(r.regions);
+                b.write(out + "/regions" + sfx);
+                log_rectangles(r.regions.data(), 8, r.regions.size() / 8);
             }
-            if (outliers) {
-                const int32_t n = (int32_t)r.outlier_flags.size();
+            if (p.detect_outliers_on()) {
                 const mdx_outlier_stats& st = r.outlier_stats;
-                const int32_t ohdr[8] = {n, st.selected, st.flagged_angle, st.flagged_magnitude, st.outliers,
-                                         r.num_active_vectors, r.num_clusters, (int32_t)r.kept_clusters.size()};
                 const double osta[4] = {st.median_angle, st.mad_angle, st.median_magnitude, st.mad_magnitude};
-                std::vector<uint8_t> ob((const uint8_t*)ohdr, (const uint8_t*)ohdr + sizeof(ohdr));
-                auto oput = [&](const void* q, size_t len) { ob.insert(ob.end(), (const uint8_t*)q, (const uint8_t*)q + len); };
-                oput(osta, sizeof(osta));
-                for (int y = 0; y < r.h; y += p.pixel_step)
-                    for (int x = 0; x < r.w; x += p.pixel_step) oput(&r.vector_image[((size_t)y * r.w + x) * 4], 32);
-                oput(r.outlier_flags.data(), r.outlier_flags.size());
-                oput(r.cluster_labels.data(), r.cluster_labels.size() * 4);
-                oput(r.kept_clusters.data(), r.kept_clusters.size() * 4);
-                oput(r.rectangles.data(), r.rectangles.size() * 4);
-                write_bytes(out + "/outliers_" + std::to_string(k) + ".bin", ob.data(), ob.size());
-                const int frame = (int)node.global_frame_count() - 1;
-                if (ml)
-                    for (size_t i = 0; i < r.kept_clusters.size(); i++)
-                        ml->write_bounding_box(r.rectangles[4 * i], r.rectangles[4 * i + 1], r.rectangles[4 * i + 2],
-                                               r.rectangles[4 * i + 3], frame, (int)i);
+                ByteBuffer b{(int32_t)r.outlier_flags.size(), st.selected, st.flagged_angle, st.flagged_magnitude,
+                             st.outliers, r.num_active_vectors, r.num_clusters, num_kept};
+                b.put(osta, sizeof(osta));
+                b.put(r.grid);
+                b.put(r.outlier_flags);
+                put_clusters(b);
+                b.write(out + "/outliers" + sfx);
             }
-            write_bytes(out + "/res_" + std::to_string(k) + ".bin", buf.data(), buf.size());
+            res.write(out + "/res" + sfx);
             write_flow(r.vector_image, r.w, r.h, p.pixel_step, out + "/flow_" + std::to_string(k));
             std::printf("frame %zu -> processed %d: num_vectors %d%s\n", fi, k, r.num_vectors,
                         p.live_path ? (", trajectories " + std::to_string(r.trajectories.size()) + ", outliers " +

@@ -18,6 +18,23 @@ def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _v(p: int):
+    """A device pointer given as an int (0: none) for a C-ABI argument."""
+    return C.c_void_p(p) if p else None
+
+
+def _cluster_buffers(n: int, min_size: int, max_kept: int | None = None):
+    """Outputs of a clustering entry for n members: cap (max_kept, default every cluster that can be
+    kept: one has more than min_size members), labels, kept ids and rectangles."""
+    cap = n // (max(int(min_size), 0) + 1) if max_kept is None else int(max_kept)
+    return cap, np.zeros(n, np.int32), np.zeros(max(cap, 0), np.int32), np.zeros((max(cap, 0), 4), np.int32)
+
+
+def _trim_kept(nkept: int, cap: int, kept: np.ndarray, rects: np.ndarray):
+    m = min(nkept, cap)
+    return kept[:m].copy(), rects[:m].copy()
+
+
 def _frame_view(img) -> np.ndarray:
     """A uint8 frame as the C-ABI reads it.  A row-pitched view (pixels and channels adjacent, a
     positive row stride of at least one row's bytes, e.g. a crop of a larger image) is kept as it is
@@ -321,17 +338,12 @@ class Context:
         """max_kept (default: every kept cluster) caps how many kept ids / rectangles are returned."""
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
         n = pts.shape[0]
-        # a kept cluster has more than min_size points
-        cap = n // (max(int(min_size), 0) + 1) if max_kept is None else int(max_kept)
-        labels = np.zeros(n, np.int32)
-        kept = np.zeros(max(cap, 0), np.int32)
-        rects = np.zeros((max(cap, 0), 4), np.int32)
+        cap, labels, kept, rects = _cluster_buffers(n, min_size, max_kept)
         nall, nkept = C.c_int(0), C.c_int(0)
         self._check(lib().mdx_cluster_euclidean(self._h, _ptr(pts), n, float(distance_threshold), int(min_size),
                                                 _ptr(labels), C.byref(nall), _ptr(kept), _ptr(rects), cap,
                                                 C.byref(nkept)))
-        m = min(nkept.value, cap)
-        return ClusterResult(labels, nall.value, kept[:m].copy(), rects[:m].copy(), nkept.value)
+        return ClusterResult(labels, nall.value, *_trim_kept(nkept.value, cap, kept, rects), nkept.value)
 
     # -- first-fit clustering by distance and angle (drop-in for FlowClusterer::getClusters + boundingRect)
     def cluster_vectors(self, vectors: np.ndarray, distance_threshold: float, angular_threshold: float,
@@ -340,17 +352,13 @@ class Context:
         abs_int: MDX_VCLUSTER_ABS_INT, the angular distance truncated as the reference's int abs does."""
         vec = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, 4)
         n = vec.shape[0]
-        cap = n // (max(int(min_size), 0) + 1)        # a kept cluster has more than min_size vectors
-        labels = np.zeros(n, np.int32)
-        kept = np.zeros(cap, np.int32)
-        rects = np.zeros((cap, 4), np.int32)
+        cap, labels, kept, rects = _cluster_buffers(n, min_size)
         nact, nall, nkept = C.c_int(0), C.c_int(0), C.c_int(0)
         self._check(lib().mdx_cluster_vectors(self._h, _ptr(vec), n, float(distance_threshold), float(angular_threshold),
                                               int(min_size), _lib.VCLUSTER_ABS_INT if abs_int else 0, _ptr(labels),
                                               C.byref(nact), C.byref(nall), _ptr(kept), _ptr(rects), cap,
                                               C.byref(nkept)))
-        m = min(nkept.value, cap)
-        return VectorClusterResult(labels, nact.value, nall.value, kept[:m].copy(), rects[:m].copy(), nkept.value)
+        return VectorClusterResult(labels, nact.value, nall.value, *_trim_kept(nkept.value, cap, kept, rects), nkept.value)
 
     # -- median / MAD outliers of the flow vectors (drop-in for OutlierDetector::findOutliers + getOutlierVectors)
     def find_outliers(self, vectors: np.ndarray, include_zeros: bool = False) -> "OutlierResult":
@@ -394,20 +402,18 @@ class Context:
                          open3: bool = True, min_area: int = 1, d_regions: int = 0, max_regions: int = 0,
                          d_num_all: int = 0, d_num_kept: int = 0, d_labels: int = 0, d_mask_out: int = 0) -> int:
         """Asynchronous on the context stream (include/mdx.h mdx_mask_regions_dev); pointers are ints."""
-        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
         return self._check(lib().mdx_mask_regions_dev(
-            self._h, batch, v(d_mask), w, h, stride, frame_stride, _lib.REGIONS_OPEN3 if open3 else 0, int(min_area),
-            v(d_regions), max_regions, v(d_num_all), v(d_num_kept), v(d_labels), v(d_mask_out)))
+            self._h, batch, _v(d_mask), w, h, stride, frame_stride, _lib.REGIONS_OPEN3 if open3 else 0, int(min_area),
+            _v(d_regions), max_regions, _v(d_num_all), _v(d_num_kept), _v(d_labels), _v(d_mask_out)))
 
     # -- device entries (pointers are ints, e.g. torch.Tensor.data_ptr())
     def flow_warp_diff_batch_dev(self, batch: int, d_img1: int, d_img2: int, w: int, h: int, stride: int,
                                  frame_stride: int, fmt: int = _lib.FMT_GRAY8, d_next_pts: int = 0, d_status: int = 0,
                                  d_vectors: int = 0, d_mask: int = 0, d_H: int = 0, d_H_external: int = 0,
                                  d_num_vectors: int = 0) -> int:
-        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
         return self._check(lib().mdx_flow_warp_diff_batch_dev(
-            self._h, batch, v(d_img1), v(d_img2), w, h, stride, frame_stride, fmt, v(d_next_pts), v(d_status),
-            v(d_vectors), v(d_mask), v(d_H), v(d_H_external), v(d_num_vectors)))
+            self._h, batch, _v(d_img1), _v(d_img2), w, h, stride, frame_stride, fmt, _v(d_next_pts), _v(d_status),
+            _v(d_vectors), _v(d_mask), _v(d_H), _v(d_H_external), _v(d_num_vectors)))
 
     def warp_diff_dev(self, batch: int, d_gray1: int, d_gray2: int, w: int, h: int, stride: int, frame_stride: int,
                       d_H: int, d_mask: int) -> int:
@@ -431,15 +437,13 @@ class Context:
     # -- row-tiled path (one pair split by rows over ranks; include/mdx.h mdx_band_*)
     def band_flow_dev(self, d_img1: int, d_img2: int, w: int, h: int, stride: int, fmt: int, y0: int, y1: int,
                       d_next_pts: int, d_status: int, d_cand: int, d_vectors: int = 0) -> int:
-        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
-        return self._check(lib().mdx_band_flow_dev(self._h, v(d_img1), v(d_img2), w, h, stride, fmt, y0, y1,
-                                                   v(d_next_pts), v(d_status), v(d_vectors), v(d_cand)))
+        return self._check(lib().mdx_band_flow_dev(self._h, _v(d_img1), _v(d_img2), w, h, stride, fmt, y0, y1,
+                                                   _v(d_next_pts), _v(d_status), _v(d_vectors), _v(d_cand)))
 
     def band_fit_warp_dev(self, nrec: int, d_cands: int, y0: int, y1: int, d_mask_band: int, d_H: int = 0,
                           d_num_vectors: int = 0) -> int:
-        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
-        return self._check(lib().mdx_band_fit_warp_dev(self._h, nrec, v(d_cands), y0, y1, v(d_mask_band), v(d_H),
-                                                       v(d_num_vectors)))
+        return self._check(lib().mdx_band_fit_warp_dev(self._h, nrec, _v(d_cands), y0, y1, _v(d_mask_band), _v(d_H),
+                                                       _v(d_num_vectors)))
 
     def input_ready(self, hip_event: int):
         """The next device-entry call waits for this hipEvent_t (an int handle) before reading its

@@ -46,7 +46,11 @@ from typing import Callable
 import numpy as np
 
 from . import _lib
+from .context import grid_points
+from .flow_clusterer import FlowClusterer, bounding_rects
+from .formats import MotionLogger
 from .optical_flow_calculator import OpticalFlowCalculator
+from .outlier_detector import OutlierDetector
 
 ENCODINGS = {"mono8": (1, _lib.FMT_GRAY8), "rgb8": (3, _lib.FMT_RGB8), "bgr8": (3, _lib.FMT_BGR8)}
 
@@ -123,10 +127,39 @@ class MotionDetectionNode:
         self.image_received = False
         self.frames_processed = 0
         self.ofc = OpticalFlowCalculator(device=device)
-        self.od = None                                    # OutlierDetector, created on first use
-        self.fc = None                                    # FlowClusterer, created on first use
+        self.od = None                                    # the live path's OutlierDetector (own context, the
+        self.fc = None                                    # rand() stream) and FlowClusterer, created on first use
         self.logger = None                                # MotionLogger (log_contours with a log_path)
+        self._pair_tools = None                           # detect_outliers' (context, detector, clusterer)
         self._device = device
+
+    def _detector(self):
+        if self.od is None:
+            self.od = OutlierDetector(seed=self.params.get("seed"), device=self._device)
+        return self.od
+
+    def _clusterer(self):
+        if self.fc is None:
+            self.fc = FlowClusterer(device=self._device)
+        return self.fc
+
+    def _pair_detector_and_clusterer(self):
+        # on the calculator's context, kept across frames (made again only when the calculator has replaced
+        # its context); not the live path's od / fc, which own contexts and, od, the live rand() stream
+        ctx = self.ofc.context
+        if self._pair_tools is None or self._pair_tools[0] is not ctx:
+            self._pair_tools = (ctx, OutlierDetector(context=ctx), FlowClusterer(context=ctx))
+        return self._pair_tools[1:]
+
+    def _log_rectangles(self, rects):
+        """MotionLogger::writeBoundingBox of each rectangle (node.cpp:431-434) when log_contours and a
+        log_path are set; the logger is created by the first stage that logs, rectangles or not."""
+        if not (self.params.get("log_contours") and self.params.get("log_path")):
+            return
+        if self.logger is None:
+            self.logger = MotionLogger(self.params["log_path"])
+        for k, rect in enumerate(rects):
+            self.logger.writeBoundingBox(rect, self.global_frame_count, k)
 
     @property
     def trajectory_size(self) -> int:
@@ -158,53 +191,31 @@ class MotionDetectionNode:
         return out
 
     def run_live_chain(self, images: list):
-        """runOpticalFlowTrajectory (node.cpp:94-110) then, with egomotion, fitSubspace (:341-348)."""
+        """runOpticalFlowTrajectory (node.cpp:94-110), then fitSubspace (:341-348, egomotion), then one
+        of the two clustering stages, then the kept clusters' rectangles and their log lines."""
         h, w = images[0].shape[:2]
         vec = np.zeros((h, w, 4))                         # cv::Mat::zeros(rows, cols, CV_32FC4) (:97)
         trajectories: list = []
         num = self.ofc.calculateOpticalFlowTrajectory(images, vec, trajectories, int(self.params["pixel_step"]),
                                                       None, float(self.params["min_vector_size"]))
-        outliers: list = []
-        subspace: list = []
-        if trajectories and self.params["egomotion"]:
-            if self.od is None:
-                from .outlier_detector import OutlierDetector
-                self.od = OutlierDetector(seed=self.params.get("seed"), device=self._device)
-            subspace = self.od.fitSubspace(trajectories, outliers, int(self.params["num_motions"]),
-                                           float(self.params["sigma"]))
-        clusters: list = []
-        rectangles: list = []
-        thr = self.params.get("distance_threshold")
-        if trajectories and self.params["egomotion"] and thr is not None:
-            from .flow_clusterer import FlowClusterer, bounding_rects
-            if self.fc is None:
-                self.fc = FlowClusterer(device=self._device)
-            clusters = self.fc.clusterEuclidean(np.asarray(outliers, np.float32).reshape(-1, 2), float(thr))   # :355
-            rectangles = bounding_rects(clusters)
-            if self.params.get("log_contours") and self.params.get("log_path"):           # :431-434
-                if self.logger is None:
-                    from .formats import MotionLogger
-                    self.logger = MotionLogger(self.params["log_path"])
-                for k, rect in enumerate(rectangles):
-                    self.logger.writeBoundingBox(rect, self.global_frame_count, k)
-        vector_clusters: list = []
-        athr = self.params.get("angular_threshold")
-        if trajectories and not self.params["egomotion"] and thr is not None and athr is not None:
-            from .flow_clusterer import FlowClusterer, bounding_rects
-            if self.fc is None:
-                self.fc = FlowClusterer(device=self._device)
-            vector_clusters = self.fc.getClusters(vec, int(self.params["pixel_step"]), float(thr), float(athr),
-                                                  bool(self.params.get("abs_int", False)))          # :375
+        ego = bool(self.params["egomotion"])
+        thr, athr = self.params.get("distance_threshold"), self.params.get("angular_threshold")
+        outliers, subspace, vector_clusters, rectangles = [], [], [], []
+        if trajectories and ego:                                                                      # :341-348
+            subspace = self._detector().fitSubspace(trajectories, outliers, int(self.params["num_motions"]),
+                                                    float(self.params["sigma"]))
+        clusters = None                                   # None: no clustering stage ran
+        if trajectories and ego and thr is not None:
+            clusters = self._clusterer().clusterEuclidean(np.asarray(outliers, np.float32).reshape(-1, 2), float(thr))   # :355
+        elif trajectories and not ego and thr is not None and athr is not None:
+            vector_clusters = self._clusterer().getClusters(vec, int(self.params["pixel_step"]), float(thr), float(athr),
+                                                            bool(self.params.get("abs_int", False)))   # :375
             clusters = [c[:, :2].astype(np.float32) for c in vector_clusters]                         # :376-386
+        if clusters is not None:
             rectangles = bounding_rects(clusters)                                                     # :395
-            if self.params.get("log_contours") and self.params.get("log_path"):                       # :431-434
-                if self.logger is None:
-                    from .formats import MotionLogger
-                    self.logger = MotionLogger(self.params["log_path"])
-                for k, rect in enumerate(rectangles):
-                    self.logger.writeBoundingBox(rect, self.global_frame_count, k)
+            self._log_rectangles(rectangles)                                                          # :431-434
         self.frames_processed += 1
-        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters, rectangles, self.global_frame_count,
+        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters or [], rectangles, self.global_frame_count,
                          vector_clusters)
         if self.on_result is not None:
             self.on_result(res)
@@ -213,12 +224,8 @@ class MotionDetectionNode:
     def detect_outliers(self, h: int, w: int, res, thr: float, athr: float):
         """detectOutliers (node.cpp:112-160) on the pair's Vec4d field: findOutliers, getOutlierVectors,
         getClusters and each kept cluster's rectangle, all on the calculator's context."""
-        from .context import grid_points
-        from .flow_clusterer import FlowClusterer, bounding_rects
-        from .outlier_detector import OutlierDetector
         ps = int(self.params["pixel_step"])
-        ctx = self.ofc.context
-        od, fc = OutlierDetector(context=ctx), FlowClusterer(context=ctx)
+        od, fc = self._pair_detector_and_clusterer()
         vec = np.zeros((h, w, 4))                         # cv::Mat::zeros(rows, cols, CV_32FC4) (:81)
         pts = grid_points(w, h, ps).astype(np.int64)
         vec[pts[:, 1], pts[:, 0], :] = res.vectors
@@ -228,12 +235,7 @@ class MotionDetectionNode:
         res.vector_clusters = fc.getClusters(outlier_vectors, ps, thr, athr, bool(self.params.get("abs_int", False)))   # :127
         res.clusters = [c[:, :2].astype(np.float32) for c in res.vector_clusters]
         res.rectangles = bounding_rects(res.clusters)
-        if self.params.get("log_contours") and self.params.get("log_path"):
-            if self.logger is None:
-                from .formats import MotionLogger
-                self.logger = MotionLogger(self.params["log_path"])
-            for k, rect in enumerate(res.rectangles):
-                self.logger.writeBoundingBox(rect, self.global_frame_count, k)
+        self._log_rectangles(res.rectangles)
 
     def run_optical_flow(self, image1: np.ndarray, image2: np.ndarray):
         """runOpticalFlow (node.cpp:76-92)."""
@@ -244,12 +246,7 @@ class MotionDetectionNode:
             # the mask is labelled on the device; what comes back is the records
             res.regions = self.ofc.context.mask_regions(res.mask, open3=bool(self.params.get("region_open", True)),
                                                         min_area=int(min_area))
-            if self.params.get("log_contours") and self.params.get("log_path"):
-                if self.logger is None:
-                    from .formats import MotionLogger
-                    self.logger = MotionLogger(self.params["log_path"])
-                for k, rect in enumerate(res.regions.rectangles):
-                    self.logger.writeBoundingBox(rect, self.global_frame_count, k)
+            self._log_rectangles(res.regions.rectangles)
         thr, athr = self.params.get("distance_threshold"), self.params.get("angular_threshold")
         if self.params.get("detect_outliers") and thr is not None and athr is not None:
             self.detect_outliers(image1.shape[0], image1.shape[1], res, float(thr), float(athr))

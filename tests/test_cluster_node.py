@@ -9,28 +9,15 @@ threshold 50) was chosen on the CPU (oracle.flow_trajectory + oracle.fit_subspac
 that every processed frame has a kept cluster; the tests assert that at least one has.
 """
 import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+from node_io import log_lines, node_exe, read_clusters, read_outlier_points, rgb8, run_node  # noqa: F401 (node_exe: a fixture)
 from test_cluster import cluster_reference
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "host")
 
 W, H, PS, NM, SIGMA, SEED, THR = 160, 120, 10, 2, 0.1, 20141105, 50.0
 TS = 2 * NM + 1
-
-
-@pytest.fixture(scope="module")
-def node_exe(mdx):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    subprocess.run(["make", "-s", "-C", HOST], check=True)
-    return os.path.join(HOST, "mdx_node")
 
 
 @pytest.fixture(scope="module")
@@ -40,39 +27,10 @@ def sequence(mdx):
     return [a, b, a, b, a, c, d]
 
 
-def run_node(exe, tmp_path, seq, **params):
-    fpath = tmp_path / "frames.bin"
-    with open(fpath, "wb") as f:
-        f.write(b"MDXF" + struct.pack("<I", len(seq)))
-        for a in seq:
-            a = np.ascontiguousarray(a, np.uint8)
-            f.write(struct.pack("<4I", a.shape[0], a.shape[1], a.strides[0], 4) + b"rgb8" + a.tobytes())
-    out = tmp_path / "out"
-    out.mkdir()
-    args = [exe, str(fpath), str(out)] + [f"{k}={v}" for k, v in params.items()]
-    return subprocess.run(args, capture_output=True, text=True, timeout=120), out
-
-
-def read_outliers(path):
-    b = open(path, "rb").read()
-    ntraj, tl, nout = struct.unpack_from("<3i", b, 20)
-    return np.frombuffer(b, np.float32, nout * 2, 32 + 72 + ntraj * tl * 8).reshape(nout, 2).copy()
-
-
-def read_clusters(path, nout):
-    b = open(path, "rb").read()
-    num_all, num_kept = struct.unpack_from("<2i", b, 0)
-    assert len(b) == 8 + 4 * nout + 4 * num_kept + 16 * num_kept
-    labels = np.frombuffer(b, np.int32, nout, 8)
-    kept = np.frombuffer(b, np.int32, num_kept, 8 + 4 * nout)
-    rects = np.frombuffer(b, np.int32, 4 * num_kept, 8 + 4 * nout + 4 * num_kept).reshape(num_kept, 4)
-    return num_all, labels, kept, rects
-
-
 @pytest.mark.gpu
 def test_cpp_node_clusters_and_motion_log(node_exe, tmp_path, sequence):
     from motion_detection_amd.formats import MotionLogger
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=1, egomotion=1, num_motions=NM, sigma=SIGMA, seed=SEED,
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=1, egomotion=1, num_motions=NM, sigma=SIGMA, seed=SEED,
                       pixel_step=PS, distance_threshold=THR, log_contours=1)
     assert p.returncode == 0, p.stderr
     nproc = len(sequence) - TS + 1
@@ -80,7 +38,7 @@ def test_cpp_node_clusters_and_motion_log(node_exe, tmp_path, sequence):
     lg = MotionLogger(str(tmp_path / "py_motion.log"))
     total_kept = 0
     for k in range(nproc):
-        outl = read_outliers(out / f"res_{k}.bin")
+        outl = read_outlier_points(out / f"res_{k}.bin")
         ref = cluster_reference(outl, THR)
         num_all, labels, kept, rects = read_clusters(out / f"clusters_{k}.bin", len(outl))
         assert num_all == ref["num_all"]
@@ -99,7 +57,7 @@ def test_cpp_node_clusters_and_motion_log(node_exe, tmp_path, sequence):
 
 @pytest.mark.gpu
 def test_cpp_node_without_threshold_writes_no_cluster_files(node_exe, tmp_path, sequence):
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=1, egomotion=1, num_motions=NM, sigma=SIGMA, seed=SEED,
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=1, egomotion=1, num_motions=NM, sigma=SIGMA, seed=SEED,
                       pixel_step=PS)
     assert p.returncode == 0, p.stderr
     names = os.listdir(out)
@@ -110,11 +68,11 @@ def test_cpp_node_without_threshold_writes_no_cluster_files(node_exe, tmp_path, 
 @pytest.mark.gpu
 def test_cpp_node_log_without_kept_cluster_is_empty(node_exe, tmp_path, sequence):
     """log_contours=1 creates motion.log even when no cluster is kept (a threshold no pair passes)."""
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=1, egomotion=1, num_motions=NM, sigma=SIGMA, seed=SEED,
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=1, egomotion=1, num_motions=NM, sigma=SIGMA, seed=SEED,
                       pixel_step=PS, distance_threshold=1e-3, log_contours=1)
     assert p.returncode == 0, p.stderr
     assert (out / "motion.log").read_bytes() == b""
-    outl = read_outliers(out / "res_0.bin")
+    outl = read_outlier_points(out / "res_0.bin")
     num_all, labels, kept, rects = read_clusters(out / "clusters_0.bin", len(outl))
     assert num_all == len(outl) and len(kept) == 0 and np.array_equal(labels, np.arange(len(outl)))
 
@@ -142,8 +100,7 @@ def test_python_node_fills_clusters_and_rectangles(mdx, sequence, tmp_path):
             assert np.array_equal(g.view(np.uint32), m.view(np.uint32))
         assert np.array_equal(np.array(r.rectangles, np.int32).reshape(-1, 4), ref["rects"])
         assert r.frame_number == fi
-        for i, (x, y, w, h) in enumerate(ref["rects"].tolist()):
-            lines.append(f"{fi}, {i}, {x}, {y}, {x + w}, {y + h}\n")
+        lines.append(log_lines(fi, ref["rects"]))
         total_kept += len(r.rectangles)
     assert total_kept >= 1
     node.logger.close()

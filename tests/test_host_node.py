@@ -15,44 +15,12 @@ byte-checked against libstdc++ in test_formats.py).
 """
 import os
 import shutil
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "host")
-EXE = os.path.join(HOST, "mdx_node")
-
-
-@pytest.fixture(scope="module")
-def node_exe(mdx):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    subprocess.run(["make", "-s", "-C", HOST], check=True)
-    return EXE
-
-
-def write_frames(path, frames):
-    """frames: list of (array, encoding); the binary's MDXF stream of sensor_msgs/Image records."""
-    with open(path, "wb") as f:
-        f.write(b"MDXF" + struct.pack("<I", len(frames)))
-        for a, enc in frames:
-            a = np.ascontiguousarray(a, np.uint8)
-            h, w = a.shape[:2]
-            step = a.strides[0]
-            f.write(struct.pack("<4I", h, w, step, len(enc)) + enc.encode() + a.tobytes())
-
-
-def run_node(exe, tmp_path, frames, **params):
-    fpath = tmp_path / "frames.bin"
-    write_frames(str(fpath), frames)
-    out = tmp_path / "out"
-    out.mkdir()
-    args = [exe, str(fpath), str(out)] + [f"{k}={int(v) if isinstance(v, bool) else v}" for k, v in params.items()]
-    p = subprocess.run(args, capture_output=True, text=True, timeout=300)
-    return p, out
+from node_io import HOST, ROOT, node_exe, read_res, run_node, write_frames  # noqa: F401 (node_exe: a fixture)
 
 
 def to_rgb8(a, enc):
@@ -64,29 +32,6 @@ def to_rgb8(a, enc):
 def kept_frames(n, skip):
     """imageCallback's skip rule (:247, :454): the counter advances on every call."""
     return [i for i in range(n) if i % skip == 0]
-
-
-def read_res(path, live, npts=0, w=0, h=0):
-    b = open(path, "rb").read()
-    num, rc, w, h, npts, ntraj, tl, nout = struct.unpack_from("<8i", b, 0)
-    o = 32
-    H = np.frombuffer(b, np.float64, 9, o).reshape(3, 3)
-    o += 72
-    r = dict(num=num, rc=rc, w=w, h=h, npts=npts, H=H)
-    if not live:
-        r["next_pts"] = np.frombuffer(b, np.float32, 2 * npts, o).reshape(npts, 2)
-        o += 8 * npts
-        r["status"] = np.frombuffer(b, np.uint8, npts, o)
-        o += npts
-        r["mask"] = np.frombuffer(b, np.uint8, w * h, o).reshape(h, w)
-    else:
-        r["traj"] = np.frombuffer(b, np.float32, ntraj * tl * 2, o).reshape(ntraj, tl, 2)
-        o += ntraj * tl * 8
-        r["outliers"] = np.frombuffer(b, np.float32, nout * 2, o).reshape(nout, 2)
-        o += nout * 8
-        nc = struct.unpack_from("<i", b, o)[0]
-        r["columns"] = np.frombuffer(b, np.int32, nc, o + 4)
-    return r
 
 
 def vector_image(vectors, w, h, ps):

@@ -13,52 +13,24 @@ the vectors, which include_zeros then pulls into the statistics (MAD 0: every mo
 outlier).  The tests assert all of that on what the device reports.
 """
 import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_cluster_node import run_node
+from node_io import (ROOT, dir_bytes, log_lines, node_exe, read_outliers, read_regions, rgb8,  # noqa: F401 (node_exe: a fixture)
+                     run_node)
 from test_outliers import STAT_DOUBLES, STAT_INTS, bits, outliers_reference
 from test_vcluster import MARGIN, vcluster_reference
-from test_vcluster_node import log_lines
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "host")
 W, H = 160, 120
 # pixel_step, min_vector_size, distance_threshold, angular_threshold, include_zeros
 SETTINGS = [(4, 1.0, 8.0, 0.5, 0), (5, 3.5, 12.0, 1.0, 0), (5, 3.5, 12.0, 1.0, 1)]
 
 
 @pytest.fixture(scope="module")
-def node_exe(mdx):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    subprocess.run(["make", "-s", "-C", HOST], check=True)
-    return os.path.join(HOST, "mdx_node")
-
-
-@pytest.fixture(scope="module")
 def sequence():
     g = np.load(os.path.join(ROOT, "tests", "golden", "synth_160x120_rgb.npz"))
     return [g["img1"], g["img2"], g["img1"], g["img2"]]
-
-
-def read_outliers(path):
-    b = open(path, "rb").read()
-    n, sel, fa, fm, nout, nact, num_all, num_kept = struct.unpack_from("<8i", b, 0)
-    med = struct.unpack_from("<4d", b, 32)
-    assert len(b) == 64 + 32 * n + n + 4 * n + 4 * num_kept + 16 * num_kept
-    vec = np.frombuffer(b, np.float64, 4 * n, 64).reshape(n, 4)
-    o = 64 + 32 * n
-    flags = np.frombuffer(b, np.uint8, n, o)
-    labels = np.frombuffer(b[o + n:o + 5 * n], np.int32)
-    kept = np.frombuffer(b[o + 5 * n:o + 5 * n + 4 * num_kept], np.int32)
-    rects = np.frombuffer(b[o + 5 * n + 4 * num_kept:], np.int32).reshape(num_kept, 4)
-    stats = dict(zip(STAT_INTS + STAT_DOUBLES, (sel, fa, fm, nout) + med))
-    return vec, stats, flags, nact, num_all, labels, kept, rects
 
 
 def chain_reference(vec, include_zeros, thr, athr):
@@ -81,7 +53,7 @@ def same_stats(got, ref):
 @pytest.mark.gpu
 @pytest.mark.parametrize("ps,mvs,thr,athr,iz", SETTINGS)
 def test_cpp_node_outliers_clusters_and_motion_log(node_exe, tmp_path, sequence, ps, mvs, thr, athr, iz):
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=0, egomotion=0, pixel_step=ps, min_vector_size=mvs,
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=0, egomotion=0, pixel_step=ps, min_vector_size=mvs,
                       distance_threshold=thr, angular_threshold=athr, detect_outliers=1, include_zeros=iz, log_contours=1)
     assert p.returncode == 0, p.stderr
     nproc = len(sequence) - 1                          # a ring of 2 frames
@@ -104,17 +76,13 @@ def test_cpp_node_outliers_clusters_and_motion_log(node_exe, tmp_path, sequence,
     assert not [n for n in os.listdir(out) if n.startswith("vclusters_") or n.startswith("clusters_")]
 
 
-def dir_bytes(d):
-    return {n: open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d))}
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("params", [dict(), dict(live_path=0, egomotion=0, distance_threshold=8.0, angular_threshold=0.5,
                                                  region_min_area=4, log_contours=1)])
 def test_cpp_node_defaults_are_unchanged(node_exe, tmp_path, sequence, params):
     """Without detect_outliers the node writes what it wrote before: the same files, byte for byte, as
     with the detector switched off explicitly; include_zeros alone does nothing."""
-    seq = sequence + [sequence[0]]                     # five frames: the default live ring fills once
+    seq = rgb8(sequence + [sequence[0]])               # five frames: the default live ring fills once
     (tmp_path / "a").mkdir(), (tmp_path / "b").mkdir(), (tmp_path / "c").mkdir()
     pa, a = run_node(node_exe, tmp_path / "a", seq, **params)
     pb, b = run_node(node_exe, tmp_path / "b", seq, detect_outliers=0, include_zeros=0, **params)
@@ -128,7 +96,7 @@ def test_cpp_node_defaults_are_unchanged(node_exe, tmp_path, sequence, params):
 
 @pytest.mark.gpu
 def test_cpp_node_needs_both_thresholds(node_exe, tmp_path, sequence):
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=0, egomotion=0, distance_threshold=8.0, detect_outliers=1)
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=0, egomotion=0, distance_threshold=8.0, detect_outliers=1)
     assert p.returncode == 0, p.stderr
     assert "res_0.bin" in os.listdir(out) and not [n for n in os.listdir(out) if n.startswith("outliers_")]
 
@@ -173,3 +141,67 @@ def test_python_node_fills_outliers_and_clusters(mdx, sequence, tmp_path, ps, mv
     node.logger.close()
     assert log.read_text() == expect
     assert plain.logger is None and off.logger is None
+
+
+# every optional stage of the pair path at once: the regions and the detector, both logging.  The
+# coarser setting: its fit leaves a motion mask with regions (checked on the CPU with the oracle and
+# test_regions.regions_reference: 4 and 6 opened regions of 4 pixels and more); the dense one's mask is empty
+ALL_PS, ALL_MVS, ALL_THR, ALL_ATHR, ALL_IZ = SETTINGS[1]
+ALL_MIN_AREA = 4
+
+
+@pytest.mark.gpu
+def test_cpp_node_all_pair_stages_at_once(node_exe, tmp_path, sequence):
+    """Each stage writes the file it writes when it runs alone, and motion.log holds, per frame, the
+    regions' lines followed by the outlier clusters' lines."""
+    base = dict(live_path=0, egomotion=0, pixel_step=ALL_PS, min_vector_size=ALL_MVS, log_contours=1)
+    detector = dict(distance_threshold=ALL_THR, angular_threshold=ALL_ATHR, detect_outliers=1, include_zeros=ALL_IZ)
+    for d in ("all", "regions", "detector"):
+        (tmp_path / d).mkdir()
+    pa, both = run_node(node_exe, tmp_path / "all", rgb8(sequence), region_min_area=ALL_MIN_AREA, **base, **detector)
+    pr, regs = run_node(node_exe, tmp_path / "regions", rgb8(sequence), region_min_area=ALL_MIN_AREA, **base)
+    pd, dets = run_node(node_exe, tmp_path / "detector", rgb8(sequence), **base, **detector)
+    assert pa.returncode == 0 and pr.returncode == 0 and pd.returncode == 0, pa.stderr + pr.stderr + pd.stderr
+    nproc = len(sequence) - 1                          # a ring of 2 frames
+    assert f"processed {nproc} of {len(sequence)}" in pa.stdout
+    fa, fr, fd = dir_bytes(both), dir_bytes(regs), dir_bytes(dets)
+    expect = ""
+    for k in range(nproc):
+        assert fa[f"regions_{k}.bin"] == fr[f"regions_{k}.bin"]
+        assert fa[f"outliers_{k}.bin"] == fd[f"outliers_{k}.bin"]
+        _, records = read_regions(both / f"regions_{k}.bin")
+        rects = read_outliers(both / f"outliers_{k}.bin")[-1]
+        assert len(records) >= 1 and len(rects) >= 1   # else the order below is not checked
+        expect += log_lines(1 + k, records[:, :4]) + log_lines(1 + k, rects)   # global_frame_count_ = the frame's index
+    assert f"regions_{nproc}.bin" not in fa and f"outliers_{nproc}.bin" not in fa
+    assert fa["motion.log"].decode() == expect
+
+
+@pytest.mark.gpu
+def test_python_node_all_pair_stages_at_once(mdx, sequence, tmp_path):
+    """The same three nodes in Python: FlowResult.regions, outlier_flags and rectangles equal the
+    single-stage nodes', and the log holds the regions' lines, then the clusters', per frame."""
+    from motion_detection_amd.node import Image, MotionDetectionNode
+    base = {"pixel_step": ALL_PS, "min_vector_size": ALL_MVS, "egomotion": False, "live_chain": False,
+            "log_contours": True}
+    detector = {"distance_threshold": ALL_THR, "angular_threshold": ALL_ATHR, "detect_outliers": True,
+                "include_zeros": bool(ALL_IZ)}
+    log = tmp_path / "all.log"
+    both = MotionDetectionNode(dict(base, region_min_area=ALL_MIN_AREA, log_path=str(log), **detector))
+    regs = MotionDetectionNode(dict(base, region_min_area=ALL_MIN_AREA, log_path=str(tmp_path / "regions.log")))
+    dets = MotionDetectionNode(dict(base, log_path=str(tmp_path / "detector.log"), **detector))
+    expect = ""
+    for fi, f in enumerate(sequence):
+        r, g, d = (n.image_callback(Image.from_array(f, "rgb8")) for n in (both, regs, dets))
+        if fi == 0:
+            assert r is None and g is None and d is None
+            continue
+        assert np.array_equal(r.regions.regions, g.regions.regions)
+        assert (r.regions.num_all, r.regions.num_kept) == (g.regions.num_all, g.regions.num_kept)
+        assert r.outlier_flags.dtype == np.uint8 and np.array_equal(r.outlier_flags, d.outlier_flags)
+        assert r.rectangles == d.rectangles
+        assert len(r.regions.rectangles) >= 1 and len(r.rectangles) >= 1   # else the order below is not checked
+        expect += log_lines(fi, r.regions.rectangles) + log_lines(fi, r.rectangles)
+    for n in (both, regs, dets):
+        n.logger.close()
+    assert log.read_text() == expect

@@ -9,26 +9,14 @@ the CPU (oracle.calculate_optical_flow + the checker) so that opened regions of 
 exist; the tests assert that at least one is kept.
 """
 import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+from node_io import log_lines, node_exe, read_mask, read_regions, rgb8, run_node  # noqa: F401 (node_exe: a fixture)
 from test_regions import regions_reference
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "host")
 W, H, PS, MIN_AREA = 160, 120, 10, 50
-
-
-@pytest.fixture(scope="module")
-def node_exe(mdx):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    subprocess.run(["make", "-s", "-C", HOST], check=True)
-    return os.path.join(HOST, "mdx_node")
 
 
 @pytest.fixture(scope="module")
@@ -38,37 +26,11 @@ def sequence(mdx):
     return [np.repeat(f[:, :, None], 3, axis=2) for f in (a, b, c, d)]   # gray scenes as rgb8 frames
 
 
-def run_node(exe, tmp_path, seq, **params):
-    fpath = tmp_path / "frames.bin"
-    with open(fpath, "wb") as f:
-        f.write(b"MDXF" + struct.pack("<I", len(seq)))
-        for a in seq:
-            a = np.ascontiguousarray(a, np.uint8)
-            f.write(struct.pack("<4I", a.shape[0], a.shape[1], a.strides[0], 4) + b"rgb8" + a.tobytes())
-    out = tmp_path / "out"
-    out.mkdir()
-    args = [exe, str(fpath), str(out)] + [f"{k}={v}" for k, v in params.items()]
-    return subprocess.run(args, capture_output=True, text=True, timeout=120), out
-
-
-def read_mask(path):
-    b = open(path, "rb").read()
-    _, _, w, h, npts = struct.unpack_from("<5i", b, 0)
-    return np.frombuffer(b, np.uint8, w * h, 32 + 72 + 9 * npts).reshape(h, w).copy()
-
-
-def read_regions(path):
-    b = open(path, "rb").read()
-    num_all, num_kept = struct.unpack_from("<2i", b, 0)
-    assert len(b) == 8 + 32 * num_kept
-    return num_all, np.frombuffer(b, np.int32, 8 * num_kept, 8).reshape(num_kept, 8)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("region_open", [1, 0])
 def test_both_nodes_regions_and_motion_log(node_exe, tmp_path, mdx, sequence, region_open):
     from motion_detection_amd.node import Image, MotionDetectionNode
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=0, egomotion=0, pixel_step=PS, region_min_area=MIN_AREA,
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=0, egomotion=0, pixel_step=PS, region_min_area=MIN_AREA,
                       region_open=region_open, log_contours=1)
     assert p.returncode == 0, p.stderr
     nproc = len(sequence) - 1
@@ -88,8 +50,7 @@ def test_both_nodes_regions_and_motion_log(node_exe, tmp_path, mdx, sequence, re
         assert num_all == ref["num_all"] == r.regions.num_all
         assert np.array_equal(regs, ref["kept"]) and np.array_equal(r.regions.regions, ref["kept"])
         assert r.regions.num_kept == len(ref["kept"])
-        for i, (x, y, w, h) in enumerate(ref["kept"][:, :4].tolist()):
-            lines.append(f"{fi}, {i}, {x}, {y}, {x + w}, {y + h}\n")
+        lines.append(log_lines(fi, ref["kept"][:, :4]))
         total_kept += len(regs)
         k += 1
     assert k == nproc and total_kept >= 1                    # else the comparison above is vacuous
@@ -102,7 +63,7 @@ def test_both_nodes_regions_and_motion_log(node_exe, tmp_path, mdx, sequence, re
 @pytest.mark.gpu
 def test_knob_off_writes_no_region_files(node_exe, tmp_path, mdx, sequence):
     from motion_detection_amd.node import Image, MotionDetectionNode
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=0, egomotion=0, pixel_step=PS)
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=0, egomotion=0, pixel_step=PS)
     assert p.returncode == 0, p.stderr
     names = os.listdir(out)
     assert "res_0.bin" in names

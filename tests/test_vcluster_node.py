@@ -10,27 +10,14 @@ the checker) so that every processed frame has several clusters, one of them kep
 value within 1e-9 of the threshold; the tests assert all of that on what the device reports.
 """
 import os
-import shutil
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_cluster_node import run_node
+from node_io import ROOT, log_lines, node_exe, read_vclusters, rgb8, run_node  # noqa: F401 (node_exe: a fixture)
 from test_vcluster import MARGIN, vcluster_reference
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "host")
 W, H, PS, THR, ATHR = 160, 120, 10, 15.0, 0.1
-
-
-@pytest.fixture(scope="module")
-def node_exe(mdx):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    subprocess.run(["make", "-s", "-C", HOST], check=True)
-    return os.path.join(HOST, "mdx_node")
 
 
 @pytest.fixture(scope="module")
@@ -39,26 +26,10 @@ def sequence():
     return [g["img1"], g["img2"], g["img1"], g["img2"]]
 
 
-def read_vclusters(path):
-    b = open(path, "rb").read()
-    n, nact, num_all, num_kept = struct.unpack_from("<4i", b, 0)
-    assert len(b) == 16 + 32 * n + 4 * n + 4 * num_kept + 16 * num_kept
-    vec = np.frombuffer(b, np.float64, 4 * n, 16).reshape(n, 4)
-    o = 16 + 32 * n
-    labels = np.frombuffer(b, np.int32, n, o)
-    kept = np.frombuffer(b, np.int32, num_kept, o + 4 * n)
-    rects = np.frombuffer(b, np.int32, 4 * num_kept, o + 4 * n + 4 * num_kept).reshape(num_kept, 4)
-    return vec, nact, num_all, labels, kept, rects
-
-
-def log_lines(frame, rects):
-    return "".join(f"{frame}, {i}, {x}, {y}, {x + w}, {y + h}\n" for i, (x, y, w, h) in enumerate(np.asarray(rects).tolist()))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("abs_int", [0, 1])
 def test_cpp_node_vector_clusters_and_motion_log(node_exe, tmp_path, sequence, abs_int):
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=1, egomotion=0, pixel_step=PS, distance_threshold=THR,
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=1, egomotion=0, pixel_step=PS, distance_threshold=THR,
                       angular_threshold=ATHR, abs_int=abs_int, log_contours=1)
     assert p.returncode == 0, p.stderr
     nproc = len(sequence) - 1                          # a ring of 2 frames
@@ -84,7 +55,7 @@ def test_cpp_node_vector_clusters_and_motion_log(node_exe, tmp_path, sequence, a
 
 @pytest.mark.gpu
 def test_cpp_node_without_angular_threshold_writes_no_file(node_exe, tmp_path, sequence):
-    p, out = run_node(node_exe, tmp_path, sequence, live_path=1, egomotion=0, pixel_step=PS, distance_threshold=THR)
+    p, out = run_node(node_exe, tmp_path, rgb8(sequence), live_path=1, egomotion=0, pixel_step=PS, distance_threshold=THR)
     assert p.returncode == 0, p.stderr
     names = os.listdir(out)
     assert "res_0.bin" in names and "motion.log" not in names
