@@ -41,6 +41,8 @@ struct Geometry {
     long long img_bytes;     // bytes of one pyramid slab (all levels)
     long long der_words;     // words of one derivative slab (all levels)
 };
+// the gray frame of a pair's pyramid slab: level 0's core, lv[0].pitch bytes per row
+inline uint8_t* level0_core(uint8_t* slab, const Geometry& g) { return slab + g.lv[0].img_off + g.lv[0].core(); }
 
 // Per-pair result of the classify + fit stage.
 struct PairFit {
@@ -330,10 +332,22 @@ struct WarpLaunch {
     const PairFit* fits = nullptr;
     const void* tinfo = nullptr;   // TileInfo[batch][ntiles] inside the launch's scratch
 };
-hipError_t launch_warp_diff(hipStream_t s, int batch, const uint8_t* g1, long long g1_stride, int g1_pitch,
-                            const uint8_t* g2, long long g2_stride, int g2_pitch, int w, int h,
-                            const PairFit* fits, uint8_t* mask, long long mask_stride, int thresh, void* scratch,
-                            size_t scratch_bytes, int row0 = 0, int row1 = -1, WarpLaunch* rec = nullptr);
+struct GrayPlane {
+    const uint8_t* p;         // pair 0's row 0
+    long long frame_stride;   // bytes between pairs
+    int pitch;                // bytes between rows
+};
+struct WarpArgs {
+    GrayPlane g1, g2;         // frame 1 (warped), frame 2
+    int w, h;
+    const PairFit* fits;
+    uint8_t* mask;            // the band's rows, w bytes each
+    long long mask_stride;    // bytes between pairs
+    int thresh;
+    int row0 = 0, row1 = -1;  // the band; row1 < 0: h
+};
+hipError_t launch_warp_diff(hipStream_t s, int batch, const WarpArgs& a, void* scratch, size_t scratch_bytes,
+                            WarpLaunch* rec = nullptr);
 // Test hook: the row path of every (pair, tile) of launch L, from the TileInfo records and fits its
 // k_warp_diff read; out[pair * ntiles + tile] = 0 general, 1 fixed point, 2 affine FP64,
 // 3 projective, -1 pair without a fit.  Waits for the stream.  At most cap codes are written.

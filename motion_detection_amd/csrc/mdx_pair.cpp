@@ -286,6 +286,21 @@ static void band_rows(const Geometry& g, const ClassPlan& P, RowSpan* rows)
     }
 }
 
+// The warp+diff stage of every entry, on c->stream: k_warp_prep's scratch, the launch, and its
+// record for the path report (mdx_debug_warp_paths).
+static int run_warp_diff(mdx_ctx* c, int batch, const WarpArgs& a)
+{
+    const size_t wsb = warp_scratch_bytes(batch, a.w, (a.row1 < 0 ? a.h : a.row1) - a.row0);
+    if (const int rc = ensure(c, c->wscr, wsb); rc != MDX_OK) return rc;
+    HIP_OR_RETURN(c, launch_warp_diff(c->stream, batch, a, c->wscr.p, wsb, &c->last_warp));
+    return MDX_OK;
+}
+// a pyramid slab's gray frames as a warp operand
+static GrayPlane pyr_gray(uint8_t* slab, const Geometry& g)
+{
+    return {level0_core(slab, g), g.img_bytes, g.lv[0].pitch};
+}
+
 // The pipeline on device buffers.  d_np/d_st must be valid (LK writes them).
 // Row-band mode (cand != null, batch 1): LK and classification for grid rows [gy0, gy1) only, the
 // band's record to *cand, no fit and no mask.
@@ -412,13 +427,8 @@ static int run_pipeline(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint
                                          fits, P.fit_mode, d_Hext, c->csum.p, cand, &ra));
     mark(c, 5);
     if (d_mask && !cand) {
-        const Level& L0 = g.lv[0];
-        const uint8_t* g1 = pyr1 + L0.img_off + L0.core();
-        const uint8_t* g2 = pyr2 + L0.img_off + L0.core();
-        const size_t wsb = warp_scratch_bytes(batch, w, h);
-        if ((rc = ensure(c, c->wscr, wsb)) != MDX_OK) return rc;
-        HIP_OR_RETURN(c, launch_warp_diff(s, batch, g1, g.img_bytes, L0.pitch, g2, g.img_bytes, L0.pitch, w, h, fits,
-                                          d_mask, (long long)w * h, P.thresh, c->wscr.p, wsb, 0, -1, &c->last_warp));
+        const WarpArgs wa = {pyr_gray(pyr1, g), pyr_gray(pyr2, g), w, h, fits, d_mask, (long long)w * h, P.thresh};
+        if ((rc = run_warp_diff(c, batch, wa)) != MDX_OK) return rc;
     }
     if ((d_H || d_num) && !cand) HIP_OR_RETURN(c, launch_export_fit(s, batch, fits, d_H, d_num));
     // (a row band: mdx_band_fit_warp_dev reads these pyramids, whichever half they are in, and
@@ -508,11 +518,9 @@ extern "C" int mdx_warp_diff_dev(mdx_ctx* c, int batch, const uint8_t* d_gray1, 
     for (int i = 0; i < 5; i++) mark(c, i);
     HIP_OR_RETURN(c, launch_set_fit_external(s, batch, d_H, fits));
     mark(c, 5);
-    const size_t wsb = warp_scratch_bytes(batch, w, h);
-    if ((rc = ensure(c, c->wscr, wsb)) != MDX_OK) return rc;
-    HIP_OR_RETURN(c, launch_warp_diff(s, batch, d_gray1, (long long)frame_stride, stride, d_gray2,
-                                      (long long)frame_stride, stride, w, h, fits, d_mask, (long long)w * h,
-                                      c->prm.thresh, c->wscr.p, wsb, 0, -1, &c->last_warp));
+    const long long fs = (long long)frame_stride;
+    const WarpArgs wa = {{d_gray1, fs, stride}, {d_gray2, fs, stride}, w, h, fits, d_mask, (long long)w * h, c->prm.thresh};
+    if ((rc = run_warp_diff(c, batch, wa)) != MDX_OK) return rc;
     mark(c, 6);
     return MDX_OK;
 }
@@ -571,19 +579,14 @@ extern "C" int mdx_band_fit_warp_dev(mdx_ctx* c, int nrec, const mdx_band_cand* 
     PairFit* fits = c->fits.as<PairFit>();
     if (!c->band_pyr1 || !c->band_img1) return set_err(c, MDX_EINVAL, "mdx_band_fit_warp_dev: no mdx_band_flow_dev before");
     HIP_OR_RETURN(c, launch_band_fit(s, nrec, d_cands, fits, w, h, y0, y1));
-    const Level& L0 = g.lv[0];
     // the band's flow built frame 1's pyramid for its own rows only: the rows this band's warp
     // reads beyond them (the fit is known now) are converted from the frame
     HIP_OR_RETURN(c, launch_gray_rows(s, c->band_img1, w, h, c->band_stride, c->band_fmt,
-                                      c->band_pyr1 + L0.img_off + L0.core(), L0.pitch, fits, c->band_built[0],
+                                      level0_core(c->band_pyr1, g), g.lv[0].pitch, fits, c->band_built[0],
                                       c->band_built[1]));
-    const uint8_t* g1 = c->band_pyr1 + L0.img_off + L0.core();
-    const uint8_t* g2 = c->band_pyr2 + L0.img_off + L0.core();
-    const size_t wsb = warp_scratch_bytes(1, w, y1 - y0);
-    if (const int erc = ensure(c, c->wscr, wsb); erc != MDX_OK) return erc;
-    HIP_OR_RETURN(c, launch_warp_diff(s, 1, g1, g.img_bytes, L0.pitch, g2, g.img_bytes, L0.pitch, w, h, fits, d_mask_band,
-                                      (long long)w * (y1 - y0), c->prm.thresh, c->wscr.p, wsb, y0, y1,
-                                      &c->last_warp));
+    const WarpArgs wa = {pyr_gray(c->band_pyr1, g), pyr_gray(c->band_pyr2, g), w, h, fits, d_mask_band,
+                         (long long)w * (y1 - y0), c->prm.thresh, y0, y1};
+    if (const int rc = run_warp_diff(c, 1, wa); rc != MDX_OK) return rc;
     if (d_H || d_num_vectors) HIP_OR_RETURN(c, launch_export_fit(s, 1, fits, d_H, d_num_vectors));
     // the band's pyramids have been read: the pipelined call two calls on may overwrite them
     if (c->prm.call_pipelining) HIP_OR_RETURN(c, hipEventRecord(c->pyr_free[c->band_half], s));

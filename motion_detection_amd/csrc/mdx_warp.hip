@@ -33,9 +33,9 @@
 //     (q0, q1) <= 8160; horizontal with one v_dot2_u32_u16: s = 64*(q0 (32-fx) + q1 fx) + 32.
 //   * Threshold without the >> 10: out = (S + 512) >> 10 with S = (s - 32)/64, and
 //     |out - g| > t  <=>  |s - 65536 g| >= 65536 t + 32800 (exact).
-//     v_sad_u32(s, g << 16, 2^31 - 65536 t - 32800) sets bit 31 iff the pixel moves (g << 16 is
-//     one v_perm of the gray2 dword); v_perm's sign-replicating selectors turn the four flags
-//     into the four 0x00/0xff mask bytes.
+//     One sum-of-absolute-differences instruction, |s - (g << 16)| + 2^31 - 65536 t - 32800, sets
+//     bit 31 iff the pixel moves (g << 16 is one v_perm of the gray2 dword); v_perm's
+//     sign-replicating selectors turn the four flags into the four 0x00/0xff mask bytes.
 //   * gray2 loads / mask stores go through buffer descriptors: lanes past the right edge get an
 //     out-of-range offset and rows past the band fall outside the mask descriptor, so the row
 //     loop is branch-free.  60 VALU per row of four pixels in the ISA of the fixed-point rows
@@ -72,18 +72,24 @@ __device__ __forceinline__ int clamp_int_from_double(double v)
     return (int)__builtin_rint(r);
 }
 
+// The reference's origin of row y in the block that starts at column xb, in its evaluation order
+// (every product and sum rounded: -ffp-contract=off is load-bearing).  Affine M: W0 goes unused.
+struct BlockOrigin { double X0, Y0, W0; };
+__device__ __forceinline__ BlockOrigin block_origin(const double* M, int xb, int y)
+{
+    return {M[0] * xb + M[1] * y + M[2], M[3] * xb + M[4] * y + M[5], M[6] * xb + M[7] * y + M[8]};
+}
+
 // General path: one destination pixel, any M, reading gray1 straight from global memory.
 __device__ __forceinline__ uint8_t warp_px_general(const double* M, const uint8_t* src, int pitch, int w, int h, int x,
                                                    int y, int bw0, int g2v, int thresh)
 {
     const int xb = (x / bw0) * bw0, x1 = x - xb;
-    const double X0 = M[0] * xb + M[1] * y + M[2];
-    const double Y0 = M[3] * xb + M[4] * y + M[5];
-    const double W0 = M[6] * xb + M[7] * y + M[8];
-    const double Wv = W0 + M[6] * x1;
+    const BlockOrigin o = block_origin(M, xb, y);
+    const double Wv = o.W0 + M[6] * x1;
     const double Wd = Wv != 0.0 ? 32.0 / Wv : 0.0;
-    const int X = clamp_int_from_double((X0 + M[0] * x1) * Wd);
-    const int Y = clamp_int_from_double((Y0 + M[3] * x1) * Wd);
+    const int X = clamp_int_from_double((o.X0 + M[0] * x1) * Wd);
+    const int Y = clamp_int_from_double((o.Y0 + M[3] * x1) * Wd);
     const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
     const int fx = X & 31, fy = Y & 31;
     // (0,0) cell of BilinearTab_i is {32767,0,0,1}; for 8-bit data it yields the same value as
@@ -157,20 +163,18 @@ __device__ TileInfo tile_info(const double* M, int x0, int y0, int w, int yend, 
     const int cxl = min(kBW - 1, w - 1 - xb), cyl = min(kTH - 1, yend - 1 - y0);
     const int c = lane & 3;
     const int x1 = (c & 1) ? cxl : 0, y = y0 + ((c & 2) ? cyl : 0);
-    const double X0 = M[0] * xb + M[1] * y + M[2];
-    const double Y0 = M[3] * xb + M[4] * y + M[5];
+    const BlockOrigin o = block_origin(M, xb, y);
     double Wd = M[8] != 0.0 ? 32.0 / M[8] : 0.0;
     int wsign = 1;
     if (!affine) {                                               // the reference's per-pixel W
-        const double W0 = M[6] * xb + M[7] * y + M[8];
-        const double Wv = W0 + M[6] * x1;
+        const double Wv = o.W0 + M[6] * x1;
         Wd = Wv != 0.0 ? 32.0 / Wv : 0.0;
         const double aw = fabs(Wv);
         // W in [2^-100, 2^100] at every corner (so over the tile): div32's range; |W| >= 64 |M6|:
         // W0 + M6 * x1 does not cancel (warp_rows_pj's estimate)
         wsign = (aw >= 0x1p-100 && aw <= 0x1p100 && aw >= 64.0 * fabs(M[6])) ? (Wv > 0.0 ? 1 : 2) : 0;
     }
-    const double px = (X0 + M[0] * x1) * Wd, py = (Y0 + M[3] * x1) * Wd;
+    const double px = (o.X0 + M[0] * x1) * Wd, py = (o.Y0 + M[3] * x1) * Wd;
     const double lim = affine ? 1073741824.0 : 16777216.0;   // 2^30; projective 2^24 (warp_rows_pj's bound)
     int ok = (px > -lim && px < lim && py > -lim && py < lim && wsign != 0) ? 1 : 0;
     int smin = wsign, smax = wsign;
@@ -224,17 +228,105 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, lon
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, n, 0x00020000);
 }
 
-// Fast-path rows of one lane: 4 columns x 8 rows (tile rows r0 + 8i).  xyp points at this lane's
-// (X0, Y0) of row r0 and block; tab8 at the weight table (entry f at byte 8f: (32-f, f), then
-// 64*(32-f, f)); src_base is the staged footprint.  g2 / mask go through buffer descriptors whose
-// per-lane offsets are out of range for idle lanes; ROWCHK (partial tiles) sends rows past the
-// band to row r0's coordinates so every tap stays inside the footprint.
+// ---- Fast-path rows of one lane: 4 columns x 8 rows (tile rows r0 + 8i).  The three row loops --
+// warp_rows (affine FP64), warp_rows_fx (fixed point), warp_rows_pj (projective) -- differ only in
+// how a row's four pixels get their 1/32-px coordinates relative to the staged origin.  Everything
+// after that is written once, here: the gray2 loads, the register-held constants, the fixed-point
+// decode and the row tail.
+//
 // Cache policy of the streamed operands: gray2 is read once and the mask written once, so both go
 // non-temporal (nt).  The staged footprint keeps the default policy: adjacent tiles share its margin
 // lines in L2.  4K x 32 launch, alternating on one box: 216-224 us with nt on gray2 + mask, 233-235
 // without, 230-234 with nt on the footprint too, 222-224 with nt on the mask only; on a second box
 // 211-220 with nt against 223-229 without.
 constexpr int kCpStream = 2;   // buffer aux bit 1 = nt
+
+// What every row loop hands the shared pieces.  The mask goes through a buffer descriptor: idle
+// lanes (past the right edge) hold an out-of-range moff and rows past the band fall outside the
+// descriptor, so their stores drop and the row loop is branch-free.
+struct RowIO {
+    uint32_t src_base;            // the staged footprint (LDS byte address)
+    __amdgpu_buffer_rsrc_t mrs;   // mask rows [0, row1) of the frame
+    uint32_t moff;                // this lane's mask dword of row r0
+    int ms;                       // bytes between two of the lane's mask rows
+    uint32_t bias;                // 2^31 - 65536 t - 32800: the threshold as row_tail's addend
+    int nvalid;                   // rows r0 + 8i inside the band: i < nvalid
+    // rows past the band (partial tiles) take row r0's coordinates: every tap stays in the footprint
+    __device__ __forceinline__ int row(int i) const { return i < nvalid ? i : 0; }
+};
+
+// gray2: the lane's dword soff bytes below its first row's (idle lanes: g2off out of range, zeros).
+// One row per call: a helper that loops over the 8 rows changes k_warp_diff's VALU code.
+__device__ __forceinline__ uint32_t load_gray2(__amdgpu_buffer_rsrc_t g2rs, uint32_t g2off, int soff)
+{
+    return __builtin_amdgcn_raw_buffer_load_b32(g2rs, (int)g2off, soff, kCpStream);
+}
+
+// Loop constants held in registers once (gfx9 VOP3 takes no literals: otherwise each row would
+// rematerialise them with v_mov): the gray2 byte selectors in SGPRs (v_perm(0, G, gsel[k]) =
+// g_k << 16), the wx multiplier in a VGPR.
+struct RowConsts { uint32_t gsel[4], mulx; };
+__device__ __forceinline__ RowConsts row_consts()
+{
+    RowConsts c;
+    asm volatile("s_mov_b32 %0, 0x0c000c0c" : "=s"(c.gsel[0]));
+    asm volatile("s_mov_b32 %0, 0x0c010c0c" : "=s"(c.gsel[1]));
+    asm volatile("s_mov_b32 %0, 0x0c020c0c" : "=s"(c.gsel[2]));
+    asm volatile("s_mov_b32 %0, 0x0c030c0c" : "=s"(c.gsel[3]));
+    asm volatile("v_mov_b32 %0, 0x3fffc0" : "=v"(c.mulx));    // 64 * 65535
+    return c;
+}
+
+// A row's four pixels ready for the taps: LDS address of v00 (src_base + ((row << 8) | col)), and
+// the weight pairs as u16 halves, (32 - fy, fy) and 64 * (32 - fx, fx)
+struct Taps { uint32_t ad[4], wys[4], wxs[4]; };
+
+// Fixed-point decode (warp_rows_fx, warp_rows_pj): per axis U = [ staged column or row (8 bits) |
+// f (5 bits) | fraction (19 bits) ].  The tap address is byte 3 of the two words (one v_perm); the
+// weight pairs come from fx, fy arithmetically (v_bfe + v_mad_u24: f * 65535 + 32 = (32 - f) | f << 16).
+__device__ __forceinline__ Taps fx_decode(const uint32_t (&ux)[4], const uint32_t (&uy)[4], uint32_t src_base,
+                                          uint32_t mulx)
+{
+    Taps t;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        t.ad[k] = src_base + __builtin_amdgcn_perm(uy[k], ux[k], 0x0c0c0703u);   // (row << 8) | col
+        const uint32_t fx = __builtin_amdgcn_ubfe(ux[k], 19, 5), fy = __builtin_amdgcn_ubfe(uy[k], 19, 5);
+        t.wys[k] = __umul24(fy, 65535u) + 32u;               // (32 - fy, fy)
+        t.wxs[k] = __umul24(fx, mulx) + 2048u;               // 64 * (32 - fx, fx)
+    }
+    return t;
+}
+
+// Row tail: taps -> vertical -> horizontal -> threshold -> pack -> store, for the lane's i-th row
+// (g: its gray2 dword).  gsel: the four gray2 byte selectors, from row_consts() or as literals.
+__device__ __forceinline__ void row_tail(const Taps& t, uint32_t g, const uint32_t (&gsel)[4], const RowIO& io, int i)
+{
+    // taps: four byte reads per pixel, c0 = (v00, v01), c1 = (v10, v11) as u16 halves.
+    // (ds_read_*_d16_hi does not preserve the low half on gfx950 with SRAM ECC, and unaligned
+    // ds_read_u16 is correct but ~4x slower here.)
+    uint32_t c0s[4], c1s[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        lds_u8* p = (lds_u8*)(uintptr_t)t.ad[k];
+        c0s[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
+        c1s[k] = (uint32_t)p[kSP] | ((uint32_t)p[kSP + 1] << 16);
+    }
+    uint32_t e[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const u16x2v c0 = __builtin_bit_cast(u16x2v, c0s[k]), c1 = __builtin_bit_cast(u16x2v, c1s[k]);
+        const u16x2v wy = __builtin_bit_cast(u16x2v, t.wys[k]);
+        const u16x2v q = c0 * wy.xx + c1 * wy.yy;     // (q0, q1): vertical, exact in u16
+        const uint32_t s = __builtin_amdgcn_udot2(q, __builtin_bit_cast(u16x2v, t.wxs[k]), 32u, false);
+        const uint32_t g16 = __builtin_amdgcn_perm(0u, g, gsel[k]);   // g_k << 16
+        asm("v_sad_u32 %0, %1, %2, %3" : "=v"(e[k]) : "v"(s), "v"(g16), "s"(io.bias));   // bit 31: moving
+    }
+    // v_perm selectors 9 / 11 replicate bit 31 of src1 / src0: 0xff or 0x00 bytes
+    const uint32_t out = __builtin_amdgcn_perm(e[1], e[0], 0x0c0c0b09u) | __builtin_amdgcn_perm(e[3], e[2], 0x0b090c0cu);
+    __builtin_amdgcn_raw_buffer_store_b32(out, io.mrs, (int)io.moff, i * io.ms, kCpStream);
+}
+
 // 32 / d correctly rounded, for |d| in [2^-100, 2^100] (tile_info keeps the fast path there): the
 // compiler's IEEE double division without its v_div_scale / v_div_fixup steps, which only act on
 // exponents far outside that range (huge quotients, denormals, inf / nan) -- two Newton steps on
@@ -252,66 +344,41 @@ __device__ __forceinline__ double div32(double d)
     const double rem = __builtin_fma(-d, q0, 32.0);
     return __builtin_fma(rem, r2, q0);
 }
-template <bool POW2, bool ROWCHK>
-__device__ __forceinline__ void warp_rows(lds_d2* xyp, lds_u8* tab8, uint32_t src_base, int nvalid,
-                                          __amdgpu_buffer_rsrc_t g2rs, uint32_t g2off, int g2s,
-                                          __amdgpu_buffer_rsrc_t mrs, uint32_t moff, int ms, const double* tx,
-                                          const double* ty, double Wd, double mX, double mY, uint32_t bias)
+
+// Affine FP64 rows (32/M8 not a power of two; a power of two takes warp_rows_fx).  xyp points at
+// this lane's (X0, Y0) of row r0 and block, tx / ty hold M0*x1, M3*x1 of its four columns, tab8 the
+// weight table (entry f at byte 8f: (32-f, f), then 64*(32-f, f)).  Per pixel one FP64 add and,
+// per axis, the product (X0 + M0*x1) * Wd rounded as the reference rounds it, then the add of the
+// magic constant that rounds it to an integer.  Every tile checks its rows against the band.
+__device__ __forceinline__ void warp_rows(const RowIO& io, lds_d2* xyp, lds_u8* tab8, __amdgpu_buffer_rsrc_t g2rs,
+                                          uint32_t g2off, int g2s, const double* tx, const double* ty, double Wd,
+                                          double mX, double mY)
 {
     uint32_t G[kTH / 8];
 #pragma unroll
-    for (int i = 0; i < kTH / 8; i++) G[i] = __builtin_amdgcn_raw_buffer_load_b32(g2rs, (int)g2off, i * g2s, kCpStream);
+    for (int i = 0; i < kTH / 8; i++) G[i] = load_gray2(g2rs, g2off, i * g2s);
+    // as literals: this loop does not hold them in registers
+    const uint32_t gsel[4] = {0x0c000c0cu, 0x0c010c0cu, 0x0c020c0cu, 0x0c030c0cu};
 #pragma unroll
     for (int i = 0; i < kTH / 8; i++) {
-        const int ri = ROWCHK ? (i < nvalid ? i : 0) : i;
-        const d2v xy = xyp[16 * ri];                      // rows are 2 blocks x 16 B apart
+        const d2v xy = xyp[16 * io.row(i)];               // rows are 2 blocks x 16 B apart
         uint32_t xs_[4], ys_[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const double ax = xy.x + tx[k], ay = xy.y + ty[k];
-            double rx, ry;
-            if (POW2) {                            // (X0 + M0*x1) * Wd exact: one rounding
-                rx = __builtin_fma(ax, Wd, mX);
-                ry = __builtin_fma(ay, Wd, mY);
-            } else {                                      // round the product, then to integer
-                rx = ax * Wd + mX;
-                ry = ay * Wd + mY;
-            }
-            xs_[k] = (uint32_t)__double2loint(rx);        // X - 32 * sxa
-            ys_[k] = (uint32_t)__double2loint(ry);        // Y - 32 * sya
+            xs_[k] = (uint32_t)__double2loint(ax * Wd + mX);   // X - 32 * sxa: round the product,
+            ys_[k] = (uint32_t)__double2loint(ay * Wd + mY);   // Y - 32 * sya  then to integer
         }
-        uint32_t ad[4], wys[4], wxs[4];
+        Taps t;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             // 8X: byte 1 is the staged column (row), bits 3..7 index the 8-B weight table
             const uint32_t lx = xs_[k] << 3, ly = ys_[k] << 3;
-            ad[k] = src_base + __builtin_amdgcn_perm(ly, lx, 0x0c0c0501u);   // (row << 8) | col
-            wys[k] = *(lds_u32*)(tab8 + (ly & 0xf8u));       // (32 - fy, fy)
-            wxs[k] = *(lds_u32*)(tab8 + (lx & 0xf8u) + 4);   // 64 * (32 - fx, fx)
+            t.ad[k] = io.src_base + __builtin_amdgcn_perm(ly, lx, 0x0c0c0501u);   // (row << 8) | col
+            t.wys[k] = *(lds_u32*)(tab8 + (ly & 0xf8u));       // (32 - fy, fy)
+            t.wxs[k] = *(lds_u32*)(tab8 + (lx & 0xf8u) + 4);   // 64 * (32 - fx, fx)
         }
-        // taps: four byte reads per pixel, c0 = (v00, v01), c1 = (v10, v11) as u16 halves.
-        // (ds_read_*_d16_hi does not preserve the low half on gfx950 with SRAM ECC, and unaligned
-        // ds_read_u16 is correct but ~4x slower here.)
-        uint32_t c0s[4], c1s[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            lds_u8* p = (lds_u8*)(uintptr_t)ad[k];
-            c0s[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-            c1s[k] = (uint32_t)p[kSP] | ((uint32_t)p[kSP + 1] << 16);
-        }
-        uint32_t e[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const u16x2v c0 = __builtin_bit_cast(u16x2v, c0s[k]), c1 = __builtin_bit_cast(u16x2v, c1s[k]);
-            const u16x2v wy = __builtin_bit_cast(u16x2v, wys[k]);
-            const u16x2v q = c0 * wy.xx + c1 * wy.yy;     // (q0, q1): vertical, exact in u16
-            const uint32_t s = __builtin_amdgcn_udot2(q, __builtin_bit_cast(u16x2v, wxs[k]), 32u, false);
-            const uint32_t g16 = __builtin_amdgcn_perm(0u, G[i], 0x0c000c0cu | ((uint32_t)k << 16));   // g_k << 16
-            asm("v_sad_u32 %0, %1, %2, %3" : "=v"(e[k]) : "v"(s), "v"(g16), "s"(bias));   // bit 31: moving
-        }
-        // v_perm selectors 9 / 11 replicate bit 31 of src1 / src0: 0xff or 0x00 bytes
-        const uint32_t out = __builtin_amdgcn_perm(e[1], e[0], 0x0c0c0b09u) | __builtin_amdgcn_perm(e[3], e[2], 0x0b090c0cu);
-        __builtin_amdgcn_raw_buffer_store_b32(out, mrs, (int)moff, i * ms, kCpStream);
+        row_tail(t, G[i], gsel, io, i);
     }
 }
 
@@ -327,9 +394,8 @@ __device__ __forceinline__ void warp_rows(lds_d2* xyp, lds_u8* tab8, uint32_t sr
 // range (about 4 in 2^19) take the reference's FP64 expression.  They are found in two steps: the
 // workgroup's per-axis bucket map marks every fraction of A that any column x1 of a block could
 // turn bad (a row-block whose A falls in a marked bucket carries a flag in s_fx), and only lanes of
-// flagged row-blocks test their four pixels.  Then, per pixel: the tap address is byte 3 of the two
-// sums (one v_perm), the bilinear weight pairs come from fx, fy arithmetically (v_bfe + v_mad_u24:
-// f * 65535 + 32 = (32 - f) | f << 16), and the rest is warp_rows's.
+// flagged row-blocks test their four pixels.  Then fx_decode and row_tail.  G: the lane's gray2
+// dwords, loaded by the caller ahead of the barrier.  ROWCHK: the tile has rows past the band.
 #ifndef MDX_WARP_BM_BITS
 #define MDX_WARP_BM_BITS 13
 #endif
@@ -337,22 +403,14 @@ constexpr int kBmBits = MDX_WARP_BM_BITS;     // bucket map: 2^kBmBits buckets o
 static_assert(kBmBits <= 16, "a bad range (5 units) must span at most two buckets");
 typedef __attribute__((address_space(3))) const v4u lds_u4;
 template <bool ROWCHK>
-__device__ __forceinline__ void warp_rows_fx(lds_u4* fxp, lds_d2* xyp, uint32_t src_base, int nvalid,
-                                             const uint32_t (&G)[kTH / 8], __amdgpu_buffer_rsrc_t mrs, uint32_t moff,
-                                             int ms, const uint32_t (&bx)[4], const uint32_t (&by)[4], double M0,
-                                             double M3, int x1b, double Wd, double mX, double mY, uint32_t bias)
+__device__ __forceinline__ void warp_rows_fx(const RowIO& io, lds_u4* fxp, lds_d2* xyp, const uint32_t (&G)[kTH / 8],
+                                             const uint32_t (&bx)[4], const uint32_t (&by)[4], double M0, double M3,
+                                             int x1b, double Wd, double mX, double mY)
 {
-    // loop constants held in registers once (gfx9 VOP3 takes no literals: otherwise each row would
-    // rematerialise them with v_mov): the gray2 byte selectors in SGPRs, the wx multiplier in a VGPR
-    uint32_t gsel[4], mulx;
-    asm volatile("s_mov_b32 %0, 0x0c000c0c" : "=s"(gsel[0]));
-    asm volatile("s_mov_b32 %0, 0x0c010c0c" : "=s"(gsel[1]));
-    asm volatile("s_mov_b32 %0, 0x0c020c0c" : "=s"(gsel[2]));
-    asm volatile("s_mov_b32 %0, 0x0c030c0c" : "=s"(gsel[3]));
-    asm volatile("v_mov_b32 %0, 0x3fffc0" : "=v"(mulx));    // 64 * 65535
+    const RowConsts rc = row_consts();
 #pragma unroll
     for (int i = 0; i < kTH / 8; i++) {
-        const int ri = ROWCHK ? (i < nvalid ? i : 0) : i;
+        const int ri = ROWCHK ? io.row(i) : i;
         const v4u f = fxp[16 * ri];                     // (A_x, A_y, flag) of this lane's row and block
         uint32_t ux[4], uy[4];
 #pragma unroll
@@ -373,33 +431,7 @@ __device__ __forceinline__ void warp_rows_fx(lds_u4* fxp, lds_d2* xyp, uint32_t 
                 }
             }
         }
-        uint32_t ad[4], wys[4], wxs[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            ad[k] = src_base + __builtin_amdgcn_perm(uy[k], ux[k], 0x0c0c0703u);   // (row << 8) | col
-            const uint32_t fx = __builtin_amdgcn_ubfe(ux[k], 19, 5), fy = __builtin_amdgcn_ubfe(uy[k], 19, 5);
-            wys[k] = __umul24(fy, 65535u) + 32u;               // (32 - fy, fy)
-            wxs[k] = __umul24(fx, mulx) + 2048u;               // 64 * (32 - fx, fx)
-        }
-        uint32_t c0s[4], c1s[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            lds_u8* p = (lds_u8*)(uintptr_t)ad[k];
-            c0s[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-            c1s[k] = (uint32_t)p[kSP] | ((uint32_t)p[kSP + 1] << 16);
-        }
-        uint32_t e[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const u16x2v c0 = __builtin_bit_cast(u16x2v, c0s[k]), c1 = __builtin_bit_cast(u16x2v, c1s[k]);
-            const u16x2v wy = __builtin_bit_cast(u16x2v, wys[k]);
-            const u16x2v q = c0 * wy.xx + c1 * wy.yy;
-            const uint32_t s = __builtin_amdgcn_udot2(q, __builtin_bit_cast(u16x2v, wxs[k]), 32u, false);
-            const uint32_t g16 = __builtin_amdgcn_perm(0u, G[i], gsel[k]);
-            asm("v_sad_u32 %0, %1, %2, %3" : "=v"(e[k]) : "v"(s), "v"(g16), "s"(bias));
-        }
-        const uint32_t out = __builtin_amdgcn_perm(e[1], e[0], 0x0c0c0b09u) | __builtin_amdgcn_perm(e[3], e[2], 0x0b090c0cu);
-        __builtin_amdgcn_raw_buffer_store_b32(out, mrs, (int)moff, i * ms, kCpStream);
+        row_tail(fx_decode(ux, uy, io.src_base, rc.mulx), G[i], rc.gsel, io, i);
     }
 }
 
@@ -417,32 +449,25 @@ __device__ __forceinline__ void warp_rows_fx(lds_u4* fxp, lds_d2* xyp, uint32_t 
 // reference within 2^-9 unit (an rcp 16x less accurate than measured would still give < 8 units):
 // whenever U's fraction is at least kPjGuard units from the boundary (0), floor(U / 2^19)
 // is the reference's X' and not a tie.  The other pixels (64 of every 2^19 fractions per axis) take
-// the exact form: W, the correctly rounded 32/W (div32) and the rounded product.  Then the taps,
-// weights and threshold are warp_rows_fx's.
+// the exact form: W, the correctly rounded 32/W (div32) and the rounded product.  Then fx_decode
+// and row_tail.  Every tile checks its rows against the band.
 constexpr uint32_t kPjGuard = 32;
 __device__ __forceinline__ bool pj_near(uint32_t u)
 {
     return ((u + kPjGuard) & 0x7ffffu) < 2 * kPjGuard;
 }
-__device__ __forceinline__ void warp_rows_pj(lds_d2* xyp, lds_d2* wpp, uint32_t src_base, int nvalid,
-                                             __amdgpu_buffer_rsrc_t g2rs, uint32_t g2off, int g2s,
-                                             __amdgpu_buffer_rsrc_t mrs, uint32_t moff, int ms, double tx0, double ty0,
-                                             double tws0, const double* M, int x1b, double mX, double mY, double mXs,
-                                             double mYs, uint32_t bias)
+__device__ __forceinline__ void warp_rows_pj(const RowIO& io, lds_d2* xyp, lds_d2* wpp, __amdgpu_buffer_rsrc_t g2rs,
+                                             uint32_t g2off, int g2s, double tx0, double ty0, double tws0,
+                                             const double* M, int x1b, double mX, double mY, double mXs, double mYs)
 {
     uint32_t G[kTH / 8];
 #pragma unroll
-    for (int i = 0; i < kTH / 8; i++) G[i] = __builtin_amdgcn_raw_buffer_load_b32(g2rs, (int)g2off, i * g2s, kCpStream);
-    uint32_t gsel[4], mulx;
-    asm volatile("s_mov_b32 %0, 0x0c000c0c" : "=s"(gsel[0]));
-    asm volatile("s_mov_b32 %0, 0x0c010c0c" : "=s"(gsel[1]));
-    asm volatile("s_mov_b32 %0, 0x0c020c0c" : "=s"(gsel[2]));
-    asm volatile("s_mov_b32 %0, 0x0c030c0c" : "=s"(gsel[3]));
-    asm volatile("v_mov_b32 %0, 0x3fffc0" : "=v"(mulx));    // 64 * 65535
+    for (int i = 0; i < kTH / 8; i++) G[i] = load_gray2(g2rs, g2off, i * g2s);
+    const RowConsts rc = row_consts();
     const double M6s = M[6] * 0x1p-24;
 #pragma unroll
     for (int i = 0; i < kTH / 8; i++) {
-        const int ri = i < nvalid ? i : 0;                // rows past the band: row r0's coordinates
+        const int ri = io.row(i);
         const d2v xy = xyp[16 * ri];                      // (X0, Y0) of this lane's row and block
         const d2v wv = wpp[16 * ri];                      // (W0, W0 / 2^24)
         const double ax0 = xy.x + tx0, ay0 = xy.y + ty0, ws0 = wv.y + tws0;
@@ -490,33 +515,7 @@ __device__ __forceinline__ void warp_rows_pj(lds_d2* xyp, lds_d2* wpp, uint32_t 
                 }
             }
         }
-        uint32_t ad[4], wys[4], wxs[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            ad[k] = src_base + __builtin_amdgcn_perm(uy[k], ux[k], 0x0c0c0703u);   // (row << 8) | col
-            const uint32_t fx = __builtin_amdgcn_ubfe(ux[k], 19, 5), fy = __builtin_amdgcn_ubfe(uy[k], 19, 5);
-            wys[k] = __umul24(fy, 65535u) + 32u;               // (32 - fy, fy)
-            wxs[k] = __umul24(fx, mulx) + 2048u;               // 64 * (32 - fx, fx)
-        }
-        uint32_t c0s[4], c1s[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            lds_u8* p = (lds_u8*)(uintptr_t)ad[k];
-            c0s[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-            c1s[k] = (uint32_t)p[kSP] | ((uint32_t)p[kSP + 1] << 16);
-        }
-        uint32_t e[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const u16x2v c0 = __builtin_bit_cast(u16x2v, c0s[k]), c1 = __builtin_bit_cast(u16x2v, c1s[k]);
-            const u16x2v wy = __builtin_bit_cast(u16x2v, wys[k]);
-            const u16x2v q = c0 * wy.xx + c1 * wy.yy;
-            const uint32_t s = __builtin_amdgcn_udot2(q, __builtin_bit_cast(u16x2v, wxs[k]), 32u, false);
-            const uint32_t g16 = __builtin_amdgcn_perm(0u, G[i], gsel[k]);
-            asm("v_sad_u32 %0, %1, %2, %3" : "=v"(e[k]) : "v"(s), "v"(g16), "s"(bias));
-        }
-        const uint32_t out = __builtin_amdgcn_perm(e[1], e[0], 0x0c0c0b09u) | __builtin_amdgcn_perm(e[3], e[2], 0x0b090c0cu);
-        __builtin_amdgcn_raw_buffer_store_b32(out, mrs, (int)moff, i * ms, kCpStream);
+        row_tail(fx_decode(ux, uy, io.src_base, rc.mulx), G[i], rc.gsel, io, i);
     }
 }
 
@@ -554,9 +553,26 @@ hipError_t debug_warp_stamps(void* dst, size_t bytes)
 {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_warp_stamps), bytes < sizeof(g_warp_stamps) ? bytes : sizeof(g_warp_stamps));
 }
-#define WARP_DIFF_FN __device__ __forceinline__ void warp_diff_tile
-#else
-#define WARP_DIFF_FN __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_warp_diff
+// the bracket around k_warp_diff's body: start stamps where it is declared, end stamps on every return
+struct WarpStamp {
+    unsigned long long* st = nullptr;   // this workgroup's record, in its thread 0 when it is sampled
+    __device__ void stamp(int i) const
+    {
+        if (!st) return;
+        st[i] = __builtin_amdgcn_s_memtime();
+        st[i + 1] = __builtin_amdgcn_s_memrealtime();
+    }
+    __device__ WarpStamp()
+    {
+        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
+        const unsigned bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+        const unsigned step = (total + kStampSamples - 1) / kStampSamples;
+        if (threadIdx.x == 0 && bid % step == 0)
+            st = g_warp_stamps + ((size_t)(g_warp_launch % kStampLaunches) * kStampSamples + bid / step) * 4;
+        stamp(0);
+    }
+    __device__ ~WarpStamp() { stamp(2); }
+};
 #endif
 
 // n / d for uniform n, d < 2^31 with m = udiv_magic_of(d) = floor(2^32 / d) (d >= 2; m = 0 for d = 1):
@@ -631,19 +647,31 @@ __global__ __launch_bounds__(256) void k_warp_prep(const PairFit* __restrict__ f
     if ((tid & 7) == 0) tinfo[(long long)pair * (nbx * nby) + tile] = t;
 }
 
+// k_warp_diff's arguments, passed by value (launch_warp_diff fills them in this order)
+struct WarpDiffArgs {
+    const uint8_t* __restrict__ g1; long long g1_stride; int g1_pitch;   // gray planes: pair 0, bytes
+    const uint8_t* __restrict__ g2; long long g2_stride; int g2_pitch;   // between pairs and rows
+    int w, h, bw0;                                                       // bw0: the reference's block width
+    const PairFit* __restrict__ fits;
+    uint8_t* __restrict__ mask; long long mask_stride;                   // the band's rows, w bytes each
+    int thresh, vec_ok, row0, row1;                                      // vec_ok: dword-aligned gray2 / mask rows
+    const TileInfo* __restrict__ tinfo; const WarpPrep* __restrict__ prep;   // from k_warp_prep
+    uint32_t mt, mx;                                                     // udiv_magic_of(tiles per pair, tile columns)
+};
+
 // grid: x -> tile column, y -> tile row of the band [row0, row1), z -> pair.  256 threads; lane l
 // of wave q owns columns x0 + 4*(l & 31) .. +3 of tile rows 2q + (l >> 5) + 8i, i = 0..7.  The
 // reference's blocking depends on the full height only through bw0, and each pixel's arithmetic
 // on (x, y) only, so a band is exactly the full frame's rows.  The tile's footprint bounds and
 // the pair's fixed-point tables come from k_warp_prep, so the setup has one barrier: footprint
 // DMA, gray2 loads and the per-row-block table in flight together, then the row loop.
-WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
-                                                   const uint8_t* __restrict__ g2, long long g2_stride, int g2_pitch,
-                                                   int w, int h, int bw0, const PairFit* __restrict__ fits,
-                                                   uint8_t* __restrict__ mask, long long mask_stride, int thresh,
-                                                   int vec_ok, int row0, int row1, const TileInfo* __restrict__ tinfo,
-                                                   const WarpPrep* __restrict__ prep, uint32_t mt, uint32_t mx)
+// The body stays in the kernel itself: as a device function inlined into it, the staging loop
+// compiles to different VALU code.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_warp_diff(const WarpDiffArgs a)
 {
+#if MDX_WARP_STAMP
+    const WarpStamp stamp;
+#endif
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[64];             // weight table (FP64 rows)
     __shared__ __attribute__((aligned(16))) double s_xy[kTH][2][2];         // (X0, Y0) per row, block
     __shared__ __attribute__((aligned(16))) double s_w0[kTH][2][2];         // projective: (W0, W0 / 2^24) per row, block
@@ -662,51 +690,52 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
         bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     }
     // the divisions by uniform values with host magic numbers: scalar multiplies, no VALU
-    const int pair = (int)udiv_magic((uint32_t)bid, (uint32_t)(nbx * nby), mt), tile = bid - pair * (nbx * nby);
-    const int ty_ = (int)udiv_magic((uint32_t)tile, (uint32_t)nbx, mx), tx_ = tile - ty_ * nbx;
+    const int pair = (int)udiv_magic((uint32_t)bid, (uint32_t)(nbx * nby), a.mt), tile = bid - pair * (nbx * nby);
+    const int ty_ = (int)udiv_magic((uint32_t)tile, (uint32_t)nbx, a.mx), tx_ = tile - ty_ * nbx;
     // The tile's scalar operands (the pair's fit, the tile's TileInfo) in ONE round trip: left to
     // itself the compiler sinks each scalar load into the branch that first uses it, and the DMA
     // then waits behind five dependent scalar-load latencies (kernel arguments, fit status, more
     // arguments, M and TileInfo, TileInfo.wd).  The TileInfo of a pair with no fit is not written
     // by k_warp_prep; it is read (in bounds) and unused.
-    const PairFit& f = fits[pair];
-    const TileInfo t = tinfo[(long long)pair * (nbx * nby) + tile];   // uniform: scalar loads
+    const PairFit& f = a.fits[pair];
+    const TileInfo t = a.tinfo[(long long)pair * (nbx * nby) + tile];   // uniform: scalar loads
     double M[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) M[k] = f.Hinv[k];
     const int fit_status = f.fit_status;
     asm volatile("" ::"s"(fit_status), "s"(t.wd), "s"(t.fast), "s"(t.sxa), "s"(t.sya), "s"(t.sw), "s"(t.sh),
                  "s"(M[0]), "s"(M[1]), "s"(M[2]), "s"(M[3]), "s"(M[4]), "s"(M[5]), "s"(M[6]), "s"(M[7]),
-                 "s"(M[8]), "s"(g1), "s"(g2), "s"(mask), "s"(prep));
+                 "s"(M[8]), "s"(a.g1), "s"(a.g2), "s"(a.mask), "s"(a.prep));
     // wave index in an SGPR: the staging loop's trip count and LDS addresses stay scalar
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int x0 = tx_ * kTW, y0 = row0 + ty_ * kTH;
+    const int x0 = tx_ * kTW, y0 = a.row0 + ty_ * kTH;
     const int cq = lane & 31;
     const int xs = x0 + 4 * cq;                     // this lane's 4 columns
     const int r0 = 2 * wave + (lane >> 5);          // this lane's first tile row (then every 8th)
-    const uint8_t* g2p = g2 + (long long)pair * g2_stride;
-    uint8_t* mp = mask + (long long)pair * mask_stride - (long long)row0 * w;   // indexed by frame row
+    const uint8_t* g2p = a.g2 + (long long)pair * a.g2_stride;
+    uint8_t* mp = a.mask + (long long)pair * a.mask_stride - (long long)a.row0 * a.w;   // indexed by frame row
 
     if (fit_status != 0) {   // no fit: the reference produces no mask; ours is all zero
-        const int nx = max(0, min(4, w - xs));
-        for (int r = r0; r < kTH && y0 + r < row1; r += 8) {
-            uint8_t* m = mp + (long long)(y0 + r) * w + xs;
+        const int nx = max(0, min(4, a.w - xs));
+        for (int r = r0; r < kTH && y0 + r < a.row1; r += 8) {
+            uint8_t* m = mp + (long long)(y0 + r) * a.w + xs;
             for (int k = 0; k < nx; k++) m[k] = 0;
         }
         return;
     }
-    const uint8_t* src = g1 + (long long)pair * g1_stride;
+    const uint8_t* src = a.g1 + (long long)pair * a.g1_stride;
     const bool affine = warp_is_affine(M);
     // fast path only over dword-aligned rows with reference blocks of 64 (uniform per workgroup)
-    const bool try_fast = warp_try_fast(bw0, vec_ok);
+    const bool try_fast = warp_try_fast(a.bw0, a.vec_ok);
     if (!warp_tile_fast(try_fast, t.fast)) {
         // ---- general path: per pixel, global gathers
-        const int nx = max(0, min(4, w - xs));
-        for (int r = r0; r < kTH && y0 + r < row1; r += 8) {
+        const int nx = max(0, min(4, a.w - xs));
+        for (int r = r0; r < kTH && y0 + r < a.row1; r += 8) {
             const int y = y0 + r;
-            const uint8_t* g2r = g2p + (long long)y * g2_pitch + xs;
-            uint8_t* m = mp + (long long)y * w + xs;
-            for (int k = 0; k < nx; k++) m[k] = warp_px_general(M, src, g1_pitch, w, h, xs + k, y, bw0, g2r[k], thresh);
+            const uint8_t* g2r = g2p + (long long)y * a.g2_pitch + xs;
+            uint8_t* m = mp + (long long)y * a.w + xs;
+            for (int k = 0; k < nx; k++)
+                m[k] = warp_px_general(M, src, a.g1_pitch, a.w, a.h, xs + k, y, a.bw0, g2r[k], a.thresh);
         }
         return;
     }
@@ -719,10 +748,10 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
         s_tab[2 * tid] = (uint32_t)(32 - tid) | ((uint32_t)tid << 16);
         s_tab[2 * tid + 1] = (uint32_t)(64 * (32 - tid)) | ((uint32_t)(64 * tid) << 16);
     }
-    const bool col_ok = xs < w;
+    const bool col_ok = xs < a.w;
     const uint32_t OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t g2rs = buf_rsrc(g2p, (long long)h * g2_pitch);
-    const uint32_t g2off = col_ok ? (uint32_t)((y0 + r0) * g2_pitch + xs) : OOB;
+    const __amdgpu_buffer_rsrc_t g2rs = buf_rsrc(g2p, (long long)a.h * a.g2_pitch);
+    const uint32_t g2off = col_ok ? (uint32_t)((y0 + r0) * a.g2_pitch + xs) : OOB;
     // lanes past the right edge compute on a valid column of block 0 and store nothing
     const int cqe = col_ok ? cq : (cq & 15);
     const int blk = cqe >> 4, x1b = 4 * (cqe & 15);
@@ -734,23 +763,23 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
     // are rewritten byte by byte once the DMA has landed.
     const int nch = (t.sw + 15) >> 4;                 // <= kSP / 16
     const int ch = lane & 15, sx = t.sxa + 16 * ch;
-    const bool inner = ch < nch && sx >= 0 && sx + 16 <= w;
+    const bool inner = ch < nch && sx >= 0 && sx + 16 <= a.w;
     {
-        const __amdgpu_buffer_rsrc_t srs = buf_rsrc(src, (long long)h * g1_pitch);
+        const __amdgpu_buffer_rsrc_t srs = buf_rsrc(src, (long long)a.h * a.g1_pitch);
         // A group of 4 staged rows wholly inside the image and the footprint (all but the edge
         // tiles' first / last groups) needs no per-lane test: the lane's offset within the group is
         // loop-invariant and the group's row start is the scalar offset (0 VALU per DMA instead of 6)
-        const uint32_t voff = inner ? (uint32_t)((lane >> 4) * g1_pitch + sx) : 0x80000000u;
+        const uint32_t voff = inner ? (uint32_t)((lane >> 4) * a.g1_pitch + sx) : 0x80000000u;
         for (int q = wave; 4 * q < t.sh; q += 4) {
             const int y4 = t.sya + 4 * q;
-            if (y4 >= 0 && y4 + 4 <= h && 4 * q + 4 <= t.sh) {
+            if (y4 >= 0 && y4 + 4 <= a.h && 4 * q + 4 <= t.sh) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(srs, (lds_ptr)&s_src[4 * q * kSP], 16, (int)voff,
-                                                         y4 * g1_pitch, 0, 0);
+                                                         y4 * a.g1_pitch, 0, 0);
             } else {
                 const int r = 4 * q + (lane >> 4);
                 const int sy = t.sya + r;
-                const uint32_t off = (inner && r < t.sh && (unsigned)sy < (unsigned)h)
-                                         ? (uint32_t)(sy * g1_pitch + sx) : 0x80000000u;
+                const uint32_t off = (inner && r < t.sh && (unsigned)sy < (unsigned)a.h)
+                                         ? (uint32_t)(sy * a.g1_pitch + sx) : 0x80000000u;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(srs, (lds_ptr)&s_src[4 * q * kSP], 16, (int)off, 0, 0, 0);
             }
         }
@@ -758,12 +787,11 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
     __builtin_amdgcn_sched_barrier(0);
     uint32_t bx[4] = {0, 0, 0, 0}, by[4] = {0, 0, 0, 0};
     if (pow2) {
-        // gray2: this lane's dwords of its 8 rows; B(x1) of its four columns (the per-column half of U)
+        // gray2, in flight with the DMA; B(x1) of the lane's four columns (the per-column half of U)
 #pragma unroll
-        for (int i = 0; i < kTH / 8; i++)
-            G[i] = __builtin_amdgcn_raw_buffer_load_b32(g2rs, (int)g2off, i * 8 * g2_pitch, kCpStream);
-        const v4u bxv = *reinterpret_cast<const v4u*>(&prep[pair].B[0][x1b]);
-        const v4u byv = *reinterpret_cast<const v4u*>(&prep[pair].B[1][x1b]);
+        for (int i = 0; i < kTH / 8; i++) G[i] = load_gray2(g2rs, g2off, i * 8 * a.g2_pitch);
+        const v4u bxv = *reinterpret_cast<const v4u*>(&a.prep[pair].B[0][x1b]);
+        const v4u byv = *reinterpret_cast<const v4u*>(&a.prep[pair].B[1][x1b]);
         bx[0] = bxv.x; bx[1] = bxv.y; bx[2] = bxv.z; bx[3] = bxv.w;
         by[0] = byv.x; by[1] = byv.y; by[2] = byv.z; by[3] = byv.w;
     }
@@ -771,21 +799,19 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
     // (the pair's bucket maps from k_warp_prep, read through L2)
     if (tid < 2 * kTH) {
         const int r = tid >> 1, b = tid & 1, y = y0 + r, xb = x0 + kBW * b;
-        const double X0 = M[0] * xb + M[1] * y + M[2];
-        const double Y0 = M[3] * xb + M[4] * y + M[5];
-        s_xy[r][b][0] = X0;
-        s_xy[r][b][1] = Y0;
+        const BlockOrigin o = block_origin(M, xb, y);
+        s_xy[r][b][0] = o.X0;
+        s_xy[r][b][1] = o.Y0;
         if (!affine) {
-            const double W0 = M[6] * xb + M[7] * y + M[8];
-            s_w0[r][b][0] = W0;
-            s_w0[r][b][1] = W0 * 0x1p-24;
+            s_w0[r][b][0] = o.W0;
+            s_w0[r][b][1] = o.W0 * 0x1p-24;
         }
         if (pow2) {
             const double fx_scale = 524288.0;                        // 2^19
-            const uint32_t Ax = floor_lo((Wd * X0 + 0.5 - 32.0 * t.sxa) * fx_scale);
-            const uint32_t Ay = floor_lo((Wd * Y0 + 0.5 - 32.0 * t.sya) * fx_scale);
+            const uint32_t Ax = floor_lo((Wd * o.X0 + 0.5 - 32.0 * t.sxa) * fx_scale);
+            const uint32_t Ay = floor_lo((Wd * o.Y0 + 0.5 - 32.0 * t.sya) * fx_scale);
             const uint32_t bx = (Ax & 0x7ffffu) >> (19 - kBmBits), by = (Ay & 0x7ffffu) >> (19 - kBmBits);
-            const WarpPrep& P = prep[pair];
+            const WarpPrep& P = a.prep[pair];
             const uint32_t flag = ((P.bm[0][bx >> 5] >> (bx & 31)) | (P.bm[1][by >> 5] >> (by & 31))) & 1u;
             s_fx[r][b] = make_uint4(Ax, Ay, flag, 0u);
         }
@@ -796,30 +822,29 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
     if (ch < nch && !inner)
         for (int q = wave; 4 * q < t.sh; q += 4) {
             const int r = 4 * q + (lane >> 4);
-            if (r < t.sh) stage_edge_chunks(src, g1_pitch, w, h, t.sya, sx, r, t.sh, t.sh, &s_src[16 * ch]);
+            if (r < t.sh) stage_edge_chunks(src, a.g1_pitch, a.w, a.h, t.sya, sx, r, t.sh, t.sh, &s_src[16 * ch]);
         }
     __syncthreads();
 
     const double magic = 6755399441055744.0;                 // 1.5 * 2^52: ulp 1
     const double mX = magic - 32.0 * t.sxa, mY = magic - 32.0 * t.sya;
-    const int tc = min(max(thresh, -1), 255);                // t < 0: all moving; t >= 255: none
-    const uint32_t bias = 0x80000000u - (uint32_t)(65536 * tc + 32800);
+    const int tc = min(max(a.thresh, -1), 255);              // t < 0: all moving; t >= 255: none
     lds_d2* xyp = (lds_d2*)(&s_xy[r0][blk][0]);
     lds_u8* tabp = (lds_u8*)(&s_tab[0]);
-    const uint32_t src_base = (uint32_t)(uintptr_t)(lds_u8*)(&s_src[0]);
-    // gray2 rows of this pair; mask rows [0, row1) of the frame (stores past the band drop)
-    const __amdgpu_buffer_rsrc_t mrs = buf_rsrc(mp, (long long)row1 * w);
-    const uint32_t moff = col_ok ? (uint32_t)((y0 + r0) * w + xs) : OOB;
-    const int nvalid = (row1 - y0 - r0 + 7) >> 3;            // rows r0 + 8i inside the band: i < nvalid
-    const bool rowchk = y0 + kTH > row1;
+    RowIO io;
+    io.src_base = (uint32_t)(uintptr_t)(lds_u8*)(&s_src[0]);
+    io.mrs = buf_rsrc(mp, (long long)a.row1 * a.w);
+    io.moff = col_ok ? (uint32_t)((y0 + r0) * a.w + xs) : OOB;
+    io.ms = 8 * a.w;
+    io.bias = 0x80000000u - (uint32_t)(65536 * tc + 32800);
+    io.nvalid = (a.row1 - y0 - r0 + 7) >> 3;
+    const bool rowchk = y0 + kTH > a.row1;
     if (pow2) {
         lds_u4* fxp = (lds_u4*)(&s_fx[r0][blk]);
         if (!rowchk)
-            warp_rows_fx<false>(fxp, xyp, src_base, nvalid, G, mrs, moff, 8 * w, bx, by, M[0],
-                                M[3], x1b, Wd, mX, mY, bias);
+            warp_rows_fx<false>(io, fxp, xyp, G, bx, by, M[0], M[3], x1b, Wd, mX, mY);
         else
-            warp_rows_fx<true>(fxp, xyp, src_base, nvalid, G, mrs, moff, 8 * w, bx, by, M[0],
-                               M[3], x1b, Wd, mX, mY, bias);
+            warp_rows_fx<true>(io, fxp, xyp, G, bx, by, M[0], M[3], x1b, Wd, mX, mY);
     } else if (affine) {
         double tx[4], ty[4];
 #pragma unroll
@@ -828,42 +853,16 @@ WARP_DIFF_FN(const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch,
             ty[k] = M[3] * (x1b + k);
             asm volatile("" : "+v"(tx[k]), "+v"(ty[k]));   // keep in registers (no per-row rematerialisation)
         }
-        warp_rows<false, true>(xyp, tabp, src_base, nvalid, g2rs, g2off, 8 * g2_pitch, mrs, moff, 8 * w, tx, ty, Wd, mX,
-                               mY, bias);
+        warp_rows(io, xyp, tabp, g2rs, g2off, 8 * a.g2_pitch, tx, ty, Wd, mX, mY);
     } else {
         const double x1d = (double)x1b;
         double tx0 = M[0] * x1d, ty0 = M[3] * x1d, tws0 = (M[6] * x1d) * 0x1p-24;
         asm volatile("" : "+v"(tx0), "+v"(ty0), "+v"(tws0));   // held in registers across the rows
         const double mXs = magic + 262144.0 - 16777216.0 * t.sxa, mYs = magic + 262144.0 - 16777216.0 * t.sya;
-        warp_rows_pj((lds_d2*)(&s_xy[r0][blk][0]), (lds_d2*)(&s_w0[r0][blk][0]), src_base, nvalid, g2rs, g2off,
-                     8 * g2_pitch, mrs, moff, 8 * w, tx0, ty0, tws0, M, x1b, mX, mY, mXs, mYs, bias);
+        warp_rows_pj(io, xyp, (lds_d2*)(&s_w0[r0][blk][0]), g2rs, g2off, 8 * a.g2_pitch, tx0, ty0, tws0, M, x1b, mX, mY,
+                     mXs, mYs);
     }
 }
-
-#if MDX_WARP_STAMP
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_warp_diff(
-    const uint8_t* __restrict__ g1, long long g1_stride, int g1_pitch, const uint8_t* __restrict__ g2,
-    long long g2_stride, int g2_pitch, int w, int h, int bw0, const PairFit* __restrict__ fits,
-    uint8_t* __restrict__ mask, long long mask_stride, int thresh, int vec_ok, int row0, int row1,
-    const TileInfo* __restrict__ tinfo, const WarpPrep* __restrict__ prep, uint32_t mt, uint32_t mx)
-{
-    const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-    const unsigned bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned step = (total + kStampSamples - 1) / kStampSamples;
-    const bool stamp = threadIdx.x == 0 && bid % step == 0;
-    unsigned long long* st = g_warp_stamps + ((size_t)(g_warp_launch % kStampLaunches) * kStampSamples + bid / step) * 4;
-    if (stamp) {
-        st[0] = __builtin_amdgcn_s_memtime();
-        st[1] = __builtin_amdgcn_s_memrealtime();
-    }
-    warp_diff_tile(g1, g1_stride, g1_pitch, g2, g2_stride, g2_pitch, w, h, bw0, fits, mask, mask_stride, thresh,
-                   vec_ok, row0, row1, tinfo, prep, mt, mx);
-    if (stamp) {
-        st[2] = __builtin_amdgcn_s_memtime();
-        st[3] = __builtin_amdgcn_s_memrealtime();
-    }
-}
-#endif
 
 size_t warp_scratch_bytes(int batch, int w, int rows)
 {
@@ -871,35 +870,34 @@ size_t warp_scratch_bytes(int batch, int w, int rows)
     return (size_t)batch * (sizeof(WarpPrep) + (size_t)tiles * sizeof(TileInfo)) + 256;
 }
 
-hipError_t launch_warp_diff(hipStream_t s, int batch, const uint8_t* g1, long long g1_stride, int g1_pitch,
-                            const uint8_t* g2, long long g2_stride, int g2_pitch, int w, int h, const PairFit* fits,
-                            uint8_t* mask, long long mask_stride, int thresh, void* scratch, size_t scratch_bytes,
-                            int row0, int row1, WarpLaunch* rec)
+hipError_t launch_warp_diff(hipStream_t s, int batch, const WarpArgs& a, void* scratch, size_t scratch_bytes,
+                            WarpLaunch* rec)
 {
     if (rec) *rec = WarpLaunch();
-    if (row1 < 0) row1 = h;
+    const int w = a.w, h = a.h, row0 = a.row0, row1 = a.row1 < 0 ? h : a.row1;
     if (row0 < 0 || row1 > h || row0 >= row1) return hipErrorInvalidValue;
     if (!scratch || scratch_bytes < warp_scratch_bytes(batch, w, row1 - row0)) return hipErrorInvalidValue;
     const int bh0 = h < 16 ? h : 16;
     const int bw0 = (1024 / bh0) < w ? (1024 / bh0) : w;
     // dword loads of gray2 / stores of the mask need 4-B aligned rows
-    const int vec_ok = ((uintptr_t)g2 % 4 == 0) && g2_stride % 4 == 0 && g2_pitch % 4 == 0 &&
-                       ((uintptr_t)mask % 4 == 0) && mask_stride % 4 == 0 && w % 4 == 0;
+    const int vec_ok = ((uintptr_t)a.g2.p % 4 == 0) && a.g2.frame_stride % 4 == 0 && a.g2.pitch % 4 == 0 &&
+                       ((uintptr_t)a.mask % 4 == 0) && a.mask_stride % 4 == 0 && w % 4 == 0;
     const dim3 grid((w + kTW - 1) / kTW, (row1 - row0 + kTH - 1) / kTH, batch);
     const int ntiles = (int)(grid.x * grid.y);
     WarpPrep* prep = reinterpret_cast<WarpPrep*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
     TileInfo* tinfo = reinterpret_cast<TileInfo*>(prep + batch);
-    hipLaunchKernelGGL(k_warp_prep, dim3(1 + (ntiles + 31) / 32, batch), dim3(256), 0, s, fits, w, row0, row1,
+    hipLaunchKernelGGL(k_warp_prep, dim3(1 + (ntiles + 31) / 32, batch), dim3(256), 0, s, a.fits, w, row0, row1,
                        (int)grid.x, (int)grid.y, tinfo, prep);
-    hipLaunchKernelGGL(k_warp_diff, grid, dim3(256), 0, s, g1, g1_stride, g1_pitch, g2, g2_stride, g2_pitch, w, h, bw0,
-                       fits, mask, mask_stride, thresh, vec_ok, row0, row1, tinfo, prep, udiv_magic_of((uint32_t)ntiles),
-                       udiv_magic_of(grid.x));
+    const WarpDiffArgs ka = {a.g1.p, a.g1.frame_stride, a.g1.pitch, a.g2.p, a.g2.frame_stride, a.g2.pitch,
+                             w, h, bw0, a.fits, a.mask, a.mask_stride, a.thresh, vec_ok, row0, row1,
+                             tinfo, prep, udiv_magic_of((uint32_t)ntiles), udiv_magic_of(grid.x)};
+    hipLaunchKernelGGL(k_warp_diff, grid, dim3(256), 0, s, ka);
     if (rec) {
         rec->batch = batch;
         rec->ntiles = ntiles;
         rec->bw0 = bw0;
         rec->vec_ok = vec_ok;
-        rec->fits = fits;
+        rec->fits = a.fits;
         rec->tinfo = tinfo;
     }
     return hipGetLastError();
