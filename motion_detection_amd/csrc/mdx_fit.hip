@@ -3,7 +3,29 @@
 // Every kernel reproduces the arithmetic of the OpenCV 2.4 routine the reference calls, bit for bit
 // (integer stages exactly; float and double stages in the same evaluation order, compiled with
 // -ffp-contract=off so no expression is fused into an FMA).
-//   A6/A7   k_classify/k_fit Vec4d classification, first-4 getPerspectiveTransform, invert
+//
+// The kernels, in launch order (launch_classify_fit; batch pairs of npts grid points, nblk blocks of
+// 256 points each):
+//   k_classify        one workgroup per block: the Vec4d of its points (optical_flow_calculator.cpp
+//                     :78-117) -> vectors; accepted count and first four accepted indices ->
+//                     BlockSummary.  Reads next_pts, status.
+//   k_fit             one wave per pair: scan of the BlockSummary counts -> accepted total and the
+//                     first four accepted points overall (the blocks are in the reference's point
+//                     order); first-4: the whole wave solves getPerspectiveTransform on them
+//                     (dev_perspective_fit_wave) and lane 0 writes the pair's PairFit; external H:
+//                     the record from H_ext; RANSAC: count and status only, and each block's
+//                     offset -> BlockSummary::ransac_off.
+//   k_band_record     row bands, in k_fit's place: the same scan; count and first four points ->
+//                     the band's mdx_band_cand.  No fit.
+//   k_ransac_compact, k_ransac_hyp, k_ransac_score, k_ransac_pick
+//                     MDX_FIT_RANSAC only, after k_fit: see the inventory above them.
+//   k_band_fit        row bands, one wave (launch_band_fit): merges every band's record -> the
+//                     frame's first four -> the same wave solve -> PairFit with the band's source rows.
+//   k_set_fit_external, k_export_fit
+//                     one thread per pair: PairFit from a given H (the warp-only entry); H and
+//                     num_vectors of the PairFit records to the caller's arrays.
+// Written once for all of them: grid_src / gather4 (grid index -> position, four correspondences),
+// classify_point (the acceptance test), block_rank, scan_blocks, write_fitted / write_no_fit.
 #include "mdx_internal.h"
 
 #include <float.h>
@@ -418,66 +440,84 @@ __device__ void dev_invert3x3(const double* m, double* out)
     }
 }
 
-// A6 + A7: classify every grid point (optical_flow_calculator.cpp:78-117), count accepted
-// vectors, pick the first four accepted in x-major order, fit and invert.  One 256-thread
-// workgroup per pair; the first-4 search is a ballot scan that stops as soon as 4 are found
-// (only the count needs the full sweep).
-// Two kernels.  k_classify: one 256-point block per workgroup writes the Vec4d of its points
-// and a summary {accepted count, first four accepted indices in block order}.  k_fit: one wave
-// per pair prefix-sums the block counts (x-major block order = the reference's point order),
-// picks the first four accepted points overall and runs the fit on lane 0.
-struct BlockSummary {
-    int count;
-    int first[4];
-    int pad_[3];
-};
-
-__global__ __launch_bounds__(256) void k_classify(const float* __restrict__ next_pts, const uint8_t* __restrict__ status,
-                                                  int npts, int ny, int gy0, int gy1, int pixel_step, double mvs,
-                                                  double* __restrict__ vectors, BlockSummary* __restrict__ summ)
+// ------------------------------------------------------------------ shared pieces
+// Grid index -> grid position: the grid is x-major, point i at column i / ny, row i % ny.
+__device__ __forceinline__ float2 grid_src(int i, int ny, int pixel_step)
 {
-    const int pair = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    __shared__ int s_wcnt[4];
-    const int i = blk * 256 + tid;
-    bool acc = false;
-    const int gyi = i % ny;
-    if (i < npts && gyi >= gy0 && gyi < gy1) {   // grid rows of the band (all rows: the full path)
-        const float sx = (float)((i / ny) * pixel_step), sy = (float)((i % ny) * pixel_step);
-        const float2 e = reinterpret_cast<const float2*>(next_pts)[(long long)pair * npts + i];
-        double v0, v1, v2, v3;
-        if (status[(long long)pair * npts + i]) {
-            const float xd = e.x - sx, yd = e.y - sy;       // float differences (:82-83)
-            if (fabs((double)fabsf(xd)) > mvs || fabs((double)fabsf(yd)) > mvs) {
-                acc = true;
-                v0 = sx; v1 = sy; v2 = xd; v3 = yd;
-            } else {
-                v0 = sx; v1 = sy; v2 = 0.0; v3 = 0.0;
-            }
-        } else {
-            v0 = -1.0; v1 = -1.0; v2 = 0.0; v3 = 0.0;
-        }
-        if (vectors) {
-            double4* v = reinterpret_cast<double4*>(vectors) + (long long)pair * npts + i;
-            *v = make_double4(v0, v1, v2, v3);
-        }
+    return make_float2((float)((i / ny) * pixel_step), (float)((i % ny) * pixel_step));
+}
+
+// The correspondence of grid point i of the pair whose points start at pair_base: src its grid
+// position, dst where the LK left it; gather4: of the four points idx (getPerspectiveTransform's
+// operands).
+__device__ __forceinline__ void gather_point(const float* next_pts, long long pair_base, int ny, int pixel_step, int i,
+                                             float* src, float* dst)
+{
+    const float2 s = grid_src(i, ny, pixel_step);
+    const float2 e = reinterpret_cast<const float2*>(next_pts)[pair_base + i];
+    src[0] = s.x;
+    src[1] = s.y;
+    dst[0] = e.x;
+    dst[1] = e.y;
+}
+__device__ __forceinline__ void gather4(const float* next_pts, long long pair_base, int ny, int pixel_step,
+                                        const int* idx, float* src, float* dst)
+{
+    for (int r = 0; r < 4; r++) gather_point(next_pts, pair_base, ny, pixel_step, idx[r], src + 2 * r, dst + 2 * r);
+}
+
+// The reference's classification of grid point i (optical_flow_calculator.cpp:78-117; o = the point's
+// offset in next_pts / status) and its Vec4d: untracked (-1, -1, 0, 0); tracked with both float
+// differences within min_vector_size (x, y, 0, 0); accepted (x, y, dx, dy).  Every kernel that asks
+// takes this one: the RANSAC list and scores must accept exactly the points k_classify counted.
+struct PointFlow {
+    float2 s, e;      // grid position, tracked position
+    bool accepted;
+    double4 vec;
+};
+__device__ __forceinline__ PointFlow classify_point(const float* next_pts, const uint8_t* status, long long o, int i,
+                                                    int ny, int pixel_step, double mvs)
+{
+    PointFlow p;
+    p.s = grid_src(i, ny, pixel_step);
+    p.e = reinterpret_cast<const float2*>(next_pts)[o];
+    p.accepted = false;
+    p.vec = make_double4(-1.0, -1.0, 0.0, 0.0);
+    if (status[o]) {
+        const float xd = p.e.x - p.s.x, yd = p.e.y - p.s.y;       // float differences (:82-83)
+        p.accepted = fabs((double)fabsf(xd)) > mvs || fabs((double)fabsf(yd)) > mvs;
+        p.vec = p.accepted ? make_double4(p.s.x, p.s.y, xd, yd) : make_double4(p.s.x, p.s.y, 0.0, 0.0);
     }
+    return p;
+}
+
+// Rank of this thread's accepted point among the accepted points of its 256-point block (block
+// order).  s_wcnt: 4 ints of LDS, the waves' counts.  Every thread of the block calls it; after it
+// block_total(s_wcnt) is the block's number of accepted points.
+__device__ __forceinline__ int block_rank(bool acc, int* s_wcnt)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned long long bal = __ballot(acc);
     if (lane == 0) s_wcnt[wave] = __popcll(bal);
     __syncthreads();
     int before = 0;
     for (int w2 = 0; w2 < wave; w2++) before += s_wcnt[w2];
-    const int rank = before + __popcll(bal & ((1ull << lane) - 1ull));
-    BlockSummary& S = summ[(long long)pair * gridDim.x + blk];
-    if (acc && rank < 4) S.first[rank] = i;
-    if (tid == 0) S.count = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+    return before + __popcll(bal & ((1ull << lane) - 1ull));
 }
+__device__ __forceinline__ int block_total(const int* s_wcnt) { return s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3]; }
 
-__global__ __launch_bounds__(64) void k_fit(const float* __restrict__ next_pts, int npts, int ny, int pixel_step,
-                                            BlockSummary* __restrict__ summ, int nblk, PairFit* __restrict__ fits,
-                                            int fit_mode, const double* __restrict__ H_ext)
+// One wave's scan over a pair's nblk block summaries S, 64 blocks at a time (block order = the
+// reference's point order): the accepted total and the first four accepted points overall (-1 where
+// there are fewer), both wave-uniform.  per_block(b, excl) runs in the lane of every block b with
+// excl = the accepted points in the blocks before it.
+struct BlockScan {
+    int total;
+    int pick[4];
+};
+template <typename Summary, typename PerBlock>
+__device__ __forceinline__ BlockScan scan_blocks(Summary* S, int nblk, PerBlock&& per_block)
 {
-    const int pair = blockIdx.x, lane = threadIdx.x;
-    BlockSummary* S = summ + (long long)pair * nblk;
+    const int lane = threadIdx.x;
     int carry = 0;          // accepted points in blocks before the current chunk
     int pick[4] = {-1, -1, -1, -1};
     for (int b0 = 0; b0 < nblk; b0 += 64) {
@@ -490,7 +530,7 @@ __global__ __launch_bounds__(64) void k_fit(const float* __restrict__ next_pts, 
             if (lane >= d) incl += t;
         }
         const int excl = carry + incl - cnt;
-        if (fit_mode == MDX_FIT_RANSAC && b < nblk) S[b].pad_[0] = excl;   // k_ransac_compact's block offsets
+        if (b < nblk) per_block(b, excl);
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             // the block holding overall rank r (one lane at most), then broadcast its index
@@ -505,41 +545,74 @@ __global__ __launch_bounds__(64) void k_fit(const float* __restrict__ next_pts, 
         }
         carry += __shfl(incl, 63);
     }
-    // carry and pick are wave-uniform: the whole wave runs the fit, lane 0 writes the record
+    return {carry, {pick[0], pick[1], pick[2], pick[3]}};
+}
+
+// A pair's record, by one thread: its matrices and status.  num_vectors stays with the callers (the
+// scan's total; k_ransac_pick keeps k_fit's, k_set_fit_external has none).
+// Fitted: H, the matrix the warp samples with, status 0.
+__device__ __forceinline__ void write_fitted(PairFit& f, const double* H)
+{
+    for (int k = 0; k < 9; k++) f.H[k] = H[k];
+    dev_invert3x3(H, f.Hinv);
+    f.fit_status = 0;
+}
+// No fit (total < 4 accepted vectors): all-zero matrices (the warp then yields a zero mask), status 1 / 2.
+__device__ __forceinline__ void write_no_fit(PairFit& f, int total)
+{
+    for (int k = 0; k < 9; k++) { f.H[k] = 0.0; f.Hinv[k] = 0.0; }
+    f.fit_status = total == 0 ? 1 : 2;
+}
+
+// ------------------------------------------------------------------ A6 + A7: classify, first-4 fit
+__global__ __launch_bounds__(256) void k_classify(const float* __restrict__ next_pts, const uint8_t* __restrict__ status,
+                                                  int npts, int ny, int gy0, int gy1, int pixel_step, double mvs,
+                                                  double* __restrict__ vectors, BlockSummary* __restrict__ summ)
+{
+    const int pair = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+    __shared__ int s_wcnt[4];
+    const int i = blk * 256 + tid;
+    bool acc = false;
+    const int gyi = i % ny;
+    if (i < npts && gyi >= gy0 && gyi < gy1) {   // grid rows of the band (all rows: the full path)
+        const PointFlow p = classify_point(next_pts, status, (long long)pair * npts + i, i, ny, pixel_step, mvs);
+        acc = p.accepted;
+        if (vectors) reinterpret_cast<double4*>(vectors)[(long long)pair * npts + i] = p.vec;
+    }
+    const int rank = block_rank(acc, s_wcnt);
+    BlockSummary& S = summ[(long long)pair * gridDim.x + blk];
+    if (acc && rank < 4) S.first[rank] = i;
+    if (tid == 0) S.count = block_total(s_wcnt);
+}
+
+__global__ __launch_bounds__(64) void k_fit(const float* __restrict__ next_pts, int npts, int ny, int pixel_step,
+                                            BlockSummary* __restrict__ summ, int nblk, PairFit* __restrict__ fits,
+                                            int fit_mode, const double* __restrict__ H_ext)
+{
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    BlockSummary* S = summ + (long long)pair * nblk;
+    const BlockScan scan = scan_blocks(S, nblk, [&](int b, int excl) {
+        if (fit_mode == MDX_FIT_RANSAC) S[b].ransac_off = excl;   // k_ransac_compact's block offsets
+    });
+    // the scan's result is wave-uniform: the whole wave runs the fit, lane 0 writes the record
     __shared__ double fw[kFitWaveDoubles];
     PairFit& f = fits[pair];
-    const int total = carry;
+    const int total = scan.total;
     if (fit_mode != MDX_FIT_EXTERNAL && fit_mode != MDX_FIT_RANSAC && total >= 4) {
         float src[8], dst[8];
-        for (int r = 0; r < 4; r++) {
-            const int i = pick[r];
-            src[2 * r] = (float)((i / ny) * pixel_step);
-            src[2 * r + 1] = (float)((i % ny) * pixel_step);
-            const float2 e = reinterpret_cast<const float2*>(next_pts)[(long long)pair * npts + i];
-            dst[2 * r] = e.x;
-            dst[2 * r + 1] = e.y;
-        }
+        gather4(next_pts, (long long)pair * npts, ny, pixel_step, scan.pick, src, dst);
         double H[9];
         dev_perspective_fit_wave(src, dst, H, fw);
         if (lane != 0) return;
-        for (int k = 0; k < 9; k++) f.H[k] = H[k];
-        dev_invert3x3(H, f.Hinv);
-        f.fit_status = 0;
+        write_fitted(f, H);
         f.num_vectors = total;
         return;
     }
     if (lane != 0) return;
     f.num_vectors = total;
-    if (fit_mode == MDX_FIT_EXTERNAL) {
-        for (int k = 0; k < 9; k++) f.H[k] = H_ext[(long long)pair * 9 + k];
-        dev_invert3x3(f.H, f.Hinv);
-        f.fit_status = 0;
-    } else if (fit_mode == MDX_FIT_RANSAC && total >= 4) {
-        f.fit_status = 0;                        // H / Hinv: k_ransac_pick
-    } else {
-        for (int k = 0; k < 9; k++) { f.H[k] = 0.0; f.Hinv[k] = 0.0; }
-        f.fit_status = total == 0 ? 1 : 2;
-    }
+    if (fit_mode == MDX_FIT_EXTERNAL) write_fitted(f, H_ext + (long long)pair * 9);
+    else if (fit_mode == MDX_FIT_RANSAC && total >= 4) f.fit_status = 0;   // H / Hinv: k_ransac_pick
+    else write_no_fit(f, total);
 }
 
 // ------------------------------------------------------------------ MDX_FIT_RANSAC (not in the reference)
@@ -562,39 +635,18 @@ __device__ __forceinline__ uint64_t ransac_mix64(uint64_t z)
     return z ^ (z >> 31);
 }
 
-// the reference's acceptance test of grid point i (k_classify's)
-__device__ __forceinline__ bool ransac_accepted(const float* next_pts, const uint8_t* status, long long o, int i, int ny,
-                                                int pixel_step, double mvs, float& sx, float& sy, float2& e)
-{
-    sx = (float)((i / ny) * pixel_step);
-    sy = (float)((i % ny) * pixel_step);
-    e = reinterpret_cast<const float2*>(next_pts)[o];
-    if (!status[o]) return false;
-    const float xd = e.x - sx, yd = e.y - sy;
-    return fabs((double)fabsf(xd)) > mvs || fabs((double)fabsf(yd)) > mvs;
-}
-
 __global__ __launch_bounds__(256) void k_ransac_compact(const float* __restrict__ next_pts,
                                                         const uint8_t* __restrict__ status, int npts, int ny,
                                                         int pixel_step, double mvs,
                                                         const BlockSummary* __restrict__ summ, int* __restrict__ list)
 {
-    const int pair = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int pair = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
     __shared__ int s_wcnt[4];
     const int i = blk * 256 + tid;
-    bool acc = false;
-    if (i < npts) {
-        float sx, sy;
-        float2 e;
-        acc = ransac_accepted(next_pts, status, (long long)pair * npts + i, i, ny, pixel_step, mvs, sx, sy, e);
-    }
-    const unsigned long long bal = __ballot(acc);
-    if (lane == 0) s_wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0;
-    for (int w2 = 0; w2 < wave; w2++) before += s_wcnt[w2];
-    const int rank = before + __popcll(bal & ((1ull << lane) - 1ull));
-    const int off = summ[(long long)pair * gridDim.x + blk].pad_[0];
+    const bool acc = i < npts &&
+        classify_point(next_pts, status, (long long)pair * npts + i, i, ny, pixel_step, mvs).accepted;
+    const int rank = block_rank(acc, s_wcnt);
+    const int off = summ[(long long)pair * gridDim.x + blk].ransac_off;
     if (acc) list[(long long)pair * npts + off + rank] = i;
 }
 
@@ -623,15 +675,9 @@ __global__ __launch_bounds__(64) void k_ransac_hyp(const float* __restrict__ nex
             }
         }
     }
+    for (int j = 0; j < 4; j++) idx[j] = list[(long long)pair * npts + idx[j]];   // draw -> grid index
     float src[8], dst[8];
-    for (int j = 0; j < 4; j++) {
-        const int i = list[(long long)pair * npts + idx[j]];
-        src[2 * j] = (float)((i / ny) * pixel_step);
-        src[2 * j + 1] = (float)((i % ny) * pixel_step);
-        const float2 e = reinterpret_cast<const float2*>(next_pts)[(long long)pair * npts + i];
-        dst[2 * j] = e.x;
-        dst[2 * j + 1] = e.y;
-    }
+    gather4(next_pts, (long long)pair * npts, ny, pixel_step, idx, src, dst);
     double Hh[9];
     dev_perspective_fit_s<kRansacLanes>(src, dst, Hh, s_fw + lane);
     for (int k = 0; k < 9; k++) hyps[((long long)pair * iters + h) * 9 + k] = Hh[k];
@@ -652,10 +698,9 @@ __global__ __launch_bounds__(256) void k_ransac_score(const float* __restrict__ 
     bool acc = false;
     double sx = 0.0, sy = 0.0, dx = 0.0, dy = 0.0;
     if (i < npts) {
-        float fsx, fsy;
-        float2 e;
-        acc = ransac_accepted(next_pts, status, (long long)pair * npts + i, i, ny, pixel_step, mvs, fsx, fsy, e);
-        sx = fsx; sy = fsy; dx = e.x; dy = e.y;
+        const PointFlow p = classify_point(next_pts, status, (long long)pair * npts + i, i, ny, pixel_step, mvs);
+        acc = p.accepted;
+        sx = p.s.x; sy = p.s.y; dx = p.e.x; dy = p.e.y;
     }
     const double* Hp = hyps + (long long)pair * iters * 9;
     for (int h = 0; h < iters; h++) {
@@ -690,8 +735,7 @@ __global__ __launch_bounds__(64) void k_ransac_pick(const double* __restrict__ h
         if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
     }
     if (lane != 0) return;
-    for (int k = 0; k < 9; k++) f.H[k] = hyps[((long long)pair * iters + bh) * 9 + k];
-    dev_invert3x3(f.H, f.Hinv);
+    write_fitted(f, hyps + ((long long)pair * iters + bh) * 9);   // status is 0 already, the count k_fit's
 }
 
 // Row-band mode: the same block scan as k_fit, but the band's count and first four accepted
@@ -701,48 +745,17 @@ __global__ __launch_bounds__(64) void k_band_record(const float* __restrict__ ne
                                                     mdx_band_cand* __restrict__ cand)
 {
     const int pair = blockIdx.x, lane = threadIdx.x;
-    const BlockSummary* S = summ + (long long)pair * nblk;
-    int carry = 0;
-    int pick[4] = {-1, -1, -1, -1};
-    for (int b0 = 0; b0 < nblk; b0 += 64) {
-        const int b = b0 + lane;
-        const int cnt = b < nblk ? S[b].count : 0;
-        int incl = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        const int excl = carry + incl - cnt;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const bool here = cnt > 0 && r >= excl && r < excl + cnt;
-            const unsigned long long m = __ballot(here);
-            if (m) {
-                const int src = __ffsll((long long)m) - 1;
-                const int v = here ? S[b].first[r - excl] : 0;
-                const int got = __shfl(v, src);
-                if (pick[r] < 0) pick[r] = got;
-            }
-        }
-        carry += __shfl(incl, 63);
-    }
+    const BlockScan scan = scan_blocks(summ + (long long)pair * nblk, nblk, [](int, int) {});
     if (lane != 0) return;
     mdx_band_cand& c = cand[pair];
-    c.count = carry;
-    c.n = carry < 4 ? carry : 4;
+    const int n = scan.total < 4 ? scan.total : 4;
+    c.count = scan.total;
+    c.n = n;
     for (int r = 0; r < 4; r++) {
-        const int i = r < c.n ? pick[r] : -1;
+        const int i = r < n ? scan.pick[r] : -1;
         c.idx[r] = i;
-        if (i >= 0) {
-            c.src[2 * r] = (float)((i / ny) * pixel_step);
-            c.src[2 * r + 1] = (float)((i % ny) * pixel_step);
-            const float2 e = reinterpret_cast<const float2*>(next_pts)[(long long)pair * npts + i];
-            c.dst[2 * r] = e.x;
-            c.dst[2 * r + 1] = e.y;
-        } else {
-            c.src[2 * r] = c.src[2 * r + 1] = c.dst[2 * r] = c.dst[2 * r + 1] = 0.f;
-        }
+        if (i >= 0) gather_point(next_pts, (long long)pair * npts, ny, pixel_step, i, c.src + 2 * r, c.dst + 2 * r);
+        else c.src[2 * r] = c.src[2 * r + 1] = c.dst[2 * r] = c.dst[2 * r + 1] = 0.f;
     }
     c.pad_[0] = c.pad_[1] = 0;
 }
@@ -815,29 +828,22 @@ __global__ __launch_bounds__(64) void k_band_fit(const mdx_band_cand* __restrict
         double H[9];
         dev_perspective_fit_wave(bs, bd, H, fw);
         if (threadIdx.x != 0) return;
-        f.num_vectors = total;
-        for (int k = 0; k < 9; k++) f.H[k] = H[k];
-        dev_invert3x3(H, f.Hinv);
-        f.fit_status = 0;
+        write_fitted(f, H);
         band_source_rows(f.Hinv, w, h, y0, y1, f.src_y0, f.src_y1);
     } else {
         if (threadIdx.x != 0) return;
-        f.num_vectors = total;
-        for (int k = 0; k < 9; k++) { f.H[k] = 0.0; f.Hinv[k] = 0.0; }
-        f.fit_status = total == 0 ? 1 : 2;
+        write_no_fit(f, total);
         f.src_y0 = f.src_y1 = 0;   // no warp (zero mask)
     }
+    f.num_vectors = total;
 }
 
 __global__ void k_set_fit_external(const double* __restrict__ H_ext, PairFit* __restrict__ fits, int batch)
 {
     const int pair = blockIdx.x * blockDim.x + threadIdx.x;
     if (pair >= batch) return;
-    PairFit& f = fits[pair];
-    for (int k = 0; k < 9; k++) f.H[k] = H_ext[(long long)pair * 9 + k];
-    dev_invert3x3(f.H, f.Hinv);
-    f.num_vectors = 0;
-    f.fit_status = 0;
+    write_fitted(fits[pair], H_ext + (long long)pair * 9);
+    fits[pair].num_vectors = 0;
 }
 
 __global__ void k_export_fit(const PairFit* __restrict__ fits, int batch, double* H, int* num)
@@ -848,31 +854,29 @@ __global__ void k_export_fit(const PairFit* __restrict__ fits, int batch, double
     if (num) num[pair] = fits[pair].num_vectors;
 }
 
-hipError_t launch_classify_fit(hipStream_t s, int batch, const float* next_pts, const uint8_t* status, int npts,
-                               int ny, int gy0, int gy1, int pixel_step, double mvs, double* vectors, PairFit* fits,
-                               int fit_mode, const double* H_external, void* scratch, mdx_band_cand* cand,
-                               const RansacArgs* ransac)
+hipError_t launch_classify_fit(hipStream_t s, int batch, const FitArgs& a)
 {
-    const int nblk = (npts + 255) / 256;
-    BlockSummary* summ = reinterpret_cast<BlockSummary*>(scratch);
+    const int npts = a.npts, ny = a.ny, ps = a.pixel_step, nblk = classify_blocks(npts);
+    const double mvs = a.min_vector_size;
+    BlockSummary* summ = reinterpret_cast<BlockSummary*>(a.scratch);
     if (nblk > 0)
-        hipLaunchKernelGGL(k_classify, dim3(nblk, batch), dim3(256), 0, s, next_pts, status, npts, ny, gy0, gy1,
-                           pixel_step, mvs, vectors, summ);
-    if (cand)
-        hipLaunchKernelGGL(k_band_record, dim3(batch), dim3(64), 0, s, next_pts, npts, ny, pixel_step, summ, nblk, cand);
+        hipLaunchKernelGGL(k_classify, dim3(nblk, batch), dim3(256), 0, s, a.next_pts, a.status, npts, ny, a.gy0, a.gy1,
+                           ps, mvs, a.vectors, summ);
+    if (a.cand)
+        hipLaunchKernelGGL(k_band_record, dim3(batch), dim3(64), 0, s, a.next_pts, npts, ny, ps, summ, nblk, a.cand);
     else
-        hipLaunchKernelGGL(k_fit, dim3(batch), dim3(64), 0, s, next_pts, npts, ny, pixel_step, summ, nblk, fits,
-                           fit_mode, H_external);
-    if (fit_mode == MDX_FIT_RANSAC && !cand) {
-        if (!ransac || nblk == 0 || ransac->iters < 1 || ransac->iters > kRansacMaxIters) return hipErrorInvalidValue;
-        const RansacArgs& r = *ransac;
-        hipLaunchKernelGGL(k_ransac_compact, dim3(nblk, batch), dim3(256), 0, s, next_pts, status, npts, ny, pixel_step,
-                           mvs, summ, r.list);
+        hipLaunchKernelGGL(k_fit, dim3(batch), dim3(64), 0, s, a.next_pts, npts, ny, ps, summ, nblk, a.fits, a.fit_mode,
+                           a.H_external);
+    if (a.fit_mode == MDX_FIT_RANSAC && !a.cand) {
+        const RansacArgs& r = a.ransac;
+        if (!r.list || nblk == 0 || r.iters < 1 || r.iters > kRansacMaxIters) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_ransac_compact, dim3(nblk, batch), dim3(256), 0, s, a.next_pts, a.status, npts, ny, ps, mvs,
+                           summ, r.list);
         hipLaunchKernelGGL(k_ransac_hyp, dim3((r.iters + kRansacLanes - 1) / kRansacLanes, batch), dim3(64), 0, s,
-                           next_pts, npts, ny, pixel_step, r.list, fits, r.iters, r.seed, r.hyps, r.counts);
-        hipLaunchKernelGGL(k_ransac_score, dim3(nblk, batch), dim3(256), 0, s, next_pts, status, npts, ny, pixel_step,
-                           mvs, r.hyps, r.iters, r.thresh * r.thresh, fits, r.counts);
-        hipLaunchKernelGGL(k_ransac_pick, dim3(batch), dim3(64), 0, s, r.hyps, r.counts, r.iters, fits);
+                           a.next_pts, npts, ny, ps, r.list, a.fits, r.iters, r.seed, r.hyps, r.counts);
+        hipLaunchKernelGGL(k_ransac_score, dim3(nblk, batch), dim3(256), 0, s, a.next_pts, a.status, npts, ny, ps, mvs,
+                           r.hyps, r.iters, r.thresh * r.thresh, a.fits, r.counts);
+        hipLaunchKernelGGL(k_ransac_pick, dim3(batch), dim3(64), 0, s, r.hyps, r.counts, r.iters, a.fits);
     }
     return hipGetLastError();
 }

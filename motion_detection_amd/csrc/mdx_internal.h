@@ -298,22 +298,65 @@ struct RansacArgs {
     double* hyps;    // [batch][iters][9]
     int* counts;     // [batch][iters]
 };
-inline size_t ransac_scratch_bytes(int batch, int npts, int iters)
+// The RANSAC scratch, byte offsets: list from 0, hyps at the next 8-B boundary, counts behind them;
+// bytes: the three arrays and 256 that cover the gap.
+struct RansacScratch {
+    size_t hyps, counts, bytes;
+};
+inline RansacScratch ransac_scratch(int batch, int npts, int iters)
 {
-    return (size_t)batch * npts * 4 + (size_t)batch * iters * 72 + (size_t)batch * iters * 4 + 256;
+    const size_t list_b = (size_t)batch * npts * sizeof(int), hyps_b = (size_t)batch * iters * 9 * sizeof(double),
+                 counts_b = (size_t)batch * iters * sizeof(int);
+    RansacScratch L;
+    L.hyps = (list_b + 7) & ~(size_t)7;
+    L.counts = L.hyps + hyps_b;
+    L.bytes = list_b + hyps_b + counts_b + 256;
+    return L;
 }
-// Grid rows [gy0, gy1) only (a row band; others are neither written nor counted).  cand != null:
-// row-band mode -- the band's count and first four accepted points go to *cand (one record per
-// pair) instead of a fit.
-hipError_t launch_classify_fit(hipStream_t s, int batch, const float* next_pts, const uint8_t* status, int npts,
-                               int ny, int gy0, int gy1, int pixel_step, double min_vector_size, double* vectors,
-                               PairFit* fits, int fit_mode, const double* H_external, void* scratch,
-                               mdx_band_cand* cand, const RansacArgs* ransac = nullptr);
+inline size_t ransac_scratch_bytes(int batch, int npts, int iters) { return ransac_scratch(batch, npts, iters).bytes; }
+// the call's RansacArgs over ransac_scratch_bytes() of device memory at base
+inline RansacArgs ransac_args(void* base, int batch, int npts, const mdx_params& P)
+{
+    const RansacScratch L = ransac_scratch(batch, npts, P.ransac_iters);
+    uint8_t* b = static_cast<uint8_t*>(base);
+    return {P.ransac_iters, P.ransac_thresh, P.ransac_seed, reinterpret_cast<int*>(b),
+            reinterpret_cast<double*>(b + L.hyps), reinterpret_cast<int*>(b + L.counts)};
+}
+// k_classify's record of one 256-point block (mdx_fit.hip), in launch_classify_fit's scratch
+struct BlockSummary {
+    int count;        // accepted points of the block
+    int first[4];     // the first four of them (grid indices, block order); [count ..) not written
+    int ransac_off;   // MDX_FIT_RANSAC: accepted points in the pair's blocks before this one (k_fit,
+                      // for k_ransac_compact)
+    int pad_[2];
+};
+static_assert(sizeof(BlockSummary) == 32, "BlockSummary: eight ints, two records per 64-B line");
+inline int classify_blocks(int npts) { return (npts + 255) / 256; }
+// bytes of the scratch launch_classify_fit needs
+inline size_t classify_scratch_bytes(int batch, int npts)
+{
+    return (size_t)batch * classify_blocks(npts) * sizeof(BlockSummary);
+}
+// The classify + fit stage of `batch` pairs (mdx_fit.hip has the kernels' inventory).
+struct FitArgs {
+    const float* next_pts;      // [batch][npts][2] the LK's points
+    const uint8_t* status;      // [batch][npts]
+    int npts, ny, pixel_step;   // the grid (x-major, ny rows)
+    int gy0, gy1;               // grid rows classified (a row band; others are neither written nor counted)
+    double min_vector_size;
+    double* vectors;            // (may be null) [batch][npts][4] Vec4d
+    PairFit* fits;              // [batch]
+    int fit_mode;
+    const double* H_external;   // MDX_FIT_EXTERNAL: [batch][9]
+    void* scratch;              // classify_scratch_bytes(batch, npts)
+    mdx_band_cand* cand;        // non-null: row-band mode -- the band's count and first four accepted
+                                // points go to cand[pair] instead of a fit
+    RansacArgs ransac;          // MDX_FIT_RANSAC without cand: ransac_args(); otherwise unused
+};
+hipError_t launch_classify_fit(hipStream_t s, int batch, const FitArgs& a);
 // Merge nrec band records (first four accepted overall = four smallest indices) and fit
 hipError_t launch_band_fit(hipStream_t s, int nrec, const mdx_band_cand* cands, PairFit* fit, int w, int h, int y0,
                            int y1);
-// bytes of the scratch launch_classify_fit needs
-inline size_t classify_scratch_bytes(int batch, int npts) { return (size_t)batch * ((npts + 255) / 256) * 32; }
 // Row bands: frame-1 gray rows [fit->src_y0, fit->src_y1) into the padded level 0 of pyr1 (the
 // band's warp may read rows its own pyramid build skipped), except the rows [built0, built1) the
 // pyramid build wrote.  gray1_l0: level-0 core, pitch bytes.

@@ -301,29 +301,45 @@ static GrayPlane pyr_gray(uint8_t* slab, const Geometry& g)
     return {level0_core(slab, g), g.img_bytes, g.lv[0].pitch};
 }
 
-// The pipeline on device buffers.  d_np/d_st must be valid (LK writes them).
-// Row-band mode (cand != null, batch 1): LK and classification for grid rows [gy0, gy1) only, the
-// band's record to *cand, no fit and no mask.
-static int run_pipeline(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint8_t* d_img2, int w, int h, int stride,
-                        size_t frame_stride, int fmt, float* d_np, uint8_t* d_st, double* d_vec, uint8_t* d_mask,
-                        double* d_H, const double* d_Hext, int* d_num, int gy0 = 0, int gy1 = -1,
-                        mdx_band_cand* cand = nullptr, bool may_overlap = false)
+// The pipeline on device buffers: a call's frames, outputs and (row-band mode) band.
+struct PipelineArgs {
+    int batch;
+    const uint8_t *d_img1, *d_img2;   // [batch] frames, frame_stride bytes apart
+    int w, h, stride;
+    size_t frame_stride;
+    int fmt;
+    float* d_np;                      // [batch][npts][2]: must be valid (the LK writes them), as d_st
+    uint8_t* d_st;                    // [batch][npts]
+    double* d_vec = nullptr;          // the optional outputs: Vec4d, mask, H, num_vectors
+    uint8_t* d_mask = nullptr;
+    double* d_H = nullptr;
+    int* d_num = nullptr;
+    const double* d_Hext = nullptr;   // MDX_FIT_EXTERNAL
+    // Row-band mode (cand != null, batch 1): LK and classification for grid rows [gy0, gy1) only
+    // (gy1 < 0: every row), the band's record to *cand, no fit and no mask.
+    int gy0 = 0, gy1 = -1;
+    mdx_band_cand* cand = nullptr;
+    bool may_overlap = false;         // a device entry: call pipelining may run this call's front end early
+};
+static int run_pipeline(mdx_ctx* c, const PipelineArgs& A)
 {
     const mdx_params& P = c->prm;
+    const int batch = A.batch, w = A.w, h = A.h, stride = A.stride, fmt = A.fmt;
+    mdx_band_cand* const cand = A.cand;
     if (w <= 0 || h <= 0 || batch <= 0) return set_err(c, MDX_EINVAL, "bad frame size or batch");
     int rc = check_frame(c, nullptr, w, h, stride, fmt);
     if (rc != MDX_OK) return rc;
-    if (batch > 1 && frame_stride < (size_t)stride * h) return set_err(c, MDX_EINVAL, "frame_stride too small");
-    if (P.fit_mode == MDX_FIT_EXTERNAL && !d_Hext) return set_err(c, MDX_EINVAL, "fit_mode EXTERNAL needs H_external");
+    if (batch > 1 && A.frame_stride < (size_t)stride * h) return set_err(c, MDX_EINVAL, "frame_stride too small");
+    if (P.fit_mode == MDX_FIT_EXTERNAL && !A.d_Hext) return set_err(c, MDX_EINVAL, "fit_mode EXTERNAL needs H_external");
     HIP_OR_RETURN(c, hipSetDevice(c->device));
     // call pipelining: this call's pyramids go to the half the previous call did not use, and its
     // front end runs on the front stream once that half's last reader (two calls back) is done
-    const bool pipe = may_overlap && P.call_pipelining && c->aux && c->lk_impl == 2;
+    const bool pipe = A.may_overlap && P.call_pipelining && c->aux && c->lk_impl == 2;
     Geometry g = make_geometry(w, h, P.max_level);
     if ((rc = ensure_workspace(c, g, batch, pipe)) != MDX_OK) return rc;
     const int npts = mdx_grid_count(w, h, P.pixel_step);
     const int ny = (h + P.pixel_step - 1) / P.pixel_step;
-    if (gy1 < 0) gy1 = ny;
+    const int gy0 = A.gy0, gy1 = A.gy1 < 0 ? ny : A.gy1;
     const int nyb = gy1 - gy0;
     hipStream_t s = c->stream;
     uint8_t* pyr1 = c->pyr1.as<uint8_t>();
@@ -357,7 +373,8 @@ static int run_pipeline(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint
     // the aux stream start on them while the second frames' pyramids are built.  Stage "gray_pad"
     // = gray + pad + level 1 of the first frames (k_front), "pyrdown" = the rest of the pyramids.
     hipEvent_t prev_ready = nullptr;
-    const long long fs = (long long)frame_stride;
+    const uint8_t *d_img1 = A.d_img1, *d_img2 = A.d_img2;
+    const long long fs = (long long)A.frame_stride;
     // a row band (batch 1): the rows of the previous frame's pyramid its class planes read
     RowSpan rows[kMaxLevels];
     const RowSpan* prows = nullptr;
@@ -406,31 +423,25 @@ static int run_pipeline(mdx_ctx* c, int batch, const uint8_t* d_img1, const uint
         a.pyr2 = pyr2;
         a.der = der;
         a.nyg = nyb;
-        a.next_pts = d_np;
-        a.status = d_st;
+        a.next_pts = A.d_np;
+        a.status = A.d_st;
         if ((rc = run_lk(c, g, a, batch, w, h, gy0, gy1, false, prev_ready)) != MDX_OK) return rc;
     }
     mark(c, 4);
     if ((rc = ensure(c, c->csum, classify_scratch_bytes(batch, npts))) != MDX_OK) return rc;
-    RansacArgs ra{};
+    FitArgs fa = {A.d_np, A.d_st, npts, ny, P.pixel_step, gy0, gy1, P.min_vector_size, A.d_vec, fits, P.fit_mode,
+                  A.d_Hext, c->csum.p, cand, RansacArgs{}};
     if (P.fit_mode == MDX_FIT_RANSAC && !cand) {
         if ((rc = ensure(c, c->rsc, ransac_scratch_bytes(batch, npts, P.ransac_iters))) != MDX_OK) return rc;
-        uint8_t* base = c->rsc.as<uint8_t>();
-        ra.iters = P.ransac_iters;
-        ra.thresh = P.ransac_thresh;
-        ra.seed = P.ransac_seed;
-        ra.list = reinterpret_cast<int*>(base);
-        ra.hyps = reinterpret_cast<double*>(base + (((size_t)batch * npts * 4 + 7) & ~(size_t)7));
-        ra.counts = reinterpret_cast<int*>(reinterpret_cast<uint8_t*>(ra.hyps) + (size_t)batch * P.ransac_iters * 72);
+        fa.ransac = ransac_args(c->rsc.p, batch, npts, P);
     }
-    HIP_OR_RETURN(c, launch_classify_fit(s, batch, d_np, d_st, npts, ny, gy0, gy1, P.pixel_step, P.min_vector_size, d_vec,
-                                         fits, P.fit_mode, d_Hext, c->csum.p, cand, &ra));
+    HIP_OR_RETURN(c, launch_classify_fit(s, batch, fa));
     mark(c, 5);
-    if (d_mask && !cand) {
-        const WarpArgs wa = {pyr_gray(pyr1, g), pyr_gray(pyr2, g), w, h, fits, d_mask, (long long)w * h, P.thresh};
+    if (A.d_mask && !cand) {
+        const WarpArgs wa = {pyr_gray(pyr1, g), pyr_gray(pyr2, g), w, h, fits, A.d_mask, (long long)w * h, P.thresh};
         if ((rc = run_warp_diff(c, batch, wa)) != MDX_OK) return rc;
     }
-    if ((d_H || d_num) && !cand) HIP_OR_RETURN(c, launch_export_fit(s, batch, fits, d_H, d_num));
+    if ((A.d_H || A.d_num) && !cand) HIP_OR_RETURN(c, launch_export_fit(s, batch, fits, A.d_H, A.d_num));
     // (a row band: mdx_band_fit_warp_dev reads these pyramids, whichever half they are in, and
     // records their release again after its warp)
     if (pipe) HIP_OR_RETURN(c, hipEventRecord(c->pyr_free[half], s));
@@ -457,8 +468,10 @@ extern "C" int mdx_flow_warp_diff_batch_dev(mdx_ctx* c, int batch, const uint8_t
         if ((rc = ensure(c, c->bst, need)) != MDX_OK) return rc;
         d_status = c->bst.as<uint8_t>();
     }
-    return run_pipeline(c, batch, d_img1, d_img2, w, h, stride, frame_stride, fmt, d_next_pts, d_status, d_vectors,
-                        d_mask, d_H, d_H_external, d_num_vectors, 0, -1, nullptr, true);
+    PipelineArgs A = {batch, d_img1, d_img2, w, h, stride, frame_stride, fmt, d_next_pts, d_status,
+                      d_vectors, d_mask, d_H, d_num_vectors, d_H_external};
+    A.may_overlap = true;
+    return run_pipeline(c, A);
 }
 
 extern "C" int mdx_flow_warp_diff(mdx_ctx* c, const uint8_t* img1, const uint8_t* img2, int w, int h, int stride,
@@ -485,11 +498,11 @@ extern "C" int mdx_flow_warp_diff(mdx_ctx* c, const uint8_t* img1, const uint8_t
     HIP_OR_RETURN(c, hipMemcpyAsync(c->in1.p, img1, copy_bytes, hipMemcpyHostToDevice, s));
     HIP_OR_RETURN(c, hipMemcpyAsync(c->in2.p, img2, copy_bytes, hipMemcpyHostToDevice, s));
     if (H_external) HIP_OR_RETURN(c, hipMemcpyAsync(c->Hext.p, H_external, 72, hipMemcpyHostToDevice, s));
-    rc = run_pipeline(c, 1, c->in1.as<uint8_t>(), c->in2.as<uint8_t>(), w, h, stride, in_bytes, fmt, c->np.as<float>(),
-                      c->st.as<uint8_t>(), vectors ? c->vec.as<double>() : nullptr,
-                      mask ? c->mask.as<uint8_t>() : nullptr, c->H.as<double>(),
-                      H_external ? c->Hext.as<double>() : nullptr, c->num.as<int>());
-    if (rc != MDX_OK) return rc;
+    const PipelineArgs A = {1, c->in1.as<uint8_t>(), c->in2.as<uint8_t>(), w, h, stride, in_bytes, fmt, c->np.as<float>(),
+                            c->st.as<uint8_t>(), vectors ? c->vec.as<double>() : nullptr,
+                            mask ? c->mask.as<uint8_t>() : nullptr, c->H.as<double>(), c->num.as<int>(),
+                            H_external ? c->Hext.as<double>() : nullptr};
+    if ((rc = run_pipeline(c, A)) != MDX_OK) return rc;
     int num = 0;
     if (next_pts && npts > 0) HIP_OR_RETURN(c, hipMemcpyAsync(next_pts, c->np.p, (size_t)npts * 8, hipMemcpyDeviceToHost, s));
     if (status && npts > 0) HIP_OR_RETURN(c, hipMemcpyAsync(status, c->st.p, (size_t)npts, hipMemcpyDeviceToHost, s));
@@ -551,8 +564,12 @@ extern "C" int mdx_band_flow_dev(mdx_ctx* c, const uint8_t* d_img1, const uint8_
     // grid rows whose y = gy*ps lies in [y0, y1)
     const int gy0 = (y0 + ps - 1) / ps, gy1 = (y1 + ps - 1) / ps;
     c->band_w = c->band_h = 0;
-    const int rc = run_pipeline(c, 1, d_img1, d_img2, w, h, stride, (size_t)stride * h, fmt, d_next_pts, d_status,
-                                d_vectors, nullptr, nullptr, nullptr, nullptr, gy0, gy1, d_cand, true);
+    PipelineArgs A = {1, d_img1, d_img2, w, h, stride, (size_t)stride * h, fmt, d_next_pts, d_status, d_vectors};
+    A.gy0 = gy0;
+    A.gy1 = gy1;
+    A.cand = d_cand;
+    A.may_overlap = true;
+    const int rc = run_pipeline(c, A);
     if (rc == MDX_OK) {
         c->band_w = w;
         c->band_h = h;
