@@ -89,6 +89,7 @@ static LkTuning read_tuning()
     t.lk_flow = num("MDX_LK_FLOW", 1) != 0;
     t.ol_reg = num("MDX_OL_REG", 1) != 0;
     t.lk_cap = std::min(std::max(num("MDX_LK_CAP", 75), 10), 100);
+    t.lk_fma = num("MDX_LK_FMA", 1) != 0;
     t.spin_max = num("MDX_LK_SPIN_MAX", kLkSpinDefault);
     return t;
 }
@@ -280,7 +281,9 @@ extern "C" int mdx_stage_ms(mdx_ctx* c, int stage, float* ms)
     return MDX_OK;
 }
 
-// Test hook: copy an internal LK v2 buffer to the host (0 = A sums, 1 = per-level trace).
+// Test hook: copy an internal LK v2 buffer to the host (0 = A sums, 1 = per-level trace, 6 = MDX_LK_DEBUG
+// contexts only: the last call's k_lk_iter wave-iterations by row body, uint32 [kMaxLevels][2] =
+// (exact, fused) per level).
 #if MDX_WARP_STAMP
 namespace mdx { hipError_t debug_warp_stamps(void* dst, size_t bytes); }
 #endif
@@ -295,7 +298,7 @@ extern "C" int mdx_debug_copy(mdx_ctx* c, int which, void* dst, size_t bytes)
     }
 #endif
     DevBuf& b = which == 0 ? c->Abuf : which == 1 ? c->dbg : which == 2 ? c->pyr1 : which == 3 ? c->pyr2
-              : which == 4 ? c->der : c->cls;
+              : which == 4 ? c->der : which == 6 ? c->lkcnt : c->cls;
     if (!b.p) return set_err(c, MDX_EINVAL, "debug buffer %d unavailable", which);
     HIP_OR_RETURN(c, hipStreamSynchronize(c->stream));
     // pyramids: the half the last pair call wrote

@@ -56,7 +56,10 @@ struct LkTuning {
     // class planes and A sums pace the level hand-offs (round 6, profiles/r06_ab_lk_w5_cap.txt: 60 -3%,
     // 70 / 80 / 85 within 1%, 75 best and steadiest, 95 -1.2%)
     int lk_cap = 75;
-    int spin_max = mdx::kLkSpinDefault;   // MDX_LK_SPIN_MAX (debug: < 0 injects timeouts)
+    // MDX_LK_FMA=0: k_lk_iter never takes its fused row body (A/B runs, tests); the certificate is
+    // still computed and loaded
+    bool lk_fma = true;
+    int spin_max = mdx::kLkSpinDefault;  // MDX_LK_SPIN_MAX (debug: < 0 injects timeouts)
     bool ol_reg = true;       // MDX_OL_REG=0: findOutliers re-reads its values on every pass at every size
 };
 
@@ -106,6 +109,7 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf bnp, bst;                         // LK outputs the batched caller did not ask for
     DevBuf cls, Abuf, ctab;                  // LK v2: class planes, A sums, residue tables
     DevBuf dbg;                              // LK v2 per-level trace (MDX_LK_DEBUG=1)
+    DevBuf lkcnt;                            // MDX_LK_DEBUG=1: the last call's k_lk_iter wave-iterations by row body
     DevBuf csum;                             // classify: per-block summaries
     DevBuf tin, tcur, tnp, tst, ttraj, tnum, tflag;   // trajectory tracking (ttraj: the four outputs, one block)
     DevBuf straj, sdata, sq, scnt, scols, sres, sout, sbest;      // subspace RANSAC

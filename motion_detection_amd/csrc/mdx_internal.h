@@ -146,6 +146,10 @@ struct LkArgs {
     int flow_cap;            // dataflow: percent of the resident waves one iteration launch takes
     float4* dbg;             // optional [batch][nlev][npts] (npx, npy, iters, status) at level end
     int dbg_pt;              // point whose per-iteration values are appended after dbg (pair 0)
+    int fma;                 // LK v2: 1: k_lk_iter may take the fused row body where every iterating
+                             // point of the wave is certified (MDX_LK_FMA, mdx_lk.hip); 0: never
+    uint32_t* body_cnt;      // optional (MDX_LK_DEBUG) [kMaxLevels][2] wave-iterations of k_lk_iter by
+                             // row body: [level][0] exact, [level][1] fused
 };
 
 // LK counters (queue heads per level and XCD, dataflow retire counts per level and pair): one per
@@ -267,7 +271,8 @@ struct LkLaunch {
     hipEvent_t* redo_ev = nullptr;   // dataflow fallback: kMaxLevels events
     uint8_t* cls = nullptr;          // class planes
     float4* Ab = nullptr;            // [nlev][batch][npts] per-point (A11, A12, A22, 1/D)
-    int* qctr = nullptr;             // [batch][kMaxLevels][8] (x kCtrPad) queue heads
+    uint8_t* cert = nullptr;         // [nlev][batch][npts] per-point product certificate (mdx_lk.hip), written with Ab
+    int* qctr = nullptr;            // [batch][kMaxLevels][8] (x kCtrPad) queue heads
     int* done = nullptr;             // dataflow: kMaxLevels x batch + kLkFlagInts counters
     // (may be null: calls do not overlap) [kMaxLevels] events, re-recorded after each level's
     // iteration launch; the aux stream waits for the previous call's before rewriting that level's

@@ -494,11 +494,36 @@ __device__ __forceinline__ float4 lk_A_result(f2 sd, float s12, bool ok, float m
     return make_float4(A11, A12, A22, Dinv);
 }
 
+// The product certificate of a point at a level: every (Ix, Iy) of its 40x40 class-plane window has
+// magnitude <= kLkCertMax.  k_lk_iter multiplies these by jd = J*32 - I*32, |jd| <= 32 * 255 = 8160,
+// so every product of a certified window is at most 2056 * 8160 = 16 776 960 < 2^24: exact in float,
+// and fma(f, fd, acc) has the bits of acc + rn(f * fd), the reference's rounded product then add.
+// The A kernels, which convert every window element anyway, keep the running maximum magnitude (one
+// v_max3_f32 per element) and store the flag beside the point's A sums; 0 ("not certified") is always
+// a sound answer.
+constexpr float kLkCertMax = 2056.f;
+static_assert(kLkCertMax * 8160.f < 16777216.f, "certified products are exact in float");
+__device__ __forceinline__ float lk_mag_max(float m, f2 f)
+{
+    return __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(f.x)), __builtin_fabsf(f.y));
+}
+// k_lk_iter's fused element: acc + f * fd in one rounding, whatever the build's contraction setting.
+// One v_pk_fma_f32; two v_fma_f32 measured slower (profiles/lk_fma_ab.txt), and two fmaf calls are
+// packed into the same v_pk_fma_f32 by the compiler anyway.
+__device__ __forceinline__ f2 lk_fma(f2 f, float fd, f2 acc) { return __builtin_elementwise_fma(f, f2{fd, fd}, acc); }
+// the quad's lanes' maxima -> the point's flag
+__device__ __forceinline__ uint8_t lk_cert_flag(float m)
+{
+    const float q = __builtin_fmaxf(__builtin_fmaxf(quad_bcast<0>(m), quad_bcast<1>(m)),
+                                    __builtin_fmaxf(quad_bcast<2>(m), quad_bcast<3>(m)));
+    return q <= kLkCertMax ? 1 : 0;
+}
+
 // ---- A pass.  grid: x -> wave (S static groups), y -> pair (XCD-remapped as one range).  The
 // chain reads are D only.
 template <int G, int UW>
 __global__ __launch_bounds__(64) void k_lk_A(LkArgs a, const uint8_t* __restrict__ cls, float4* __restrict__ Ab,
-                                             int* __restrict__ qctr, int level, int ngroups)
+                                             uint8_t* __restrict__ cert, int* __restrict__ qctr, int level, int ngroups)
 {
     using Sh = LkShape<G, UW>;
     constexpr int LPS = Sh::LPS, S = Sh::S, ND = Sh::ND;
@@ -528,7 +553,7 @@ __global__ __launch_bounds__(64) void k_lk_A(LkArgs a, const uint8_t* __restrict
 
     // lane k owns SSE lane k (columns 4g+k), rows in order; ((P0+P1)+P2)+P3 across the quad
     f2 sd = {0.f, 0.f};
-    float s12 = 0.f;
+    float s12 = 0.f, mag = 0.f;                                    // mag: the certificate's max(|Ix|, |Iy|)
     constexpr int PF = NB - 1;                                     // rows in flight ahead
     im.template dma<0>(uoff);
     im.template dma<1>(uoff);
@@ -553,10 +578,18 @@ __global__ __launch_bounds__(64) void k_lk_A(LkArgs a, const uint8_t* __restrict
             // exact in float: one fused multiply-add rounds exactly like the two operations
             sd = __builtin_elementwise_fma(f, f, sd);      // (Ix*Ix, Iy*Iy)
             s12 = __builtin_fmaf(f.x, f.y, s12);           // Ix*Iy
+            mag = lk_mag_max(mag, f);
         }
+        // an opaque use per row: a maximum may be reassociated freely, and without it the compiler
+        // gathered all 40 unrolled rows' elements first (256 VGPRs and scratch)
+        asm volatile("" : "+v"(mag));
     });
     const float4 r = lk_A_result(sd, s12, ok, a.min_eig);
-    if (q.valid && k == 0) Ab[(long long)pair * a.npts + q.gx * a.ny + q.gy] = r;
+    const uint8_t cf = lk_cert_flag(mag);
+    if (q.valid && k == 0) {
+        Ab[(long long)pair * a.npts + q.gx * a.ny + q.gy] = r;
+        cert[(long long)pair * a.npts + q.gx * a.ny + q.gy] = cf;
+    }
 }
 
 // ---- A pass per row strip.  Neighbouring grid rows of one residue class have windows that start
@@ -571,7 +604,7 @@ __global__ __launch_bounds__(64) void k_lk_A(LkArgs a, const uint8_t* __restrict
 // grid: x -> (strip, column-group wave), y -> pair (XCD-remapped as one range)
 template <int G, int UW, int NW>
 __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __restrict__ cls, float4* __restrict__ Ab,
-                                                  int* __restrict__ qctr, int level, int ncg)
+                                                  uint8_t* __restrict__ cert, int* __restrict__ qctr, int level, int ncg)
 {
     using Sh = LkShape<G, UW>;
     constexpr int LPS = Sh::LPS, S = Sh::S, ND = Sh::ND;
@@ -618,9 +651,17 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
     const int el = 2 * (slot * UW + off + k);
 
     // window slots: rin[s] = rows the slot's window has summed (-1: idle), jw[s] = its strip row
+    // magp: the windows' certificate maxima (integers <= 4080), two slots per register, fed once per
+    // plane row with the row's maximum by v_pk_max_u16.  Every slot is fed, idle ones too: a slot's
+    // half is cleared when its next window starts.
+    static_assert(NW % 2 == 0, "slot pairs");
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     f2 sd[NW];
     float s12[NW];
+    us2 magp[NW / 2];
     int rin[NW], jw[NW];
+#pragma unroll
+    for (int s = 0; s < NW / 2; s++) magp[s] = us2{0, 0};
 #pragma unroll
     for (int s = 0; s < NW; s++) {
         sd[s] = f2{0.f, 0.f};
@@ -629,12 +670,16 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
         jw[s] = 0;
     }
     int nextj = 0;
-    auto finish = [&](int j, f2 sdv, float s12v) {
+    auto finish = [&](int j, f2 sdv, float s12v, float magv) {
         const int gy = yo[r0 + j];
         const int ipy = lk_win_origin(gy, a.pixel_step, level);
         const bool ok = valid && !(ipx < -kWin || ipx >= L.w || ipy < -kWin || ipy >= L.h);
         const float4 r = lk_A_result(sdv, s12v, ok, a.min_eig);
-        if (valid && k == 0) Ab[(long long)pair * a.npts + gx * a.ny + gy] = r;
+        const uint8_t cf = lk_cert_flag(magv);
+        if (valid && k == 0) {
+            Ab[(long long)pair * a.npts + gx * a.ny + gy] = r;
+            cert[(long long)pair * a.npts + gx * a.ny + gy] = cf;
+        }
     };
     // one plane row: its elements (loaded once), then every window that contains it
     auto row = [&](int t, auto bc) {
@@ -651,18 +696,25 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
         f2 f[10];
 #pragma unroll
         for (int gi = 0; gi < 10; gi++) f[gi] = f2{(float)(int16_t)dw[gi], (float)((int)dw[gi] >> 16)};
+        float rmag = 0.f;                       // this lane's elements of the row
+#pragma unroll
+        for (int gi = 0; gi < 10; gi++) rmag = lk_mag_max(rmag, f[gi]);
         if (nextj < nr && t == nextj * asp) {   // window nextj starts here (slot nextj % NW is free)
             static_for<0, NW>([&](auto sc) {
                 constexpr int s = decltype(sc)::value;
                 if (nextj % NW == s) {
                     sd[s] = f2{0.f, 0.f};
                     s12[s] = 0.f;
+                    magp[s / 2][s & 1] = 0;
                     rin[s] = 0;
                     jw[s] = nextj;
                 }
             });
             nextj++;
         }
+        const unsigned short ri = (unsigned short)(uint32_t)rmag;   // exact: a maximum of converted int16
+#pragma unroll
+        for (int s = 0; s < NW / 2; s++) magp[s] = __builtin_elementwise_max(magp[s], us2{ri, ri});
         static_for<0, NW>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
             if (rin[s] >= 0) {
@@ -673,7 +725,7 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
                     s12[s] = __builtin_fmaf(f[gi].x, f[gi].y, s12[s]);
                 }
                 if (++rin[s] == kWin) {
-                    finish(jw[s], sd[s], s12[s]);
+                    finish(jw[s], sd[s], s12[s], (float)magp[s / 2][s & 1]);
                     rin[s] = -1;
                 }
             }
@@ -710,8 +762,8 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
 // one pair, so a chain element is one 2-cycle LDS access (it was two read2_b32 halves).
 template <int G, int UW, bool DF>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWavesPerEU, 8))) void k_lk_iter(
-    LkArgs a, const uint8_t* __restrict__ cls, const float4* __restrict__ Ab, int* __restrict__ qctr, int level,
-    int ngroups, int batch)
+    LkArgs a, const uint8_t* __restrict__ cls, const float4* __restrict__ Ab, const uint8_t* __restrict__ cert,
+    int* __restrict__ qctr, int level, int ngroups, int batch)
 {
     using Sh = LkShape<G, UW>;
     constexpr int LPS = Sh::LPS, S = Sh::S, ND = Sh::ND;
@@ -787,7 +839,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
     float A11 = 0.f, A12 = 0.f, A22 = 0.f, Dinv = 0.f;
     float nx = 0.f, ny = 0.f, npx = 0.f, npy = 0.f, pdx = 0.f, pdy = 0.f;
     bool act = false, gave_up = false;
+    bool certd = false;                                           // the point's product certificate (lk_cert_flag)
     int status = 1, iters = 0;
+    uint32_t n_exact = 0, n_fused = 0;                            // debug: this wave's iterations by row body
 
     auto retire = [&]() {
         if (level == 0 && q.valid && status) {
@@ -843,6 +897,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
                     A12 = Av.y;
                     A22 = Av.z;
                     Dinv = Av.w;
+                    certd = q.valid && cert[po] != 0;
                     if (level == a.maxl) {
                         npx = (float)(q.gx * a.pixel_step) * scale;
                         npy = (float)(q.gy * a.pixel_step) * scale;
@@ -992,7 +1047,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
         // row y (in buffer R = y % 2): wait until union row y and J row y+1 have landed, fetch
         // union row y+1 and J row y+2 into the buffers rows y-1 / y (already summed) used, and sum
         // the row.  An opaque use of acc pins each row's arithmetic before the next row's wait.
-        auto row = [&](int y, auto Rc, s2 (&up)[10], s2 (&lo)[10]) {
+        // Two bodies (Fc): the exact one rounds each product to float and then adds, as the
+        // reference does; the fused one is one fma per element, the same bits wherever the product
+        // is exact -- every product of a certified window (kLkCertMax).
+        auto row = [&](auto Fc, int y, auto Rc, s2 (&up)[10], s2 (&lo)[10]) {
+            constexpr bool FUSED = decltype(Fc)::value;
             constexpr int R = decltype(Rc)::value;
             if (y) lk_vmcnt0();
             if (y + 1 < kWin) dma_union(std::integral_constant<int, 1 - R>{}, y + 1);
@@ -1014,14 +1073,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
                                                       false) >> 9;
                 const float fd = (float)jd;
                 const f2 f = {(float)(int16_t)dc.x, (float)((int)dc.x >> 16)};
-                acc = acc + f * fd;
+                if constexpr (FUSED) acc = lk_fma(f, fd, acc);
+                else acc = acc + f * fd;
             }
             asm volatile("" : "+v"(acc));
         };
+        // The fused body runs iff every iterating point of the wave is certified: lanes that are
+        // not iterating drop their sums, so they never veto, and a wave moves to the fused body once
+        // its uncertified points have converged.
+        const bool fused = a.fma && __all(!act || certd);
+        if (a.body_cnt) (fused ? n_fused : n_exact)++;
+        if (fused) {
 #pragma unroll 1
-        for (int y = 0; y < kWin; y += 2) {
-            row(y, I0{}, pa, pb);
-            row(y + 1, I1{}, pb, pa);
+            for (int y = 0; y < kWin; y += 2) {
+                row(std::true_type{}, y, I0{}, pa, pb);
+                row(std::true_type{}, y + 1, I1{}, pb, pa);
+            }
+        } else {
+#pragma unroll 1
+            for (int y = 0; y < kWin; y += 2) {
+                row(std::false_type{}, y, I0{}, pa, pb);
+                row(std::false_type{}, y + 1, I1{}, pb, pa);
+            }
         }
         if (!act) acc = f2{0.f, 0.f};
         // b = (P0+P2) + (P1+P3) across the quad; inactive quads compute values they ignore
@@ -1057,6 +1130,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
                 retire();
             }
         }
+    }
+    if (a.body_cnt && lane == 0) {                          // debug mode only: iterations by row body
+        atomicAdd(a.body_cnt + 2 * level, n_exact);
+        atomicAdd(a.body_cnt + 2 * level + 1, n_fused);
     }
     if (a.dbg && lane == 0 && blockIdx.x < kLkDbgWaves) {   // debug mode only: wave lifetimes
         uint4* st = reinterpret_cast<uint4*>(a.dbg + (long long)batch * a.g.nlev * a.npts + kLkDbgStampOff) +
@@ -1128,30 +1205,32 @@ static int lk_iter_resident()
 static int lk_groups(const ClassPlan& plan, int l, int nyg) { return (plan.lv[l].nxp / plan.lv[l].G) * nyg; }
 
 template <int G, int UW>
-static void launch_A(hipStream_t s, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab, int* qctr, int l)
+static void launch_A(hipStream_t s, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab, uint8_t* cert, int* qctr,
+                     int l)
 {
     constexpr int S = LkShape<G, UW>::S;
     const int ngroups = lk_groups(a.plan, l, a.nyg);
     const dim3 grid((ngroups + S - 1) / S, batch);
-    hipLaunchKernelGGL((k_lk_A<G, UW>), grid, dim3(64), 0, s, a, cls, Ab, qctr, l, ngroups);
+    hipLaunchKernelGGL((k_lk_A<G, UW>), grid, dim3(64), 0, s, a, cls, Ab, cert, qctr, l, ngroups);
 }
 
 template <int G, int UW>
-static void launch_A_rows(hipStream_t s, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab, int* qctr, int l)
+static void launch_A_rows(hipStream_t s, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab, uint8_t* cert,
+                          int* qctr, int l)
 {
     constexpr int S = LkShape<G, UW>::S;
     const ClassLevel& C = a.plan.lv[l];
     const int ncg = C.nxp / G;
     const dim3 grid(((ncg + S - 1) / S) * C.nstrip, batch);
     if (C.asp >= 10)
-        hipLaunchKernelGGL((k_lk_A_rows<G, UW, 4>), grid, dim3(64), 0, s, a, cls, Ab, qctr, l, ncg);
+        hipLaunchKernelGGL((k_lk_A_rows<G, UW, 4>), grid, dim3(64), 0, s, a, cls, Ab, cert, qctr, l, ncg);
     else
-        hipLaunchKernelGGL((k_lk_A_rows<G, UW, 8>), grid, dim3(64), 0, s, a, cls, Ab, qctr, l, ncg);
+        hipLaunchKernelGGL((k_lk_A_rows<G, UW, 8>), grid, dim3(64), 0, s, a, cls, Ab, cert, qctr, l, ncg);
 }
 
 template <int G, int UW>
-static void launch_iter(hipStream_t s, int batch, const LkArgs& a, const uint8_t* cls, const float4* Ab, int* qctr,
-                        int l)
+static void launch_iter(hipStream_t s, int batch, const LkArgs& a, const uint8_t* cls, const float4* Ab,
+                        const uint8_t* cert, int* qctr, int l)
 {
     constexpr int S = LkShape<G, UW>::S;
     const int ngroups = lk_groups(a.plan, l, a.nyg);
@@ -1165,22 +1244,24 @@ static void launch_iter(hipStream_t s, int batch, const LkArgs& a, const uint8_t
     if (a.done) res = res * std::min(std::max(a.flow_cap, 10), 100) / 100;   // the context's (MDX_LK_CAP)
     int W = std::max(8, std::min((need + 7) / 8, res / 8) * 8);
     if (a.redo) W = std::max(8, std::min(W, kLkRedoWaves));
-    if (df) hipLaunchKernelGGL((k_lk_iter<G, UW, true>), dim3(W), dim3(64), 0, s, a, cls, Ab, qctr, l, ngroups, batch);
-    else hipLaunchKernelGGL((k_lk_iter<G, UW, false>), dim3(W), dim3(64), 0, s, a, cls, Ab, qctr, l, ngroups, batch);
+    if (df)
+        hipLaunchKernelGGL((k_lk_iter<G, UW, true>), dim3(W), dim3(64), 0, s, a, cls, Ab, cert, qctr, l, ngroups, batch);
+    else
+        hipLaunchKernelGGL((k_lk_iter<G, UW, false>), dim3(W), dim3(64), 0, s, a, cls, Ab, cert, qctr, l, ngroups, batch);
 }
 
 // One level's A sums (iter false: per row strip where the plan allows, else per group) or its
 // iteration launch, in the level's (G, UW) shape.  false: the plan names a shape that is not built.
-static bool launch_level(bool iter, hipStream_t st, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab, int* qctr,
-                         int l)
+static bool launch_level(bool iter, hipStream_t st, int batch, const LkArgs& a, const uint8_t* cls, float4* Ab,
+                         uint8_t* cert, int* qctr, int l)
 {
     const ClassLevel& C = a.plan.lv[l];
     switch (C.G * 1000 + C.UW) {
 #define LK_CASE(g, uw)                                                   \
     case g * 1000 + uw:                                                  \
-        if (iter) launch_iter<g, uw>(st, batch, a, cls, Ab, qctr, l);    \
-        else if (C.asp) launch_A_rows<g, uw>(st, batch, a, cls, Ab, qctr, l); \
-        else launch_A<g, uw>(st, batch, a, cls, Ab, qctr, l);            \
+        if (iter) launch_iter<g, uw>(st, batch, a, cls, Ab, cert, qctr, l);    \
+        else if (C.asp) launch_A_rows<g, uw>(st, batch, a, cls, Ab, cert, qctr, l); \
+        else launch_A<g, uw>(st, batch, a, cls, Ab, cert, qctr, l);            \
         return true;
         LK_SHAPES
 #undef LK_CASE
@@ -1226,7 +1307,8 @@ static hipError_t lk_enqueue_planes(const LkLaunch& L, hipStream_t sa, int batch
             hipLaunchKernelGGL(k_lk_class, grid, dim3(64), 0, sa, b.pyr1, b.der, bcls, ca);
         }
         float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
-        if (!launch_level(false, sa, nb, b, bcls, bA, bq, l)) return hipErrorInvalidValue;
+        uint8_t* bC = L.cert + ((long long)l * batch + p) * a.npts;
+        if (!launch_level(false, sa, nb, b, bcls, bA, bC, bq, l)) return hipErrorInvalidValue;
         if (L.aux) {
             if (hipError_t e = hipEventRecord(L.ev[l], sa)) return e;
         }
@@ -1276,7 +1358,8 @@ static hipError_t lk_enqueue_iters(const LkLaunch& L, int batch, int p, int nb, 
                                a.spin_max, lflags + (kLkFlagGiveup + l) * kCtrPad);
         }
         float4* bA = L.Ab + ((long long)l * batch + p) * a.npts;
-        if (!launch_level(true, st, nb, bl, bcls, bA, bq, l)) return hipErrorInvalidValue;
+        uint8_t* bC = L.cert + ((long long)l * batch + p) * a.npts;
+        if (!launch_level(true, st, nb, bl, bcls, bA, bC, bq, l)) return hipErrorInvalidValue;
         if (flow) {
             // the level's recompute, behind it on its stream and behind the coarser level's
             // (launch and recompute): exits at once unless the level gave up or the coarser
@@ -1288,7 +1371,8 @@ static hipError_t lk_enqueue_iters(const LkLaunch& L, int batch, int p, int nb, 
                 br.dep_groups = 0;
                 br.redo = 1;
                 br.dbg = nullptr;
-                if (!launch_level(true, st, nb, br, bcls, bA, bq, l)) return hipErrorInvalidValue;
+                br.body_cnt = nullptr;
+                if (!launch_level(true, st, nb, br, bcls, bA, bC, bq, l)) return hipErrorInvalidValue;
             }
             if (hipError_t e = hipEventRecord(L.redo_ev[l], st)) return e;
         }
@@ -1326,7 +1410,7 @@ hipError_t launch_lk_v2(const LkLaunch& L, int batch, const LkArgs& a)
         b.next_pts = a.next_pts + (long long)p * a.npts * 2;
         b.carry = a.carry ? a.carry + (long long)p * a.npts * 2 : nullptr;   // carry_lstride: whole batch
         b.status = a.status + (long long)p * a.npts;
-        if (p) b.dbg = nullptr;   // the trace covers the first sub-batch
+        if (p) b.dbg = nullptr;   // the trace covers the first sub-batch (the body counts every one)
         uint8_t* bcls = L.cls + (long long)p * a.plan.bytes_per_pair;
         int* bq = L.qctr + si * kMaxLevels * 8 * kCtrPad;
         if (hipError_t e = lk_enqueue_planes(L, sa, batch, p, nb, a, b, bcls, bq)) return e;

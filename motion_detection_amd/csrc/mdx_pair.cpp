@@ -187,9 +187,10 @@ static inline void mark(mdx_ctx* c, int i, hipStream_t st = nullptr)
 // from 0), the queue heads ([sub-batch][level][XCD] counters), the dataflow counters and flags
 // ([level][pair] + kLkFlagInts counters) and the points carried between levels (per level a
 // [pair][point] float2 array of carry_level bytes, a multiple of 128: with the counter regions whole
-// 128-B lines and npts a multiple of 16 the arrays start on 128-B lines, which the dataflow requires).
+// 128-B lines and npts a multiple of 16 the arrays start on 128-B lines, which the dataflow requires),
+// then the product certificates ([level][pair][point] bytes, written and read with the A sums).
 struct LkScratch {
-    size_t qctr, done, carry, carry_level, bytes;
+    size_t qctr, done, carry, carry_level, cert, bytes;
 };
 static LkScratch lk_scratch(int nlev, int batch, int npts)
 {
@@ -198,7 +199,8 @@ static LkScratch lk_scratch(int nlev, int batch, int npts)
     s.done = s.qctr + (size_t)batch * kMaxLevels * 8 * kCtrPad * sizeof(int);
     s.carry = s.done + ((size_t)kMaxLevels * batch + kLkFlagInts) * kCtrPad * sizeof(int);
     s.carry_level = ((size_t)batch * npts * 8 + 127) / 128 * 128;
-    s.bytes = s.carry + s.carry_level * nlev;
+    s.cert = s.carry + s.carry_level * nlev;
+    s.bytes = s.cert + (size_t)nlev * batch * npts;
     return s;
 }
 
@@ -228,6 +230,7 @@ int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int 
     a.err = c->errw.as<int>();
     a.spin_max = c->spin_max;
     a.flow_cap = c->lk_cap;
+    a.fma = c->lk_fma ? 1 : 0;
     a.cmap = c->ctab.as<int16_t>();
     a.rlist = c->ctab.as<int16_t>() + kMaxLevels * 2 * 128;
     a.ord = c->ctab.as<int16_t>() + 2 * kMaxLevels * 2 * 128;
@@ -239,6 +242,10 @@ int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int 
         a.dbg = c->dbg.as<float4>();
         const char* e = std::getenv("MDX_LK_DEBUG_PT");
         a.dbg_pt = e ? std::atoi(e) : -1;
+        // this call's wave-iterations by row body (mdx_debug_copy selector 6)
+        if ((rc = ensure(c, c->lkcnt, kMaxLevels * 2 * sizeof(uint32_t))) != MDX_OK) return rc;
+        HIP_OR_RETURN(c, hipMemsetAsync(c->lkcnt.p, 0, kMaxLevels * 2 * sizeof(uint32_t), s));
+        a.body_cnt = c->lkcnt.as<uint32_t>();
     }
     const LkScratch sc = lk_scratch(g.nlev, batch, npts);
     if ((rc = ensure(c, c->Abuf, sc.bytes)) != MDX_OK) return rc;
@@ -256,6 +263,7 @@ int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int 
     LkLaunch L = c->lk;
     L.cls = c->cls.as<uint8_t>();
     L.Ab = c->Abuf.as<float4>();
+    L.cert = base + sc.cert;
     L.qctr = reinterpret_cast<int*>(base + sc.qctr);
     L.done = reinterpret_cast<int*>(base + sc.done);
     L.lvl_done = c->prm.call_pipelining ? c->lvl_done : nullptr;
