@@ -86,21 +86,24 @@ bool MotionDetectionNode::image_callback(const Image& msg, FrameResult* out)
         raw_images_.pop_front();
         image_received_ = true;
     }
-    if (p_.live_path) {
+    if (p_.ring_on()) {
         // the device ring mirrors raw_images_: this frame is converted, uploaded and pyramided once
-        // (the reference re-converts every ring frame on every callback, :266-287)
+        // (the reference re-converts every ring frame on every callback, :266-287, and on every pass
+        // of run(), :464-480); the polling caller's frames wider than 320 px enter halved (:470-474)
         last_rgb_ = to_rgb8(msg);
-        const int rc = mdx_ring_push(ctx_, last_rgb_.data.data(), (int)last_rgb_.width, (int)last_rgb_.height,
-                                     (int)last_rgb_.step, MDX_FMT_RGB8, (int)raw_images_.size());
+        const bool half = !p_.use_all_frames && last_rgb_.width > 320;
+        ring_w_ = (int)last_rgb_.width;
+        ring_h_ = (int)last_rgb_.height;
+        if (half && mdx_half_size(ring_w_, ring_h_, &ring_w_, &ring_h_) != MDX_OK)
+            throw std::invalid_argument("frame too small to halve");
+        const int rc = (half ? mdx_ring_push_half : mdx_ring_push)(ctx_, last_rgb_.data.data(), (int)last_rgb_.width,
+                                                                   (int)last_rgb_.height, (int)last_rgb_.step,
+                                                                   MDX_FMT_RGB8, (int)raw_images_.size());
         if (rc < 0) throw std::runtime_error(std::string("mdx_ring_push: ") + mdx_last_error(ctx_));
     }
     bool done = false;
     if (p_.use_all_frames && image_received_) {                  // :262
-        mdx_params mp;
-        mdx_get_params(ctx_, &mp);
-        mp.pixel_step = p_.pixel_step;                           // re-read every frame (:264)
-        mp.min_vector_size = p_.min_vector_size;
-        if (mdx_set_params(ctx_, &mp) != MDX_OK) throw std::runtime_error(mdx_last_error(ctx_));
+        set_flow_params();
         FrameResult local;
         FrameResult* r = out ? out : &local;
         if (p_.live_path) {
@@ -113,6 +116,32 @@ bool MotionDetectionNode::image_callback(const Image& msg, FrameResult* out)
     }
     global_frame_count_++;
     return done;
+}
+
+// pixel_step and min_vector_size are re-read on every frame (:264) and every pass of run()
+void MotionDetectionNode::set_flow_params()
+{
+    mdx_params mp;
+    mdx_get_params(ctx_, &mp);
+    mp.pixel_step = p_.pixel_step;
+    mp.min_vector_size = p_.min_vector_size;
+    if (mdx_set_params(ctx_, &mp) != MDX_OK) throw std::runtime_error(mdx_last_error(ctx_));
+}
+
+// run() (node.cpp:457-553), one pass of its body
+bool MotionDetectionNode::run_once(FrameResult* out)
+{
+    if (!image_received_) return false;                          // :459
+    if (p_.use_all_frames || !p_.ring_on()) throw std::logic_error("run_once needs use_all_frames = false");
+    set_flow_params();
+    FrameResult local;
+    FrameResult* r = out ? out : &local;
+    reset_stages(r);
+    ring_flow(ring_w_, ring_h_, (int)raw_images_.size(), r);     // :488
+    if (r->trajectories.empty()) return true;                    // (the reference reads trajectories[0] here)
+    fit_subspace((int)raw_images_.size(), 2, p_.residual_threshold, r);   // :494
+    if (p_.run_clusters_on()) cluster_points(r);                 // :497
+    return true;
 }
 
 // runOpticalFlow (node.cpp:76-92) -> calculateOpticalFlow (optical_flow_calculator.cpp:30-130)
@@ -206,10 +235,22 @@ void MotionDetectionNode::cluster_vectors(const std::vector<double>& vectors, Fr
 // with egomotion, fitSubspace (:341-348)
 void MotionDetectionNode::run_live(int nimg, FrameResult* r)
 {
-    const int w = (int)last_rgb_.width, h = (int)last_rgb_.height, ps = p_.pixel_step;
+    reset_stages(r);
+    ring_flow((int)last_rgb_.width, (int)last_rgb_.height, nimg, r);
+    publish(kTopicFlowMarkers, flow_image(last_rgb_, r->vector_image, p_.pixel_step, p_.min_vector_size));   // (not :101-103's arrows)
+    if (r->trajectories.empty()) return;                        // :296-318
+    stage_vector_clusters(r);
+    stage_subspace(nimg, r);
+    stage_point_clusters(r);
+}
+
+// calculateOpticalFlowTrajectory over the device ring's nimg frames of w x h: the vector image and the
+// complete trajectories
+void MotionDetectionNode::ring_flow(int w, int h, int nimg, FrameResult* r)
+{
+    const int ps = p_.pixel_step;
     for (const Image& m : raw_images_)
         if (m.width != last_rgb_.width || m.height != last_rgb_.height) throw std::invalid_argument("frame sizes differ");
-    reset_stages(r);
     const int npts = mdx_grid_count(w, h, ps);
     r->w = w;
     r->h = h;
@@ -229,11 +270,6 @@ void MotionDetectionNode::run_live(int nimg, FrameResult* r)
     r->trajectories.clear();
     for (int k = 0; k < npts; k++)                              // full-length ones only (:244-249)
         if (tlen[k] == nimg) r->trajectories.emplace_back(&traj[(size_t)k * nimg * 2], &traj[(size_t)(k + 1) * nimg * 2]);
-    publish(kTopicFlowMarkers, flow_image(last_rgb_, r->vector_image, ps, p_.min_vector_size));   // (not :101-103's arrows)
-    if (r->trajectories.empty()) return;                        // :296-318
-    stage_vector_clusters(r);
-    stage_subspace(nimg, r);
-    stage_point_clusters(r);
 }
 
 // without egomotion (:357-389): getClusters(optical_flow_vectors, pixel_step, distance_threshold,
@@ -248,14 +284,18 @@ void MotionDetectionNode::stage_vector_clusters(FrameResult* r)
 // fitSubspace on the complete trajectories (:341-348), one rand() stream across frames
 void MotionDetectionNode::stage_subspace(int nimg, FrameResult* r)
 {
-    if (!p_.subspace_on()) return;
-    const int nt = (int)r->trajectories.size(), d = 4 * p_.num_motions;
+    if (p_.subspace_on()) fit_subspace(nimg, p_.num_motions, p_.sigma, r);
+}
+
+void MotionDetectionNode::fit_subspace(int nimg, int num_motions, double sigma, FrameResult* r)
+{
+    const int nt = (int)r->trajectories.size(), d = 4 * num_motions;
     std::vector<float> flat((size_t)nt * nimg * 2);
     for (int i = 0; i < nt; i++) std::memcpy(&flat[(size_t)i * nimg * 2], r->trajectories[i].data(), (size_t)nimg * 8);
     std::vector<int> cols(d);
     std::vector<float> outl((size_t)nt * 2);
     int nout = 0;
-    const int rc = mdx_fit_subspace(ctx_, flat.data(), nt, nimg, p_.num_motions, p_.sigma, &rng_, cols.data(), nullptr,
+    const int rc = mdx_fit_subspace(ctx_, flat.data(), nt, nimg, num_motions, sigma, &rng_, cols.data(), nullptr,
                                     nullptr, outl.data(), &nout);
     if (rc < 0) throw std::runtime_error(std::string("mdx_fit_subspace: ") + mdx_last_error(ctx_));
     r->outlier_points.assign(outl.begin(), outl.begin() + 2 * nout);
@@ -267,7 +307,11 @@ void MotionDetectionNode::stage_subspace(int nimg, FrameResult* r)
 // (optical_flow_visualizer.cpp:230-236)
 void MotionDetectionNode::stage_point_clusters(FrameResult* r)
 {
-    if (!p_.point_clusters_on()) return;
+    if (p_.point_clusters_on()) cluster_points(r);
+}
+
+void MotionDetectionNode::cluster_points(FrameResult* r)
+{
     const int nout = (int)(r->outlier_points.size() / 2);
     cluster_and_trim("mdx_cluster_euclidean", nout, r, [&](int max_kept, int* nkept) {
         return mdx_cluster_euclidean(ctx_, r->outlier_points.data(), nout, p_.distance_threshold, 5,

@@ -47,6 +47,8 @@ struct Params {
     bool egomotion = true;
     bool use_all_frames = true;
     double sigma = 0.5;
+    // the polling caller's fitSubspace threshold (run(), node.cpp:491); run_once() reads it, nothing else does
+    double residual_threshold = 0.2;
     // which caller body to run per frame: true = the live path (trajectories + fitSubspace,
     // node.cpp:266-348), false = runOpticalFlow on the ring's last two frames (:76-92), the only
     // caller that produces the motion mask
@@ -83,6 +85,9 @@ struct Params {
     bool vector_clusters_on() const { return live_path && !egomotion && both_thresholds(); }
     bool subspace_on() const { return live_path && egomotion; }
     bool point_clusters_on() const { return subspace_on() && distance_threshold > 0; }
+    // the polling caller (run_once): which frames enter the device ring, and its clusterEuclidean (:497)
+    bool ring_on() const { return live_path || !use_all_frames; }
+    bool run_clusters_on() const { return distance_threshold > 0; }
 };
 
 // What the optional stages behind the flow write.  A stage that is off or did not run leaves its fields
@@ -150,6 +155,20 @@ public:
     // imageCallback (node.cpp:235-455): returns true and fills *out when the frame was processed.
     bool image_callback(const Image& msg, FrameResult* out);
 
+    // One pass of the polling caller run()'s body (node.cpp:464-529), for use_all_frames = false, where
+    // imageCallback only fills the ring: returns false until image_received_; then the trajectories over the
+    // ring's frames, fitSubspace(trajectories, outlier_points, 2, residual_threshold) (:494: the 2 is
+    // hard-coded there, whatever num_motions says; num_motions still sizes the ring) and, with
+    // distance_threshold > 0, clusterEuclidean (:497) and the kept clusters' rectangles.  With
+    // use_all_frames false every frame wider than 320 px enters the device ring halved
+    // (cv::resize(.., 0.5, 0.5), :470-474; mdx_ring_push_half), once, from image_callback; *out then has
+    // the halved size.  With no complete trajectory (the reference indexes trajectories[0], undefined)
+    // the fit and the clustering are skipped and *out carries empty lists.  There is no egomotion branch,
+    // nothing is published (the markers would need the halved frame back on the host) and nothing is
+    // logged.  Two passes without a new frame see the same ring and a further-advanced rand() stream, as
+    // the reference's spinning loop does.
+    bool run_once(FrameResult* out);
+
     Params& params() { return p_; }
     long global_frame_count() const { return global_frame_count_; }
     int trajectory_size() const { return p_.egomotion ? 2 * p_.num_motions + 1 : 2; }   // :241-245
@@ -157,6 +176,10 @@ public:
 private:
     void run_pair(const Image& a, const Image& b, FrameResult* r);
     void run_live(int nimg, FrameResult* r);
+    void set_flow_params();
+    void ring_flow(int w, int h, int nimg, FrameResult* r);
+    void fit_subspace(int nimg, int num_motions, double sigma, FrameResult* r);
+    void cluster_points(FrameResult* r);
     // the optional stages behind the flow; each returns at once unless its Params::*_on() holds
     void stage_detect_outliers(FrameResult* r);
     void stage_regions(FrameResult* r);
@@ -173,6 +196,7 @@ private:
     mdx_rand_state rng_{};
     std::deque<Image> raw_images_;
     Image last_rgb_;                          // the newest frame as rgb8 (also in the device ring)
+    int ring_w_ = 0, ring_h_ = 0;             // the size the newest frame has in the device ring (halved or not)
     bool image_received_ = false;
     long global_frame_count_ = 0;
 };

@@ -14,10 +14,17 @@
 //            [detect_outliers=0]      (pair path with both thresholds > 0: flag the flow vectors' median / MAD
 //                                      outliers and cluster them by distance and angle)
 //            [include_zeros=0]        (findOutliers: vectors without flow take part in the statistics)
+//            [use_all_frames=1]       (0: the polling caller run() (node.cpp:457-553) instead of imageCallback's
+//                                      body: the callback only fills the ring, every frame wider than 320 px
+//                                      entering it halved on the device (:470-474), and run_once() is called once
+//                                      after every delivered frame, a deterministic stand-in for the polling loop)
+//            [residual_threshold=0.2] (use_all_frames=0: fitSubspace's threshold (:491); its num_motions is 2 there)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
-// For the k-th processed frame it writes to <outdir>:
+// For the k-th processed frame (use_all_frames=0: the k-th run_once() that processed, which writes what a
+// live frame writes -- res, flow, traj and, with distance_threshold > 0, clusters -- at the size the frames
+// have in the ring, publishes nothing and logs nothing) it writes to <outdir>:
 //   pub_<k>_<topic>.rgb8          every published image (raw RGB8, step 3 * width)
 //   res_<k>.bin                   i32 num_vectors, rc, w, h, npts, ntraj, traj_len, nout; f64 H[9];
 //                                 pair: f32 next_pts[2 npts], u8 status[npts], u8 mask[w h];
@@ -141,6 +148,9 @@ int main(int argc, char** argv)
         p.region_open = geti("region_open", 1) != 0;
         p.detect_outliers = geti("detect_outliers", 0) != 0;
         p.include_zeros = geti("include_zeros", 0) != 0;
+        p.use_all_frames = geti("use_all_frames", 1) != 0;
+        p.residual_threshold = getd("residual_threshold", 0.2);
+        const bool polling = !p.use_all_frames;
         const int device = geti("device", 0);
         const std::string out = argv[2];
         const std::vector<Image> frames = read_frames(argv[1]);
@@ -157,7 +167,7 @@ int main(int argc, char** argv)
         // `stride` ints); the frame is the callback's global_frame_count_ (node.cpp:433), before its closing
         // increment (:454)
         auto log_rectangles = [&](const int32_t* rects, int stride, size_t count) {
-            if (!ml) return;
+            if (!ml || polling) return;   // run() logs nothing
             const int frame = (int)node.global_frame_count() - 1;
             for (size_t i = 0; i < count; i++) {
                 const int32_t* q = rects + stride * i;
@@ -166,7 +176,13 @@ int main(int argc, char** argv)
         };
         for (size_t fi = 0; fi < frames.size(); fi++) {
             FrameResult r;
-            if (!node.image_callback(frames[fi], &r)) continue;
+            if (polling) {
+                node.image_callback(frames[fi], nullptr);
+                if (!node.run_once(&r)) continue;
+            } else if (!node.image_callback(frames[fi], &r)) {
+                continue;
+            }
+            const bool live = p.live_path || polling;
             const std::string sfx = "_" + std::to_string(k) + ".bin";
             const int32_t num_kept = (int32_t)r.kept_clusters.size();
             // labels, kept ids and rectangles: the tail of every cluster file, then the rectangles' log lines
@@ -180,7 +196,7 @@ int main(int argc, char** argv)
             ByteBuffer res{r.num_vectors, r.rc, r.w, r.h, r.npts, (int32_t)r.trajectories.size(), traj_len,
                            (int32_t)(r.outlier_points.size() / 2)};
             res.put(r.H, sizeof(r.H));
-            if (!p.live_path) {
+            if (!live) {
                 res.put(r.next_pts);
                 res.put(r.status);
                 res.put(r.mask);
@@ -192,25 +208,25 @@ int main(int argc, char** argv)
                 res.put(r.subspace_columns);
                 write_trajectories(r.trajectories, out + "/traj_" + std::to_string(k));
             }
-            if (p.point_clusters_on()) {
+            if (polling ? p.run_clusters_on() : p.point_clusters_on()) {
                 ByteBuffer b{r.num_clusters, num_kept};
                 put_clusters(b);
                 b.write(out + "/clusters" + sfx);
             }
-            if (p.vector_clusters_on()) {
+            if (!polling && p.vector_clusters_on()) {
                 // (no trajectory survived: the stage did not run, no grid, n = 0)
                 ByteBuffer b{(int32_t)r.cluster_labels.size(), r.num_active_vectors, r.num_clusters, num_kept};
                 b.put(r.grid);
                 put_clusters(b);
                 b.write(out + "/vclusters" + sfx);
             }
-            if (p.regions_on()) {
+            if (!polling && p.regions_on()) {
                 ByteBuffer b{r.num_regions_all, (int32_t)(r.regions.size() / 8)};
                 b.put(r.regions);
                 b.write(out + "/regions" + sfx);
                 log_rectangles(r.regions.data(), 8, r.regions.size() / 8);
             }
-            if (p.detect_outliers_on()) {
+            if (!polling && p.detect_outliers_on()) {
                 const mdx_outlier_stats& st = r.outlier_stats;
                 const double osta[4] = {st.median_angle, st.mad_angle, st.median_magnitude, st.mad_magnitude};
                 ByteBuffer b{(int32_t)r.outlier_flags.size(), st.selected, st.flagged_angle, st.flagged_magnitude,
@@ -224,7 +240,7 @@ int main(int argc, char** argv)
             res.write(out + "/res" + sfx);
             write_flow(r.vector_image, r.w, r.h, p.pixel_step, out + "/flow_" + std::to_string(k));
             std::printf("frame %zu -> processed %d: num_vectors %d%s\n", fi, k, r.num_vectors,
-                        p.live_path ? (", trajectories " + std::to_string(r.trajectories.size()) + ", outliers " +
+                        live ? (", trajectories " + std::to_string(r.trajectories.size()) + ", outliers " +
                                        std::to_string(r.outlier_points.size() / 2)).c_str()
                                     : "");
             k++;

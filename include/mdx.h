@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 9    /* 2: mdx_params.call_pipelining, mdx_input_ready.
+#define MDX_ABI_VERSION 10   /* 2: mdx_params.call_pipelining, mdx_input_ready.
                                 3: mdx_lk_fallbacks; mdx_params grew ransac_iters, ransac_thresh and
                                    ransac_seed (16 more bytes: a caller built against ABI 2 passes a
                                    shorter struct); mdx_sync / mdx_device_sync return MDX_OK after an
@@ -38,7 +38,9 @@ extern "C" {
                                    unchanged, 80 bytes).
                                 8: mdx_cluster_vectors (a new entry; mdx_params is unchanged, 80 bytes).
                                 9: mdx_find_outliers and mdx_outlier_stats (a new entry; mdx_params is
-                                   unchanged, 80 bytes). */
+                                   unchanged, 80 bytes).
+                                10: mdx_half_size, mdx_resize_half_dev, mdx_resize_half and
+                                   mdx_ring_push_half (new entries; mdx_params is unchanged, 80 bytes). */
 
 /* Return codes */
 #define MDX_OK           0
@@ -304,6 +306,50 @@ int mdx_ring_push(mdx_ctx* ctx, const uint8_t* img, int w, int h, int stride, in
 int mdx_ring_trajectory(mdx_ctx* ctx, float* traj, int32_t* traj_len, float* start_pts, double* vectors,
                         int* num_vectors);
 int mdx_ring_reset(mdx_ctx* ctx);
+
+/*
+ * Half-size ingest: the reference node's cv::resize(img, out, cv::Size(), 0.5, 0.5) of every frame
+ * wider than 320 px (ros/src/motion_detection_node.cpp:470-474), as a device stage.  The arithmetic is
+ * OpenCV 2.4.8's resize(): INTER_LINEAR at an integer scale of 2 is redirected to INTER_AREA's fast
+ * 2x2 mode.  Restated from the published algorithm and unpinned against a real build.
+ *   size      dw = cvRound(w * 0.5), dh = cvRound(h * 0.5), half to even: an even side halves, an odd
+ *             side 2k+1 gives k for even k and k+1 for odd k (3->2, 5->2, 7->4, 9->4, 321->160, 323->162)
+ *   full      destination pixel (dx, dy) with 2dx+1 < w and 2dy+1 < h, per channel:
+ *             (S[2dy][2dx] + S[2dy][2dx+1] + S[2dy+1][2dx] + S[2dy+1][2dx+1] + 2) >> 2
+ *   partial   only where an odd side rounded up (the last column for dw = k+1, the last row likewise):
+ *             cvRound((float)sum / count) over the block's in-frame pixels (count 2 on an edge, 1 in the
+ *             corner), half to even: two pixels summing to 1 give 0, summing to 3 give 2
+ *   dropped   where an odd side rounded down, the last source column or row is read by nothing
+ * Channels are treated alone, so cv_bridge's mono8 replication and bgr8 reordering commute with it:
+ * mono8 is halved as one channel and stays MDX_FMT_GRAY8, rgb8 / bgr8 as three and keep their format.
+ */
+/* dst size of the reference's cv::resize(src, dst, Size(), 0.5, 0.5).  MDX_EINVAL: w or h < 1, or a
+ * side that rounds to 0 (w == 1 or h == 1: the reference's CV_Assert(dsize.area())); *dw, *dh are then
+ * untouched. */
+int mdx_half_size(int w, int h, int* dw, int* dh);
+
+/* Asynchronous, batched, every pointer a device pointer; queued on the context stream; honours
+ * mdx_input_ready like the other device entries.  channels 1 or 3.  Frame b's row y starts at
+ * d_src + b * frame_stride + y * stride, its halved row at d_dst + b * dst_frame_stride + y * dst_stride;
+ * the bytes between dw * channels and dst_stride are never written.  d_dst must not overlap d_src.
+ * Bases and pitches that are all multiples of 4 take the kernel's vector path, anything else its
+ * byte path; the results are the same. */
+int mdx_resize_half_dev(mdx_ctx* ctx, int batch, const uint8_t* d_src, int w, int h, int stride,
+                        size_t frame_stride, int channels,
+                        uint8_t* d_dst, int dst_stride, size_t dst_frame_stride);
+
+/* One host frame, synchronous.  Only w * channels bytes of the last source row are read, and only
+ * dw * channels bytes of each destination row are written. */
+int mdx_resize_half(mdx_ctx* ctx, const uint8_t* src, int w, int h, int stride, int channels,
+                    uint8_t* dst, int dst_stride);
+
+/* mdx_ring_push of the halved frame: upload the full frame, halve it on the device, pyramid the
+ * result.  The ring's geometry is (dw, dh); everything else is mdx_ring_push's contract (keep, the
+ * return value, a frame of another size empties the ring, the host frame stays unchanged until the
+ * next mdx_ring_trajectory / mdx_sync).  Frames pushed either way may share a ring when their
+ * resulting sizes agree.  The context's size limits apply to the halved frame: the source may be up
+ * to twice max_w x max_h; its staging buffer grows on first use. */
+int mdx_ring_push_half(mdx_ctx* ctx, const uint8_t* img, int w, int h, int stride, int fmt, int keep);
 
 /*
  * Trajectory subspace RANSAC: replaces OutlierDetector::fitSubspace

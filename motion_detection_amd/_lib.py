@@ -46,14 +46,14 @@ EXPORTED = [
     "mdx_host_alloc", "mdx_host_free", "mdx_probe_stream3_dev", "mdx_lk_fallbacks",
     "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
     "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions", "mdx_cluster_vectors",
-    "mdx_find_outliers",
+    "mdx_find_outliers", "mdx_half_size", "mdx_resize_half_dev", "mdx_resize_half", "mdx_ring_push_half",
 ]
-ABI_VERSION = 9  # include/mdx.h MDX_ABI_VERSION
+ABI_VERSION = 10  # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_internal.h", "mdx_ctx.h", "mdx_dev.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp",
            "mdx_post.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "mdx_resize.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -232,6 +232,15 @@ def lib() -> C.CDLL:
     L.mdx_flow_trajectory.restype = C.c_int
     L.mdx_ring_push.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.mdx_ring_push.restype = C.c_int
+    L.mdx_ring_push_half.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.mdx_ring_push_half.restype = C.c_int
+    L.mdx_half_size.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mdx_half_size.restype = C.c_int
+    L.mdx_resize_half_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, vp, C.c_int,
+                                      C.c_size_t]
+    L.mdx_resize_half_dev.restype = C.c_int
+    L.mdx_resize_half.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    L.mdx_resize_half.restype = C.c_int
     L.mdx_ring_trajectory.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.mdx_ring_trajectory.restype = C.c_int
     L.mdx_ring_reset.argtypes = [vp]

@@ -63,6 +63,15 @@ def grid_count(w: int, h: int, pixel_step: int) -> int:
     return lib().mdx_grid_count(w, h, pixel_step)
 
 
+def half_size(w: int, h: int) -> tuple:
+    """(dw, dh) of the reference's cv::resize(src, dst, Size(), 0.5, 0.5) (include/mdx.h mdx_half_size):
+    cvRound(side * 0.5), half to even.  ValueError when a side is below 1 or rounds to 0."""
+    dw, dh = C.c_int(0), C.c_int(0)
+    if lib().mdx_half_size(int(w), int(h), C.byref(dw), C.byref(dh)) != _lib.MDX_OK:
+        raise ValueError(f"a {w} x {h} frame has no half size")
+    return dw.value, dh.value
+
+
 def grid_points(w: int, h: int, pixel_step: int) -> np.ndarray:
     """Grid of the reference (optical_flow_calculator.cpp:56-64): x-major, float32 (n, 2)."""
     xs = np.arange(0, w, pixel_step, dtype=np.float32)
@@ -261,14 +270,16 @@ class Context:
         return TrajectoryResult(num.value, traj, tlen, start, vec)
 
     # -- resident frame ring (the node's raw_images_ deque kept in HBM: mdx_ring_*)
-    def ring_push(self, image: np.ndarray, keep: int, fmt: int | None = None) -> int:
+    def ring_push(self, image: np.ndarray, keep: int, fmt: int | None = None, half: bool = False) -> int:
         """Append one frame (pyramided once, on the device) and keep at most `keep` frames.
-        Returns the number of frames held."""
+        Returns the number of frames held.  half: the frame is halved on the device on its way in
+        (mdx_ring_push_half); the ring then holds half_size(w, h) frames."""
         im = _frame_view(image)
         h, w = im.shape[:2]
         if fmt is None:
             fmt = _lib.FMT_GRAY8 if im.ndim == 2 else _lib.FMT_RGB8
-        n = self._check(lib().mdx_ring_push(self._h, _ptr(im), w, h, im.strides[0], fmt, int(keep)))
+        push = lib().mdx_ring_push_half if half else lib().mdx_ring_push
+        n = self._check(push(self._h, _ptr(im), w, h, im.strides[0], fmt, int(keep)))
         # the upload is queued, not done (include/mdx.h): hold the frame until the next
         # ring_trajectory / sync returns
         self._ring_hold.append(im)
@@ -405,6 +416,26 @@ class Context:
         return self._check(lib().mdx_mask_regions_dev(
             self._h, batch, _v(d_mask), w, h, stride, frame_stride, _lib.REGIONS_OPEN3 if open3 else 0, int(min_area),
             _v(d_regions), max_regions, _v(d_num_all), _v(d_num_kept), _v(d_labels), _v(d_mask_out)))
+
+    # -- half-size ingest (the node's cv::resize(img, out, Size(), 0.5, 0.5), node.cpp:470-474)
+    def resize_half(self, image: np.ndarray) -> np.ndarray:
+        """image: (h, w) or (h, w, 3) uint8, a row-pitched view allowed.  Returns a new packed array of
+        half_size(w, h)."""
+        im = _frame_view(image)
+        if im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] != 3):
+            raise ValueError("image must be (h, w) or (h, w, 3)")
+        h, w = im.shape[:2]
+        cn = 1 if im.ndim == 2 else 3
+        dw, dh = half_size(w, h)
+        out = np.empty((dh, dw) if cn == 1 else (dh, dw, 3), np.uint8)
+        self._check(lib().mdx_resize_half(self._h, _ptr(im), w, h, im.strides[0], cn, _ptr(out), dw * cn))
+        return out
+
+    def resize_half_dev(self, batch: int, d_src: int, w: int, h: int, stride: int, frame_stride: int, channels: int,
+                        d_dst: int, dst_stride: int, dst_frame_stride: int) -> int:
+        """Asynchronous on the context stream (include/mdx.h mdx_resize_half_dev); pointers are ints."""
+        return self._check(lib().mdx_resize_half_dev(self._h, batch, _v(d_src), w, h, stride, frame_stride, channels,
+                                                     _v(d_dst), dst_stride, dst_frame_stride))
 
     # -- device entries (pointers are ints, e.g. torch.Tensor.data_ptr())
     def flow_warp_diff_batch_dev(self, batch: int, d_img1: int, d_img2: int, w: int, h: int, stride: int,

@@ -383,3 +383,81 @@ extern "C" int mdx_memcpy_d2h(mdx_ctx* c, void* dst, const void* src, size_t byt
     HIP_OR_RETURN(c, hipStreamSynchronize(c->stream));
     return MDX_OK;
 }
+
+// Half-size ingest (include/mdx.h; the kernel is mdx_resize.hip's k_half).
+extern "C" int mdx_half_size(int w, int h, int* dw, int* dh)
+{
+    if (w < 2 || h < 2 || !dw || !dh) return MDX_EINVAL;   // a side of 1 rounds to 0
+    // cvRound(side * 0.5): an odd side 2k + 1 lies halfway between k and k + 1 and goes to the even one
+    auto half = [](int v) { return v / 2 + ((v & 1) & (v / 2 & 1)); };
+    *dw = half(w);
+    *dh = half(h);
+    return MDX_OK;
+}
+
+static int check_half(mdx_ctx* c, const char* who, int batch, const uint8_t* src, int w, int h, int stride,
+                      size_t frame_stride, int channels, const uint8_t* dst, int dst_stride, size_t dst_frame_stride,
+                      int* dw, int* dh)
+{
+    if (!src || !dst || batch < 1) return set_err(c, MDX_EINVAL, "%s: null pointer or batch < 1", who);
+    if (channels != 1 && channels != 3) return set_err(c, MDX_EINVAL, "%s: channels %d, not 1 or 3", who, channels);
+    if (mdx_half_size(w, h, dw, dh) != MDX_OK) return set_err(c, MDX_EINVAL, "%s: a side of %d x %d halves to 0", who, w, h);
+    if (*dh > 65535 * kHalfRows) return set_err(c, MDX_EINVAL, "%s: more than %d rows", who, 2 * 65535 * kHalfRows);
+    if ((long long)w * channels > INT32_MAX || stride < w * channels)
+        return set_err(c, MDX_EINVAL, "%s: stride %d < w*channels", who, stride);
+    if (frame_stride < (size_t)h * (size_t)stride) return set_err(c, MDX_EINVAL, "%s: frame_stride < h*stride", who);
+    if (dst_stride < *dw * channels) return set_err(c, MDX_EINVAL, "%s: dst_stride %d < dw*channels %d", who, dst_stride, *dw * channels);
+    if (dst_frame_stride < (size_t)*dh * (size_t)dst_stride)
+        return set_err(c, MDX_EINVAL, "%s: dst_frame_stride < dh*dst_stride", who);
+    // the bytes either side touches: whole frames but the last, whose last row ends with its pixels
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t s1 = s0 + (size_t)(batch - 1) * frame_stride + (size_t)(h - 1) * stride + (size_t)w * channels;
+    const uintptr_t d1 = d0 + (size_t)(batch - 1) * dst_frame_stride + (size_t)(*dh - 1) * dst_stride + (size_t)*dw * channels;
+    if (s0 < d1 && d0 < s1) return set_err(c, MDX_EINVAL, "%s: source and destination overlap", who);
+    return MDX_OK;
+}
+
+extern "C" int mdx_resize_half_dev(mdx_ctx* c, int batch, const uint8_t* d_src, int w, int h, int stride,
+                                   size_t frame_stride, int channels, uint8_t* d_dst, int dst_stride,
+                                   size_t dst_frame_stride)
+{
+    if (!c) return MDX_EINVAL;
+    int dw, dh;
+    if (const int rc = check_half(c, "mdx_resize_half_dev", batch, d_src, w, h, stride, frame_stride, channels, d_dst,
+                                  dst_stride, dst_frame_stride, &dw, &dh);
+        rc != MDX_OK)
+        return rc;
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (c->input_ev) {      // mdx_input_ready: one-shot
+        hipEvent_t e = c->input_ev;
+        c->input_ev = nullptr;
+        HIP_OR_RETURN(c, hipStreamWaitEvent(s, e, 0));
+    }
+    HIP_OR_RETURN(c, launch_half(s, batch, d_src, w, h, stride, frame_stride, channels, d_dst, dst_stride, dst_frame_stride));
+    return MDX_OK;
+}
+
+extern "C" int mdx_resize_half(mdx_ctx* c, const uint8_t* src, int w, int h, int stride, int channels, uint8_t* dst,
+                               int dst_stride)
+{
+    if (!c) return MDX_EINVAL;
+    int dw, dh;
+    const size_t fs = (size_t)std::max(h, 0) * (size_t)std::max(stride, 0);
+    // (host pointers: the overlap test compares what it is given; the device copies never overlap)
+    if (const int rc = check_half(c, "mdx_resize_half", 1, src, w, h, stride, fs, channels, dst, dst_stride,
+                                  (size_t)std::max(h, 0) * (size_t)std::max(dst_stride, 0), &dw, &dh);
+        rc != MDX_OK)
+        return rc;
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const int dpitch = (dw * channels + 3) & ~3;
+    if (const int rc = ensure_all(c, {{&c->hsrc, fs}, {&c->hdst, (size_t)dpitch * dh}}); rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    // the caller's last row holds w * channels bytes, not stride
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->hsrc.p, src, (size_t)(h - 1) * stride + (size_t)w * channels, hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, launch_half(s, 1, c->hsrc.as<uint8_t>(), w, h, stride, 0, channels, c->hdst.as<uint8_t>(), dpitch, 0));
+    HIP_OR_RETURN(c, hipMemcpy2DAsync(dst, (size_t)dst_stride, c->hdst.p, (size_t)dpitch, (size_t)dw * channels, (size_t)dh,
+                                      hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    return MDX_OK;
+}

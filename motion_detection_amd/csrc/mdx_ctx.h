@@ -125,6 +125,8 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf rgscr;                            // mdx_mask_regions_dev: labels, block counts, component records
     DevBuf rgin, rgout;                      // mdx_mask_regions (host entry): the mask, every output
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
+    DevBuf rfull;                            // mdx_ring_push_half: the full-size frame, halved into rin
+    DevBuf hsrc, hdst;                       // mdx_resize_half (host entry): the frame and its half
     DevBuf wscr;                             // k_warp_prep's per-pair / per-tile tables
     mdx::WarpLaunch last_warp;               // the last launch_warp_diff (mdx_debug_warp_paths)
     DevBuf rsc;                              // MDX_FIT_RANSAC scratch (list, hypotheses, counts)

@@ -1,5 +1,5 @@
 // mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
-// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip, mdx_resize.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
 // mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
@@ -415,5 +415,21 @@ size_t regions_scratch_bytes(int batch, int w, int h, RegionsScratch* lay = null
 hipError_t launch_mask_regions(hipStream_t s, int batch, const uint8_t* mask, int w, int h, int stride,
                                size_t frame_stride, int open3, int min_area, mdx_region* regions, int max_regions,
                                int32_t* num_all, int32_t* num_kept, int32_t* labels, uint8_t* mask_out, void* scratch);
+
+// Half-size ingest (mdx_resize.hip k_half): `batch` frames of w x h pixels of `channels`
+// (1 or 3) interleaved bytes halved to mdx_half_size(w, h), one launch on s (per kHalfMaxBatch frames).
+// A lane owns kHalfPx adjacent destination pixels of kHalfRows rows; a wave 64 * kHalfPx and a
+// workgroup kHalfWgPx destination pixels of a row.
+constexpr int kHalfPx = 4;
+constexpr int kHalfWavePx = 64 * kHalfPx;
+constexpr int kHalfWgPx = 256 * kHalfPx;
+constexpr int kHalfRows = 4;
+constexpr int kHalfMaxBatch = 65535;   // frames per launch (grid z)
+// whether launch_half takes k_half's vector path: every base and pitch (a batch's frame pitches too) a
+// multiple of 4; otherwise its byte path
+bool half_vector_path(int batch, const void* src, int stride, size_t frame_stride, const void* dst, int dst_stride,
+                      size_t dst_frame_stride);
+hipError_t launch_half(hipStream_t s, int batch, const uint8_t* src, int w, int h, int stride, size_t frame_stride,
+                       int channels, uint8_t* dst, int dst_stride, size_t dst_frame_stride);
 
 }  // namespace mdx

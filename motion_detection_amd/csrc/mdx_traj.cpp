@@ -221,25 +221,34 @@ extern "C" int mdx_ring_reset(mdx_ctx* c)
     return MDX_OK;
 }
 
-extern "C" int mdx_ring_push(mdx_ctx* c, const uint8_t* img, int w, int h, int stride, int fmt, int keep)
+// mdx_ring_push and mdx_ring_push_half: the frame (halved first when `half`) enters a free slot as its
+// padded pyramid and Scharr planes.  The ring's geometry is the size the frame has after the halving.
+static int ring_push(mdx_ctx* c, const char* who, const uint8_t* img, int w, int h, int stride, int fmt, int keep,
+                     bool half)
 {
     if (!c) return MDX_EINVAL;
-    if (!img) return set_err(c, MDX_EINVAL, "mdx_ring_push: null frame");
-    if (keep < 1) return set_err(c, MDX_EINVAL, "mdx_ring_push: keep must be >= 1");
-    int rc = check_frame(c, "mdx_ring_push", w, h, stride, fmt);
+    if (!img) return set_err(c, MDX_EINVAL, "%s: null frame", who);
+    if (keep < 1) return set_err(c, MDX_EINVAL, "%s: keep must be >= 1", who);
+    int rc = check_frame(c, who, w, h, stride, fmt);
     if (rc != MDX_OK) return rc;
+    const int cn = fmt == MDX_FMT_GRAY8 ? 1 : 3;
+    int rw = w, rh = h, rstride = stride;          // the frame the pyramid is built from
+    if (half) {
+        if (mdx_half_size(w, h, &rw, &rh) != MDX_OK) return set_err(c, MDX_EINVAL, "%s: a side of %d x %d halves to 0", who, w, h);
+        rstride = (rw * cn + 3) & ~3;              // k_half's vector path, whenever the caller's pitch allows it
+    }
     HIP_OR_RETURN(c, hipSetDevice(c->device));
-    if (w != c->ring_w || h != c->ring_h || c->prm.max_level != c->ring_ml) {   // another geometry: start over
+    if (rw != c->ring_w || rh != c->ring_h || c->prm.max_level != c->ring_ml) {   // another geometry: start over
         c->ring_order.clear();
         if (c->ring_pyr.p) (void)hipStreamSynchronize(c->stream);
         c->ring_pyr.reset();
         c->ring_der.reset();
         c->ring_cap = 0;
-        c->ring_w = w;
-        c->ring_h = h;
+        c->ring_w = rw;
+        c->ring_h = rh;
         c->ring_ml = c->prm.max_level;
     }
-    const Geometry g = make_geometry(w, h, c->prm.max_level);
+    const Geometry g = make_geometry(rw, rh, c->prm.max_level);
     const int n = (int)c->ring_order.size();
     if ((rc = ring_grow(c, g, std::max(n + 1, std::max(keep, 4)))) != MDX_OK) return rc;
     // a free slot: the lowest one no held frame uses
@@ -247,19 +256,33 @@ extern "C" int mdx_ring_push(mdx_ctx* c, const uint8_t* img, int w, int h, int s
     for (int o : c->ring_order) used[o] = 1;
     int slot = 0;
     while (used[slot]) slot++;
-    const size_t fbytes = (size_t)stride * h;
-    if ((rc = ensure(c, c->rin, fbytes)) != MDX_OK) return rc;
+    const size_t fbytes = (size_t)rstride * rh;
+    // the upload lands in rfull when it is halved into rin, else in rin itself
+    DevBuf& up = half ? c->rfull : c->rin;
+    if ((rc = ensure_all(c, {{&up, (size_t)stride * h}, {&c->rin, fbytes}})) != MDX_OK) return rc;
     hipStream_t s = c->stream;
-    HIP_OR_RETURN(c, hipMemcpyAsync(c->rin.p, img, frame_copy_bytes(w, h, stride, fmt), hipMemcpyHostToDevice, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(up.p, img, frame_copy_bytes(w, h, stride, fmt), hipMemcpyHostToDevice, s));
+    if (half)
+        HIP_OR_RETURN(c, launch_half(s, 1, up.as<uint8_t>(), w, h, stride, 0, cn, c->rin.as<uint8_t>(), rstride, 0));
     uint8_t* pyr = c->ring_pyr.as<uint8_t>() + (size_t)g.img_bytes * slot;
     uint32_t* der = c->ring_der.as<uint32_t>() + (size_t)g.der_words * slot;
-    HIP_OR_RETURN(c, launch_front(s, 1, c->rin.as<uint8_t>(), c->rin.as<uint8_t>(), w, h, stride, (long long)fbytes, fmt,
+    HIP_OR_RETURN(c, launch_front(s, 1, c->rin.as<uint8_t>(), c->rin.as<uint8_t>(), rw, rh, rstride, (long long)fbytes, fmt,
                                   pyr, pyr, g, 1));
     HIP_OR_RETURN(c, launch_pyr_levels(s, 1, pyr, pyr, g, 1));
     HIP_OR_RETURN(c, launch_scharr_levels(s, 1, pyr, der, g));
     c->ring_order.push_back(slot);
     while ((int)c->ring_order.size() > keep) c->ring_order.erase(c->ring_order.begin());
     return (int)c->ring_order.size();
+}
+
+extern "C" int mdx_ring_push(mdx_ctx* c, const uint8_t* img, int w, int h, int stride, int fmt, int keep)
+{
+    return ring_push(c, "mdx_ring_push", img, w, h, stride, fmt, keep, false);
+}
+
+extern "C" int mdx_ring_push_half(mdx_ctx* c, const uint8_t* img, int w, int h, int stride, int fmt, int keep)
+{
+    return ring_push(c, "mdx_ring_push_half", img, w, h, stride, fmt, keep, true);
 }
 
 extern "C" int mdx_ring_trajectory(mdx_ctx* c, float* traj, int32_t* traj_len, float* start_pts, double* vectors,

@@ -36,6 +36,15 @@ out) and both thresholds set, the pair callback also runs MotionDetectionNode::d
 (:112-160) on the pair's Vec4d image: findOutliers (``include_zeros`` is its parameter) ->
 getOutlierVectors -> getClusters; the FlowResult then carries ``outlier_flags``, ``vector_clusters``,
 ``clusters`` and ``rectangles``, and under ``log_contours`` the rectangles are logged.
+
+With ``use_all_frames=False`` the callback only fills the ring (:262) and the reference's polling caller
+run() (:457-553) does the work: ``run_once()`` is one pass of its body (:464-529) and ``run()`` the loop.
+Every ring frame wider than 320 px is halved (cv::resize(img, out, Size(), 0.5, 0.5), :470-474) -- here
+on the device, on its way into the context's resident ring, which each message enters once --, then the
+trajectories, fitSubspace(trajectories, outlier_points, 2, residual_threshold) (:494: the 2 is hard-coded
+there, whatever ``num_motions`` says, which still sizes the ring) and clusterEuclidean (:497).  run() has
+no egomotion branch and writes no motion.log.  Two passes without a new frame see the same ring and a
+further-advanced rand() stream, as the reference's spinning loop does.
 """
 from __future__ import annotations
 
@@ -46,7 +55,7 @@ from typing import Callable
 import numpy as np
 
 from . import _lib
-from .context import grid_points
+from .context import grid_points, half_size
 from .flow_clusterer import FlowClusterer, bounding_rects
 from .formats import MotionLogger
 from .optical_flow_calculator import OpticalFlowCalculator
@@ -107,6 +116,8 @@ class MotionDetectionNode:
         # (live_chain True; False selects the pair path on the ring's last two frames)
         self.params = {"pixel_step": 10, "min_vector_size": 1.0, "skip_frames": 1, "num_motions": 2,
                        "egomotion": True, "use_all_frames": True, "sigma": 0.5, "live_chain": True,
+                       # run()'s fitSubspace threshold (:491); only run_once() reads it
+                       "residual_threshold": 0.2,
                        # clustering: distance_threshold has no default in the reference (node.cpp:34;
                        # the launch files set it) -- None leaves the stage off; log_contours false (:39), log_path "" (:42)
                        "distance_threshold": None, "log_contours": False, "log_path": "",
@@ -132,6 +143,8 @@ class MotionDetectionNode:
         self.logger = None                                # MotionLogger (log_contours with a log_path)
         self._pair_tools = None                           # detect_outliers' (context, detector, clusterer)
         self._device = device
+        self._ring_msgs: list = []                        # run_once: the messages held by the device ring, oldest
+        self._ring_ctx = None                             # first, and the context whose ring it is
 
     def _detector(self):
         if self.od is None:
@@ -220,6 +233,81 @@ class MotionDetectionNode:
         if self.on_result is not None:
             self.on_result(res)
         return res
+
+    def _sync_ring(self, msgs: list) -> bool:
+        """Bring the device ring up to date with `msgs` (raw_images, oldest first): every message that has
+        entered since the last pass is converted (toCvCopy "rgb8", :469) and pushed once, halved when
+        wider than 320 px (:470-474).  False: the ring could not take them all (frames of several sizes)."""
+        ps, mvs = int(self.params["pixel_step"]), float(self.params["min_vector_size"])
+        held, keep = self._ring_msgs, len(msgs)
+        # the messages to keep: the longest tail of the ring's that heads msgs
+        k = min(len(held), keep)
+        while k > 0 and not all(a is b for a, b in zip(held[-k:], msgs[:k])):
+            k -= 1
+        if k == 0:
+            held = []
+            if self._ring_ctx is not None:
+                self._ring_ctx.ring_reset()
+        for m in msgs[k:]:
+            n, ctx = self.ofc.ring_push(to_rgb8(m), keep, m.width > 320, ps, mvs)
+            if ctx is not self._ring_ctx or n != min(len(held) + 1, keep):
+                # a new context (the frame outgrew the old one) or a frame of another size: the ring was
+                # empty when this frame entered
+                held = []
+                self._ring_ctx = ctx
+            held = (held + [m])[-keep:]
+        self._ring_msgs = held
+        return len(held) == keep
+
+    def run_once(self):
+        """One pass of run()'s body (node.cpp:464-529); None until image_received.  With no complete
+        trajectory (the reference indexes trajectories[0] there, undefined) the fit and the clustering are
+        skipped and the result carries empty lists."""
+        if not self.image_received:                                                                  # :459
+            return None
+        msgs = list(self.raw_images)
+        if not self._sync_ring(msgs):
+            raise ValueError("the ring's frames differ in size")
+        w, h = msgs[-1].width, msgs[-1].height
+        if w > 320:
+            w, h = half_size(w, h)
+        vec = np.zeros((h, w, 4))
+        trajectories: list = []
+        num = self.ofc.ring_trajectory(w, h, len(msgs), vec, trajectories, int(self.params["pixel_step"]),
+                                       float(self.params["min_vector_size"]))                        # :488
+        outliers, subspace, clusters, rectangles = [], [], [], []
+        thr = self.params.get("distance_threshold")
+        if trajectories:
+            subspace = self._detector().fitSubspace(trajectories, outliers, 2,
+                                                    float(self.params["residual_threshold"]))        # :494
+            if thr is not None:
+                clusters = self._clusterer().clusterEuclidean(np.asarray(outliers, np.float32).reshape(-1, 2),
+                                                              float(thr))                            # :497
+                rectangles = bounding_rects(clusters)
+        self.frames_processed += 1
+        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters, rectangles, self.global_frame_count)
+        if self.on_result is not None:
+            self.on_result(res)
+        return res
+
+    def run(self, max_runs: int | None = None, spin_once: Callable | None = None) -> list:
+        """main()'s polling loop over run() (node.cpp:579-582), for callers that want it.  spin_once, the
+        stand-in for ros::spinOnce, is called before every pass to deliver pending frames through
+        image_callback; the loop ends when it returns False, after max_runs passes that processed, or,
+        without a spin_once, at a pass that finds no full ring.  Returns the results.  The reference's loop
+        never ends, so one of the two arguments is required."""
+        if max_runs is None and spin_once is None:
+            raise ValueError("run() needs max_runs or spin_once: nothing else ends the loop")
+        out = []
+        while max_runs is None or len(out) < max_runs:
+            if spin_once is not None and spin_once() is False:
+                break
+            res = self.run_once()
+            if res is not None:
+                out.append(res)
+            elif spin_once is None:
+                break
+        return out
 
     def detect_outliers(self, h: int, w: int, res, thr: float, athr: float):
         """detectOutliers (node.cpp:112-160) on the pair's Vec4d field: findOutliers, getOutlierVectors,

@@ -38,7 +38,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .context import Context, FlowResult, grid_points
+from .context import Context, FlowResult, grid_points, half_size
 
 
 class OpticalFlowCalculator:
@@ -81,7 +81,10 @@ class OpticalFlowCalculator:
         h, w = imgs[0].shape[:2]
         fmt = _lib.FMT_GRAY8 if imgs[0].ndim == 2 else _lib.FMT_RGB8
         ctx = self._context(w, h, pixel_step, min_vector_size)
-        res = ctx.flow_trajectory(imgs, fmt=fmt)
+        return self._store_trajectory(ctx.flow_trajectory(imgs, fmt=fmt), w, h, optical_flow_vectors, trajectories)
+
+    @staticmethod
+    def _store_trajectory(res, w: int, h: int, optical_flow_vectors: np.ndarray | None, trajectories: list) -> int:
         if optical_flow_vectors is not None:
             if optical_flow_vectors.shape[:2] != (h, w) or optical_flow_vectors.shape[-1] != 4:
                 raise ValueError("optical_flow_vectors must be (h, w, 4)")
@@ -91,6 +94,25 @@ class OpticalFlowCalculator:
                 optical_flow_vectors[ix[i, 1], ix[i, 0], :] = res.vectors[i]
         trajectories.extend(res.trajectories)
         return res.num_vectors
+
+    # -- the same call over frames kept on the device (the node's polling caller run(), node.cpp:464-488)
+    def ring_push(self, image: np.ndarray, keep: int, half: bool, pixel_step: int, min_vector_size: float) -> tuple:
+        """One frame into the context's resident ring (Context.ring_push), halved on the device on its way
+        in when `half` (cv::resize(img, out, Size(), 0.5, 0.5), node.cpp:470-474).  Returns (frames held,
+        context): a frame too large for the context replaces it, and the new context's ring is empty."""
+        image = np.asarray(image)
+        h, w = image.shape[:2]
+        rw, rh = half_size(w, h) if half else (w, h)
+        ctx = self._context(rw, rh, pixel_step, min_vector_size)
+        fmt = _lib.FMT_GRAY8 if image.ndim == 2 else _lib.FMT_RGB8
+        return ctx.ring_push(image, keep, fmt=fmt, half=half), ctx
+
+    def ring_trajectory(self, w: int, h: int, nimg: int, optical_flow_vectors: np.ndarray | None, trajectories: list,
+                        pixel_step: int, min_vector_size: float) -> int:
+        """calculateOpticalFlowTrajectory over the ring's nimg frames of w x h (the size they have in the
+        ring); outputs as calculateOpticalFlowTrajectory's."""
+        ctx = self._context(w, h, pixel_step, min_vector_size)
+        return self._store_trajectory(ctx.ring_trajectory(w, h, nimg), w, h, optical_flow_vectors, trajectories)
 
     def compute(self, image1: np.ndarray, image2: np.ndarray, pixel_step: int = 10, min_vector_size: float = 1.0,
                 fmt: int | None = None, want_mask: bool = True) -> FlowResult:
