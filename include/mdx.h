@@ -577,7 +577,9 @@ int mdx_timing_calls(const mdx_ctx* ctx);
 int mdx_stage_ms(mdx_ctx* ctx, int stage, float* ms);
 
 /* Test hook: copy an internal buffer of the last call to the host (0: per-(pair, level,
- * point) float4 LK gradient sums; 1: per-level LK trace when MDX_LK_DEBUG=1 at create). */
+ * point) float4 LK gradient sums; 1: per-level LK trace when MDX_LK_DEBUG=1 at create;
+ * 7: the centred data of the last mdx_fit_subspace, [ntraj * 2 * traj_len] floats then the two
+ * means; 8: its 50 per-hypothesis inlier counts, int32). */
 int mdx_debug_copy(mdx_ctx* ctx, int which, void* dst, size_t bytes);
 /* Test hook: d_out[i] = 32 / d_in[i] through the projective warp's FP64 division (device buffers,
  * queued on the context stream); equal to IEEE division for |d_in[i]| in [2^-100, 2^100]. */

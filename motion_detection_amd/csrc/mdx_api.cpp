@@ -283,7 +283,8 @@ extern "C" int mdx_stage_ms(mdx_ctx* c, int stage, float* ms)
 
 // Test hook: copy an internal LK v2 buffer to the host (0 = A sums, 1 = per-level trace, 6 = MDX_LK_DEBUG
 // contexts only: the last call's k_lk_iter wave-iterations by row body, uint32 [kMaxLevels][2] =
-// (exact, fused) per level).
+// (exact, fused) per level; 7 = the last mdx_fit_subspace's centred data, [ntraj * 2 * traj_len] floats
+// followed by the two means; 8 = its 50 per-hypothesis inlier counts, int32).
 #if MDX_WARP_STAMP
 namespace mdx { hipError_t debug_warp_stamps(void* dst, size_t bytes); }
 #endif
@@ -298,7 +299,7 @@ extern "C" int mdx_debug_copy(mdx_ctx* c, int which, void* dst, size_t bytes)
     }
 #endif
     DevBuf& b = which == 0 ? c->Abuf : which == 1 ? c->dbg : which == 2 ? c->pyr1 : which == 3 ? c->pyr2
-              : which == 4 ? c->der : which == 6 ? c->lkcnt : c->cls;
+              : which == 4 ? c->der : which == 6 ? c->lkcnt : which == 7 ? c->sdata : which == 8 ? c->scnt : c->cls;
     if (!b.p) return set_err(c, MDX_EINVAL, "debug buffer %d unavailable", which);
     HIP_OR_RETURN(c, hipStreamSynchronize(c->stream));
     // pyramids: the half the last pair call wrote

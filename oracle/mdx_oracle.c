@@ -1254,6 +1254,13 @@ int ora_fit_subspace(const float* traj, int N, int T, int num_motions, double si
 int ora_fit_subspace_ex(const float* traj, int N, int T, int num_motions, double sigma, ora_rand_state* rng,
                         int* columns, uint8_t* is_outlier, double* residuals, int precision)
 {
+    return ora_fit_subspace_counts(traj, N, T, num_motions, sigma, rng, columns, is_outlier, residuals, precision, NULL);
+}
+
+/* counts (may be NULL): every hypothesis's inlier count np, in drawing order; untouched on -1 */
+int ora_fit_subspace_counts(const float* traj, int N, int T, int num_motions, double sigma, ora_rand_state* rng,
+                            int* columns, uint8_t* is_outlier, double* residuals, int precision, int counts[50])
+{
     const int n = 2 * T, d = 4 * num_motions;
     if (N <= 0 || d <= 0 || d > n || n > ORA_MAX_SUBSPACE || n - d == 10) return -1;
     float* data = (float*)malloc(sizeof(float) * (size_t)N * n);
@@ -1281,6 +1288,7 @@ int ora_fit_subspace_ex(const float* traj, int N, int T, int num_motions, double
         int np = 0;
         for (int i = 0; i < N; i++)
             if (ORA_RES(i) < inlier_thr) np++;
+        if (counts) counts[it] = np;
         if (np > max_points) {
             max_points = np;
             have = 1;

@@ -105,6 +105,8 @@ def lib():
         L.ora_fit_subspace_ex.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(OraRandState),
                                           C.POINTER(C.c_int), u8p, f64p, C.c_int]
         L.ora_fit_subspace_ex.restype = C.c_int
+        L.ora_fit_subspace_counts.argtypes = L.ora_fit_subspace_ex.argtypes + [C.POINTER(C.c_int)]
+        L.ora_fit_subspace_counts.restype = C.c_int
         L.ora_subspace_data.argtypes = [f32p, C.c_int, C.c_int, f32p]
         _lib = L
     return _lib
@@ -343,3 +345,18 @@ def fit_subspace(traj: np.ndarray, num_motions: int, sigma: float, st: OraRandSt
                                   cols.ctypes.data_as(C.POINTER(C.c_int)), _p(out, C.c_uint8), _p(res, C.c_double),
                                   int(precision))
     return dict(n_outliers=n, columns=cols, is_outlier=out[:N], residuals=res[:N])
+
+
+def fit_subspace_counts(traj: np.ndarray, num_motions: int, sigma: float, st: OraRandState, precision: int = 0):
+    """fit_subspace plus counts (50,) int32: every hypothesis's inlier count in drawing order
+    (ora_fit_subspace_counts); counts stay -1 when the arguments are rejected."""
+    traj = np.ascontiguousarray(traj, dtype=np.float32)
+    N, T = traj.shape[:2]
+    cols = np.full(4 * num_motions, -1, np.int32)
+    out = np.zeros(max(N, 1), np.uint8)
+    res = np.zeros(max(N, 1), np.float64)
+    counts = np.full(50, -1, np.int32)
+    n = lib().ora_fit_subspace_counts(_p(traj, C.c_float), N, T, num_motions, sigma, C.byref(st),
+                                      cols.ctypes.data_as(C.POINTER(C.c_int)), _p(out, C.c_uint8), _p(res, C.c_double),
+                                      int(precision), counts.ctypes.data_as(C.POINTER(C.c_int)))
+    return dict(n_outliers=n, columns=cols, is_outlier=out[:N], residuals=res[:N], counts=counts)
