@@ -229,6 +229,24 @@ void MotionDetectionNode::cluster_vectors(const std::vector<double>& vectors, Fr
                                    &r->num_active_vectors, &r->num_clusters, r->kept_clusters.data(),
                                    r->rectangles.data(), max_kept, nkept);
     });
+    if (!p_.cluster_contours) return;
+    std::vector<float> pts((size_t)2 * n);                      // cv::Point2f(vec[0], vec[1]) (node.cpp:382)
+    for (int i = 0; i < n; i++) pts[2 * i] = (float)vectors[4 * (size_t)i], pts[2 * i + 1] = (float)vectors[4 * (size_t)i + 1];
+    cluster_hulls(pts, r);
+}
+
+// showClusterContours' cv::convexHull of every kept cluster (optical_flow_visualizer.cpp:204-221) of the
+// clustering that has just filled r's labels and kept ids; points: one (x, y) per label
+void MotionDetectionNode::cluster_hulls(const std::vector<float>& points, FrameResult* r)
+{
+    const int n = (int)r->cluster_labels.size(), k = (int)r->kept_clusters.size();
+    int total = 0;
+    r->contour_offsets.assign((size_t)k + 1, 0);
+    r->contours.assign((size_t)2 * n, 0);                       // a hull has at most as many vertices as members
+    const int rc = mdx_cluster_hulls(ctx_, points.data(), r->cluster_labels.data(), n, r->kept_clusters.data(), k,
+                                     r->contour_offsets.data(), r->contours.data(), n, &total);
+    if (rc < 0) throw std::runtime_error(std::string("mdx_cluster_hulls: ") + mdx_last_error(ctx_));
+    r->contours.resize((size_t)2 * total);
 }
 
 // runOpticalFlowTrajectory (node.cpp:94-110) over the nimg ring frames already on the device, and,
@@ -318,6 +336,7 @@ void MotionDetectionNode::cluster_points(FrameResult* r)
                                      r->cluster_labels.data(), &r->num_clusters, r->kept_clusters.data(),
                                      r->rectangles.data(), max_kept, nkept);
     });
+    if (p_.cluster_contours) cluster_hulls(r->outlier_points, r);
 }
 
 std::vector<double> grid_vectors(const std::vector<double>& vi, int w, int h, int ps)

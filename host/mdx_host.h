@@ -76,6 +76,11 @@ struct Params {
     // DESIGN.md §7h).  include_zeros: findOutliers' argument
     bool detect_outliers = false;
     bool include_zeros = false;
+    // showClusterContours' convex hull of every kept cluster (node.cpp:393 live, :510 run();
+    // optical_flow_visualizer.cpp:204-221) behind each clustering stage that ran (mdx_cluster_hulls,
+    // DESIGN.md §7j).  Off by default: the reference's writeContour loop (:426-429) is commented out, and
+    // drawing the hulls (drawContours, the published cluster_image) is out of scope
+    bool cluster_contours = false;
 
     // Whether each optional stage runs on a processed frame (the conditions documented above, written
     // once: the node's stages and mdx_node's output files both ask here)
@@ -116,6 +121,11 @@ struct StageOutputs {
     // the four fields above are filled the same way, cluster_labels per grid vector in the reference's
     // visiting order (image rows outer), -1 for a vector without flow
     int num_active_vectors = 0;                     // grid vectors with a non-zero flow
+    // cluster_contours: the convex hull of each kept cluster, in kept_clusters' order, whichever clustering
+    // stage filled the fields above; hull i's vertices (x, y) are contours[2 * contour_offsets[i] ..
+    // 2 * contour_offsets[i + 1]), in cv::convexHull(.., clockwise=false)'s order (include/mdx.h)
+    std::vector<int32_t> contour_offsets;           // kept_clusters.size() + 1 entries
+    std::vector<int32_t> contours;
 };
 
 // One processed frame's outputs (what the node hands to its publishers / logs).
@@ -187,6 +197,7 @@ private:
     void stage_subspace(int nimg, FrameResult* r);
     void stage_point_clusters(FrameResult* r);
     void cluster_vectors(const std::vector<double>& vectors, FrameResult* r);
+    void cluster_hulls(const std::vector<float>& points, FrameResult* r);
     template <class Entry> void cluster_and_trim(const char* name, int n, FrameResult* r, Entry entry);
     void publish(const std::string& topic, const Image& img) const;
 

@@ -19,6 +19,8 @@
 //                                      entering it halved on the device (:470-474), and run_once() is called once
 //                                      after every delivered frame, a deterministic stand-in for the polling loop)
 //            [residual_threshold=0.2] (use_all_frames=0: fitSubspace's threshold (:491); its num_motions is 2 there)
+//            [cluster_contours=0]     (the convex hull of every kept cluster, showClusterContours' (:393, :510),
+//                                      behind each clustering stage that ran)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -54,8 +56,13 @@
 //   motion.log                    log_contours=1: created at start; MotionLogger::writeBoundingBox of
 //                                 every kept cluster's rectangle (node.cpp:431-434), "frame, id, tl.x,
 //                                 tl.y, br.x, br.y" with frame = the node's global_frame_count_ during
-//                                 that callback and id the index among the kept clusters.  (writeContour,
-//                                 :426-429, needs the convex hulls, which are out of scope.)
+//                                 that callback and id the index among the kept clusters; with
+//                                 cluster_contours=1, behind a frame's rectangle lines,
+//                                 MotionLogger::writeContour of every kept cluster's hull (:426-429), "frame,
+//                                 id, x, y, x, y, ..."
+// With cluster_contours=1 every cluster file (clusters, vclusters, outliers) ends in the hulls of its kept
+// clusters, behind the rectangles: i32 offsets[num_kept + 1]; i32 xy[offsets[num_kept]][2] -- hull i's
+// vertices are xy[offsets[i] .. offsets[i + 1]), in cv::convexHull(.., clockwise=false)'s order (include/mdx.h).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -150,6 +157,7 @@ int main(int argc, char** argv)
         p.include_zeros = geti("include_zeros", 0) != 0;
         p.use_all_frames = geti("use_all_frames", 1) != 0;
         p.residual_threshold = getd("residual_threshold", 0.2);
+        p.cluster_contours = geti("cluster_contours", 0) != 0;
         const bool polling = !p.use_all_frames;
         const int device = geti("device", 0);
         const std::string out = argv[2];
@@ -185,12 +193,22 @@ int main(int argc, char** argv)
             const bool live = p.live_path || polling;
             const std::string sfx = "_" + std::to_string(k) + ".bin";
             const int32_t num_kept = (int32_t)r.kept_clusters.size();
-            // labels, kept ids and rectangles: the tail of every cluster file, then the rectangles' log lines
+            // labels, kept ids and rectangles (cluster_contours: and the hulls): the tail of every cluster file,
+            // then the rectangles' and the hulls' log lines
             auto put_clusters = [&](ByteBuffer& b) {
                 b.put(r.cluster_labels);
                 b.put(r.kept_clusters);
                 b.put(r.rectangles);
                 log_rectangles(r.rectangles.data(), 4, r.kept_clusters.size());
+                if (!p.cluster_contours) return;
+                if (r.contour_offsets.empty()) r.contour_offsets.assign(1, 0);   // the stage did not run: no cluster
+                b.put(r.contour_offsets);
+                b.put(r.contours);
+                if (!ml || polling) return;   // run() logs nothing
+                for (size_t i = 0; i + 1 < r.contour_offsets.size(); i++)
+                    ml->write_contour(std::vector<int>(r.contours.begin() + 2 * r.contour_offsets[i],
+                                                       r.contours.begin() + 2 * r.contour_offsets[i + 1]),
+                                      (int)node.global_frame_count() - 1, (int)i);
             };
             const int traj_len = r.trajectories.empty() ? 0 : (int)r.trajectories[0].size() / 2;
             ByteBuffer res{r.num_vectors, r.rc, r.w, r.h, r.npts, (int32_t)r.trajectories.size(), traj_len,

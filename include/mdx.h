@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 10   /* 2: mdx_params.call_pipelining, mdx_input_ready.
+#define MDX_ABI_VERSION 11  /* 2: mdx_params.call_pipelining, mdx_input_ready.
                                 3: mdx_lk_fallbacks; mdx_params grew ransac_iters, ransac_thresh and
                                    ransac_seed (16 more bytes: a caller built against ABI 2 passes a
                                    shorter struct); mdx_sync / mdx_device_sync return MDX_OK after an
@@ -40,7 +40,8 @@ extern "C" {
                                 9: mdx_find_outliers and mdx_outlier_stats (a new entry; mdx_params is
                                    unchanged, 80 bytes).
                                 10: mdx_half_size, mdx_resize_half_dev, mdx_resize_half and
-                                   mdx_ring_push_half (new entries; mdx_params is unchanged, 80 bytes). */
+                                   mdx_ring_push_half (new entries; mdx_params is unchanged, 80 bytes).
+                                11: mdx_cluster_hulls (a new entry; mdx_params is unchanged, 80 bytes). */
 
 /* Return codes */
 #define MDX_OK           0
@@ -463,6 +464,50 @@ int mdx_cluster_vectors(mdx_ctx* ctx, const double* vectors, int n, double dista
                         int* num_kept);
 
 /*
+ * Convex hulls of clusters: replaces cv::convexHull of every kept cluster in
+ * showClusterContours (common/src/optical_flow_visualizer.cpp:204-221; showFlowClusters :123-135
+ * takes the same hull), which the node calls after clusterEuclidean / getClusters
+ * (motion_detection_node.cpp:393 live, :510 run()) and whose hulls MotionLogger::writeContour
+ * would log (:426-429, commented out in the reference).
+ *   points [n][2] float host and labels [n]: the members and the cluster of each, as
+ *   mdx_cluster_euclidean returns `labels`; for mdx_cluster_vectors' clusters pass (float)x, (float)y
+ *   of every vector (node.cpp:382) with its `labels`.  ids [k]: the clusters wanted, strictly
+ *   ascending -- what those entries return as `kept`, or any subset.  Members whose label is not in
+ *   ids, and label -1, take no part.
+ *   Conversion: cv::Mat(cluster).copyTo(vector<cv::Point>), exactly mdx_cluster_euclidean's for the
+ *   rectangles: cvRound, half to even, float -> int32.
+ *   Vertices: the extreme points of the converted set.  Duplicates count once; a point on the
+ *   segment between two other members is not a vertex (collinear boundary points are excluded).  One
+ *   distinct point gives 1 vertex, members that are all collinear give the 2 end points.
+ *   Order: cv::convexHull(.., clockwise=false) -- counter-clockwise in a frame whose y axis points
+ *   up.  The first vertex is the lexicographically greatest (greatest x, then greatest y); the hull
+ *   runs along its max-y side to the lexicographically smallest vertex and along its min-y side
+ *   back.  Not closed: the first vertex is not repeated.
+ *   The vertex set is determined mathematically.  The start and the orientation are restated from
+ *   OpenCV 2.4's documentation and source as recalled and, like the entries above, unpinned against
+ *   a real build (no OpenCV to compare with).  All arithmetic is integer and exact; no tolerance
+ *   exists anywhere.  Cross products are taken in int64, so converted coordinates are limited to
+ *   |v| <= 2^29 (differences <= 2^30, products <= 2^60).
+ * Outputs:
+ *   offsets      [k+1] hull j's vertices are xy[offsets[j] .. offsets[j+1]); always complete
+ *   xy           [<= max_vertices][2] int32 x, y: the first max_vertices vertices of the hulls, packed
+ *                in the order of ids (may be NULL when max_vertices is 0)
+ *   num_vertices (may be NULL) all vertices = offsets[k]; may exceed max_vertices
+ * k == 0 or n == 0 is MDX_OK with all offsets zero.  MDX_EINVAL: a null context; n, k or max_vertices
+ * negative; n > MDX_CLUSTER_MAX_POINTS; a needed pointer NULL (offsets; points and labels with n > 0; ids
+ * with k > 0; xy with max_vertices > 0); ids not strictly ascending, or negative; an id with no
+ * member; a non-finite coordinate (of any member); a converted coordinate of a taking-part member
+ * beyond +-2^29; a requested cluster spanning more than MDX_HULL_MAX_SPAN pixel columns (8192 covers
+ * an 8K frame).  The host groups the members by cluster, O(n log k); the column extremes, the chains
+ * and the vertex order are the device's, one workgroup per cluster and one launch per call, with no
+ * size limit per cluster below MDX_CLUSTER_MAX_POINTS.  Scratch belongs to the context and only
+ * grows.  Synchronous.  There is no CPU fallback.
+ */
+#define MDX_HULL_MAX_SPAN 8192
+int mdx_cluster_hulls(mdx_ctx* ctx, const float* points, const int32_t* labels, int n, const int32_t* ids, int k,
+                      int32_t* offsets, int32_t* xy, int max_vertices, int* num_vertices);
+
+/*
  * Flow-vector outliers by median and median absolute deviation: replaces
  * OutlierDetector::findOutliers and getOutlierVectors (common/src/outlier_detector.cpp:37-186), the
  * pair path's detector, which the node would run on calculateOpticalFlow's Vec4d image in front of
@@ -571,7 +616,9 @@ int mdx_memcpy_d2h(mdx_ctx* ctx, void* dst, const void* src, size_t bytes);
  * mdx_enable_timing(ctx, 1) (re)starts recording; every later pipeline call records one
  * event set (up to 256 calls).  mdx_stage_ms returns the SUM over the recorded calls, in
  * milliseconds, of stage: 0 gray+pad, 1 pyramids, 2 Scharr, 3 LK, 4 classify+fit,
- * 5 warp+diff, 6 whole call; mdx_timing_calls returns how many calls were recorded. */
+ * 5 warp+diff, 6 whole call; mdx_timing_calls returns how many calls were recorded.
+ * mdx_cluster_hulls records a set too: stage 0 its upload, 3 k_hull, 4 its readback, 6 the three
+ * together (1, 2 and 5 are empty). */
 int mdx_enable_timing(mdx_ctx* ctx, int on);
 int mdx_timing_calls(const mdx_ctx* ctx);
 int mdx_stage_ms(mdx_ctx* ctx, int stage, float* ms);

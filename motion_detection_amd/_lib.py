@@ -32,6 +32,7 @@ VCLUSTER_ABS_INT = 1          # include/mdx.h MDX_VCLUSTER_ABS_INT
 VCLUSTER_MAX_POINTS = 131072  # include/mdx.h MDX_VCLUSTER_MAX_POINTS
 OUTLIERS_INCLUDE_ZEROS = 1    # include/mdx.h MDX_OUTLIERS_INCLUDE_ZEROS
 OUTLIERS_MAX_POINTS = 131072  # include/mdx.h MDX_OUTLIERS_MAX_POINTS
+HULL_MAX_SPAN = 8192          # include/mdx.h MDX_HULL_MAX_SPAN
 
 # every symbol include/mdx.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -47,13 +48,14 @@ EXPORTED = [
     "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
     "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions", "mdx_cluster_vectors",
     "mdx_find_outliers", "mdx_half_size", "mdx_resize_half_dev", "mdx_resize_half", "mdx_ring_push_half",
+    "mdx_cluster_hulls",
 ]
-ABI_VERSION = 10  # include/mdx.h MDX_ABI_VERSION
+ABI_VERSION = 11  # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_internal.h", "mdx_ctx.h", "mdx_dev.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp",
            "mdx_post.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "mdx_resize.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "mdx_resize.hip", "mdx_hull.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -258,6 +260,8 @@ def lib() -> C.CDLL:
     L.mdx_cluster_vectors.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.mdx_cluster_vectors.restype = C.c_int
+    L.mdx_cluster_hulls.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.mdx_cluster_hulls.restype = C.c_int
     L.mdx_find_outliers.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.mdx_find_outliers.restype = C.c_int
     L.mdx_mask_regions_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp,

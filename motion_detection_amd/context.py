@@ -95,6 +95,7 @@ class FlowResult:
     vector_clusters: list = field(default_factory=list)   # getClusters' kept clusters, (n_k, 4) float64 each
     clusters: list = field(default_factory=list)          # their points, (n_k, 2) float32 each
     rectangles: list = field(default_factory=list)        # their (x, y, width, height), as cv::Rect
+    contours: list = field(default_factory=list)          # their convex hulls, (v_k, 2) int32 each (cluster_contours)
 
 
 @dataclass
@@ -370,6 +371,25 @@ class Context:
                                               C.byref(nact), C.byref(nall), _ptr(kept), _ptr(rects), cap,
                                               C.byref(nkept)))
         return VectorClusterResult(labels, nact.value, nall.value, *_trim_kept(nkept.value, cap, kept, rects), nkept.value)
+
+    # -- convex hulls of clusters (drop-in for showClusterContours' cv::convexHull of every kept cluster)
+    def cluster_hulls(self, points: np.ndarray, labels: np.ndarray, ids) -> list:
+        """points (n, 2) float32 and labels (n,): the members and each one's cluster, as cluster_euclidean
+        returns `labels` (for cluster_vectors' clusters: every vector's (x, y) and its `labels`); ids: the
+        clusters wanted, strictly ascending (`kept`, or a subset).  Returns one (v_k, 2) int32 array per
+        id: the hull's vertices in cv::convexHull(.., clockwise=false)'s order (include/mdx.h)."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        want = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        n, k = pts.shape[0], want.shape[0]
+        if lab.shape[0] != n:
+            raise ValueError("labels must hold one entry per point")
+        offsets = np.zeros(k + 1, np.int32)
+        xy = np.zeros((n, 2), np.int32)               # a hull has at most as many vertices as members
+        total = C.c_int(0)
+        self._check(lib().mdx_cluster_hulls(self._h, _ptr(pts), _ptr(lab), n, _ptr(want), k, _ptr(offsets),
+                                            _ptr(xy) if n else None, n, C.byref(total)))
+        return [xy[offsets[j]:offsets[j + 1]].copy() for j in range(k)]
 
     # -- median / MAD outliers of the flow vectors (drop-in for OutlierDetector::findOutliers + getOutlierVectors)
     def find_outliers(self, vectors: np.ndarray, include_zeros: bool = False) -> "OutlierResult":

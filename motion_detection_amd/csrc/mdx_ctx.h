@@ -119,6 +119,9 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     std::vector<double> vc_host;             // its staging of the active vectors' planes: only ever grows
     std::vector<float> vc_pts;               // the active vectors' (x, y) as float, for the rectangles
     std::vector<int32_t> vc_idx;             // active vector -> input index, then the compact labels
+    DevBuf hlin, hlout;                      // mdx_cluster_hulls: records + grouped members, counts + staged hulls
+    std::vector<int32_t> hl_in, hl_out;      // their host images: only ever grow
+    std::vector<int32_t> hl_idx;             // each member's requested cluster (-1: none), then the fill cursors
     DevBuf olin, olmag, olout;               // findOutliers: (dx, dy) planes + angles, magnitudes, stats + flags
     std::vector<double> ol_host;             // its staging of the planes: only ever grows
     std::vector<uint8_t> ol_flags;           // the flags when the caller takes only the vectors
@@ -162,6 +165,18 @@ inline int set_err(mdx_ctx* c, int code, const char* fmt, ...)
         if (e_ != hipSuccess)                                                                  \
             return set_err((c), MDX_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
+
+// mdx_enable_timing: event i (0 .. 6) of the timed call in flight, recorded on st (default: the context's
+// stream); i == 0 opens the call's event set.  Nothing unless timing is on.
+inline void mark(mdx_ctx* c, int i, hipStream_t st = nullptr)
+{
+    if (!c->timing || c->ev.empty()) return;
+    if (i == 0) {
+        c->cur = c->ncalls < (int)c->ev.size() / 7 ? c->ncalls : -1;
+        c->ncalls++;
+    }
+    if (c->cur >= 0) (void)hipEventRecord(c->ev[c->cur * 7 + i], st ? st : c->stream);
+}
 
 // buildOpticalFlowPyramid level count and the padded slab layout for a w x h frame.
 inline Geometry make_geometry(int w, int h, int max_level)

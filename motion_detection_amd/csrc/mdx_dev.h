@@ -1,6 +1,6 @@
 // mdx_dev.h -- device-only helpers shared by the stage kernel files (mdx_front.hip,
-// mdx_lk_point.hip, mdx_fit.hip): reflect-101 indexing, 4-byte-aligned vector loads, the gray
-// conversion.  Nothing host-visible: mdx_internal.h is the one host/device interface.
+// mdx_lk_point.hip, mdx_fit.hip, mdx_hull.hip): reflect-101 indexing, 4-byte-aligned vector loads, the
+// gray conversion, a workgroup scan.  Nothing host-visible: mdx_internal.h is the one host/device interface.
 #pragma once
 
 #include "mdx_internal.h"
@@ -39,6 +39,32 @@ __device__ __forceinline__ T gload(uintptr_t a)
 #else
     return *reinterpret_cast<const T*>(a);   // the host pass only type-checks device code
 #endif
+}
+
+// Exclusive prefix sum of v over a workgroup of T threads (a multiple of 64), in thread order; total
+// receives the sum.  wsum: T / 64 ints of LDS, free again on return.  Every thread must call it.
+template <int T>
+__device__ __forceinline__ int block_scan_exclusive(int v, int* wsum, int& total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < T / 64; i++) {
+        const int s = wsum[i];
+        if (i < w) off += s;
+        tot += s;
+    }
+    __syncthreads();
+    total = tot;
+    return off + inc - v;
 }
 
 __device__ __forceinline__ int gray_of(const uint8_t* s, int fmt)

@@ -1,5 +1,5 @@
 // mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
-// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip, mdx_resize.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip, mdx_resize.hip, mdx_hull.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
 // mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
@@ -415,6 +415,25 @@ size_t regions_scratch_bytes(int batch, int w, int h, RegionsScratch* lay = null
 hipError_t launch_mask_regions(hipStream_t s, int batch, const uint8_t* mask, int w, int h, int stride,
                                size_t frame_stride, int open3, int min_area, mdx_region* regions, int max_regions,
                                int32_t* num_all, int32_t* num_kept, int32_t* labels, uint8_t* mask_out, void* scratch);
+
+// cv::Mat(vector<Point2f>).copyTo(vector<cv::Point>): saturate_cast<int>(float) = cvRound, half to even.
+// The rectangles (mdx_post.cpp clusters_from_roots) and the hulls (host and k_hull) convert with this.
+__host__ __device__ inline int32_t cv_round(float v) { return (int32_t)lrint((double)v); }
+
+// Convex hulls of clusters (mdx_hull.hip k_hull): one workgroup per cluster, one launch
+// on s.  pts: the members grouped by cluster; recs [k]; max_ncols: the widest cluster's columns (<=
+// MDX_HULL_MAX_SPAN), which sizes the dynamic LDS (hull_lds_bytes: 12 B per column).  counts [k]: each
+// hull's vertices; staging: cluster c's vertices (x, y), in order, from pair out_off on (at most bound).
+struct HullCluster {
+    int32_t start, count;    // the cluster's members: pts[start .. start + count)
+    int32_t xmin, ncols;     // smallest converted x, and xmax - xmin + 1
+    int32_t out_off, bound;  // its slice of staging, in vertices: min(count, 2 * ncols) holds any hull
+    int32_t pad_[2];
+};
+static_assert(sizeof(HullCluster) == 32, "HullCluster: eight ints");
+size_t hull_lds_bytes(int ncols);
+hipError_t launch_hull(hipStream_t s, int k, const HullCluster* recs, const float* pts, int max_ncols,
+                       int32_t* counts, int32_t* staging);
 
 // Half-size ingest (mdx_resize.hip k_half): `batch` frames of w x h pixels of `channels`
 // (1 or 3) interleaved bytes halved to mdx_half_size(w, h), one launch on s (per kHalfMaxBatch frames).

@@ -173,16 +173,6 @@ static int wait_input(mdx_ctx* c, hipStream_t st)
     return MDX_OK;
 }
 
-static inline void mark(mdx_ctx* c, int i, hipStream_t st = nullptr)
-{
-    if (!c->timing || c->ev.empty()) return;
-    if (i == 0) {
-        c->cur = c->ncalls < (int)c->ev.size() / 7 ? c->ncalls : -1;
-        c->ncalls++;
-    }
-    if (c->cur >= 0) (void)hipEventRecord(c->ev[c->cur * 7 + i], st ? st : c->stream);
-}
-
 // The class-plane LK's scratch (mdx_ctx::Abuf), byte offsets: the A sums ([level][pair][point] float4,
 // from 0), the queue heads ([sub-batch][level][XCD] counters), the dataflow counters and flags
 // ([level][pair] + kLkFlagInts counters) and the points carried between levels (per level a

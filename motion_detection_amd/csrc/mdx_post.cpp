@@ -1,7 +1,7 @@
 // mdx_post.cpp -- what follows the flow: the reference's random stream, the trajectory subspace
 // fit (OutlierDetector::fitSubspace), Euclidean clustering (FlowClusterer::clusterEuclidean), flow
-// vectors clustered by distance and angle (getClusters), their median / MAD outliers (findOutliers)
-// and the pair path's mask labelled into regions (BackgroundSubtractor::getMotionContours' recipe).
+// vectors clustered by distance and angle (getClusters), the kept clusters' convex hulls
+// (showClusterContours), the flow vectors' median / MAD outliers (findOutliers) and the pair path's mask labelled into regions (BackgroundSubtractor::getMotionContours' recipe).
 #include "mdx_ctx.h"
 
 #include <cfloat>
@@ -108,8 +108,7 @@ static int clusters_from_roots(mdx_ctx* c, const char* who, const float* points,
         const int32_t r = root[i];
         if (r < 0 || (size_t)r > i || root[r] != r)
             return set_err(c, MDX_EHIP, "%s: inconsistent root %d of point %zu", who, r, i);
-        // cv::Mat(cluster).copyTo(vector<cv::Point>): saturate_cast<int>(float) = cvRound, half to even
-        const int32_t xi = (int32_t)std::lrint((double)points[2 * i]), yi = (int32_t)std::lrint((double)points[2 * i + 1]);
+        const int32_t xi = cv_round(points[2 * i]), yi = cv_round(points[2 * i + 1]);   // copyTo(vector<cv::Point>)
         if ((size_t)r == i) {
             rank[i] = nall++;
             size[i] = 1;
@@ -263,6 +262,116 @@ extern "C" int mdx_cluster_vectors(mdx_ctx* c, const double* vectors, int n, dou
     if (labels)
         for (size_t a = 0; a < N; a++) labels[idx[a]] = lab[a];
     if (num_active) *num_active = (int)N;
+    return MDX_OK;
+}
+
+// showClusterContours' cv::convexHull of each requested cluster (optical_flow_visualizer.cpp:204-221,
+// DESIGN.md §7j).  The host checks the input and, in the O(n) walk that clusters_from_roots' callers
+// already make, groups the members by cluster and takes each cluster's column range; the column
+// extremes, the chains and the ordered vertices are the device's (mdx_hull.hip), one launch.  The hulls
+// come back in one copy, each in its own slice of a staging block, and are packed behind `offsets` here.
+extern "C" int mdx_cluster_hulls(mdx_ctx* c, const float* points, const int32_t* labels, int n, const int32_t* ids,
+                                 int k, int32_t* offsets, int32_t* xy, int max_vertices, int* num_vertices)
+{
+    if (!c) return MDX_EINVAL;
+    if (n < 0 || k < 0 || max_vertices < 0) return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: negative n, k or max_vertices");
+    if (n > MDX_CLUSTER_MAX_POINTS)
+        return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: more than %d points", MDX_CLUSTER_MAX_POINTS);
+    if (!offsets || (n > 0 && (!points || !labels)) || (k > 0 && !ids) || (max_vertices > 0 && !xy))
+        return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: a needed pointer is NULL");
+    for (int j = 0; j < k; j++)
+        if (ids[j] < 0 || (j > 0 && ids[j] <= ids[j - 1]))
+            return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: ids[%d] = %d: ids must be non-negative and strictly ascending", j, ids[j]);
+    if (num_vertices) *num_vertices = 0;
+    if (k == 0 || n == 0) {
+        std::fill(offsets, offsets + k + 1, 0);
+        return MDX_OK;
+    }
+    if (k > n) return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: %d ids for %d members: an id has no member", k, n);
+    for (size_t i = 0; i < (size_t)2 * n; i++)
+        if (!std::isfinite(points[i]))
+            return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: point %zu has a non-finite coordinate", i / 2);
+    const size_t N = (size_t)n, K = (size_t)k;
+    try {
+        if (c->hl_idx.size() < N + K) c->hl_idx.resize(N + K);
+        if (c->hl_in.size() < 8 * K + 2 * N) c->hl_in.resize(8 * K + 2 * N);
+        if (c->hl_out.size() < K) c->hl_out.resize(K);
+    } catch (const std::bad_alloc&) {
+        return set_err(c, MDX_ENOMEM, "mdx_cluster_hulls: no host memory for %d points", n);
+    }
+    int32_t *cidx = c->hl_idx.data(), *fill = cidx + N;
+    HullCluster* rec = reinterpret_cast<HullCluster*>(c->hl_in.data());
+    float* grouped = reinterpret_cast<float*>(c->hl_in.data() + 8 * K);
+    std::vector<int32_t>& xmax = c->hl_out;           // [K] until the launch
+    for (size_t j = 0; j < K; j++) rec[j] = HullCluster{0, 0, INT32_MAX, 0, 0, 0, {0, 0}}, xmax[j] = INT32_MIN;
+    constexpr float kLim = 536870912.f;               // 2^29: cross products of differences stay in int64
+    for (size_t i = 0; i < N; i++) {
+        const int32_t* at = std::lower_bound(ids, ids + k, labels[i]);
+        if (labels[i] < 0 || at == ids + k || *at != labels[i]) {
+            cidx[i] = -1;
+            continue;
+        }
+        const float x = points[2 * i], y = points[2 * i + 1];
+        if (!(std::fabs(x) <= kLim) || !(std::fabs(y) <= kLim))   // floats there are integers: rounding changes nothing
+            return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: point %zu lies beyond +-2^29", i);
+        const size_t j = (size_t)(at - ids);
+        cidx[i] = (int32_t)j;
+        const int32_t xi = cv_round(x);
+        rec[j].count++;
+        rec[j].xmin = std::min(rec[j].xmin, xi);
+        xmax[j] = std::max(xmax[j], xi);
+    }
+    size_t members = 0, slots = 0;
+    int max_ncols = 0;
+    for (size_t j = 0; j < K; j++) {
+        if (rec[j].count == 0) return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: cluster %d has no member", ids[j]);
+        const long long span = (long long)xmax[j] - rec[j].xmin + 1;
+        if (span > MDX_HULL_MAX_SPAN)
+            return set_err(c, MDX_EINVAL, "mdx_cluster_hulls: cluster %d spans %lld columns, more than %d", ids[j], span,
+                           MDX_HULL_MAX_SPAN);
+        rec[j].ncols = (int32_t)span;
+        rec[j].start = (int32_t)members;
+        rec[j].out_off = (int32_t)slots;
+        rec[j].bound = (int32_t)std::min<long long>(rec[j].count, 2 * span);
+        fill[j] = rec[j].start;
+        members += (size_t)rec[j].count;
+        slots += (size_t)rec[j].bound;
+        max_ncols = std::max(max_ncols, rec[j].ncols);
+    }
+    for (size_t i = 0; i < N; i++)
+        if (cidx[i] >= 0) std::memcpy(grouped + 2 * (size_t)fill[cidx[i]]++, points + 2 * i, 8);
+    std::vector<int32_t>& out = c->hl_out;            // counts [K], then the staging block [slots][2]
+    try {
+        if (out.size() < K + 2 * slots) out.resize(K + 2 * slots);
+    } catch (const std::bad_alloc&) {
+        return set_err(c, MDX_ENOMEM, "mdx_cluster_hulls: no host memory for %zu vertices", slots);
+    }
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const size_t in_bytes = (8 * K + 2 * members) * 4, out_bytes = (K + 2 * slots) * 4;
+    if (const int rc = ensure_all(c, {{&c->hlin, in_bytes}, {&c->hlout, out_bytes}}); rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    int32_t *d_in = c->hlin.as<int32_t>(), *d_out = c->hlout.as<int32_t>();
+    // (mdx_enable_timing: stage 0 the upload, 3 k_hull, 4 the readback, 6 the three together)
+    mark(c, 0);
+    HIP_OR_RETURN(c, hipMemcpyAsync(d_in, c->hl_in.data(), in_bytes, hipMemcpyHostToDevice, s));
+    for (int i = 1; i <= 3; i++) mark(c, i);
+    HIP_OR_RETURN(c, launch_hull(s, k, reinterpret_cast<const HullCluster*>(d_in), reinterpret_cast<const float*>(d_in + 8 * K),
+                                 max_ncols, d_out, d_out + K));
+    mark(c, 4);
+    HIP_OR_RETURN(c, hipMemcpyAsync(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    for (int i = 5; i <= 6; i++) mark(c, i);
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    long long total = 0;
+    for (size_t j = 0; j < K; j++) {
+        const int32_t nv = out[j];
+        if (nv < 1 || nv > rec[j].bound) return set_err(c, MDX_EHIP, "mdx_cluster_hulls: cluster %d: %d vertices", ids[j], nv);
+        offsets[j] = (int32_t)total;
+        const long long room = std::min<long long>(nv, (long long)max_vertices - total);
+        if (room > 0) std::memcpy(xy + 2 * total, out.data() + K + 2 * (size_t)rec[j].out_off, (size_t)room * 8);
+        total += nv;
+    }
+    offsets[K] = (int32_t)total;
+    if (num_vertices) *num_vertices = (int)total;
     return MDX_OK;
 }
 

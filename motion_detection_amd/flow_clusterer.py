@@ -61,6 +61,19 @@ def bounding_rects(clusters) -> list:
     return out
 
 
+def hulls_of(clusters, context: Context) -> list:
+    """cv::convexHull of each cluster after cv::Mat(cluster).copyTo(vector<cv::Point>), as
+    showClusterContours takes it (optical_flow_visualizer.cpp:204-221): one (v_k, 2) int32 array per
+    cluster, in cv::convexHull(.., clockwise=false)'s order (include/mdx.h mdx_cluster_hulls).  For
+    callers that hold member lists, next to bounding_rects; every hull is computed on the device, in one
+    call on `context`.  An empty cluster has no hull and raises."""
+    members = [np.asarray(c, dtype=np.float32).reshape(-1, 2) for c in clusters]
+    if not members:
+        return []
+    labels = np.repeat(np.arange(len(members), dtype=np.int32), [len(m) for m in members])
+    return context.cluster_hulls(np.concatenate(members), labels, np.arange(len(members), dtype=np.int32))
+
+
 def grid_vectors(flow_vectors, pixel_step: int) -> np.ndarray:
     """The Vec4d image's grid as getClusters visits it (flow_clusterer.cpp:180-184): rows i = 0,
     pixel_step, .. outer, columns j inner -- y-major, unlike the x-major grid of the flow entries.
@@ -80,13 +93,14 @@ class FlowClusterer:
         self._ctx = context
         self._own = context is None
         self.last: ClusterResult | VectorClusterResult | None = None
+        self._last_points = None      # (n, 2) float32: the last call's members, one per entry of last.labels
 
     def clusterEuclidean(self, points, distance_threshold: float) -> list:
         pts = np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, 2)
         if self._ctx is None:
             self._ctx = Context(self._device, 64, 64, 1)
         res = self._ctx.cluster_euclidean(pts, float(distance_threshold), MIN_SIZE)
-        self.last = res
+        self.last, self._last_points = res, pts
         return clusters_from_labels(pts, res.labels, res.kept)
 
     def getClusters(self, flow_vectors, pixel_step: int, distance_threshold: float, angular_threshold: float,
@@ -96,8 +110,16 @@ class FlowClusterer:
         if self._ctx is None:
             self._ctx = Context(self._device, 64, 64, 1)
         res = self._ctx.cluster_vectors(vec, float(distance_threshold), float(angular_threshold), MIN_SIZE, abs_int)
-        self.last = res
+        self.last, self._last_points = res, vec[:, :2].astype(np.float32)   # cv::Point2f(vec[0], vec[1]) (node.cpp:382)
         return [vec[res.labels == int(k)] for k in res.kept]
+
+    def hulls(self) -> list:
+        """The convex hulls of the last call's kept clusters (showClusterContours' cv::convexHull,
+        optical_flow_visualizer.cpp:204-221): one (v_k, 2) int32 array per cluster of `last.kept`, computed
+        on the device (Context.cluster_hulls)."""
+        if self.last is None:
+            raise ValueError("hulls() follows clusterEuclidean or getClusters")
+        return self._ctx.cluster_hulls(self._last_points, self.last.labels, self.last.kept)
 
     def close(self):
         if self._ctx is not None and self._own:

@@ -37,6 +37,13 @@ out) and both thresholds set, the pair callback also runs MotionDetectionNode::d
 getOutlierVectors -> getClusters; the FlowResult then carries ``outlier_flags``, ``vector_clusters``,
 ``clusters`` and ``rectangles``, and under ``log_contours`` the rectangles are logged.
 
+With ``cluster_contours`` (off by default) every clustering stage above is followed by
+showClusterContours' convex hull of each kept cluster (:393, :510; optical_flow_visualizer.cpp:204-221),
+computed on the device (mdx_cluster_hulls): the result carries them as ``contours``, and
+under ``log_contours`` each is written with MotionLogger::writeContour behind the frame's rectangle
+lines (the reference's loop at :426-429 is commented out, hence the opt-in).  Drawing them
+(drawContours, the published cluster_image) is out of scope.
+
 With ``use_all_frames=False`` the callback only fills the ring (:262) and the reference's polling caller
 run() (:457-553) does the work: ``run_once()`` is one pass of its body (:464-529) and ``run()`` the loop.
 Every ring frame wider than 320 px is halved (cv::resize(img, out, Size(), 0.5, 0.5), :470-474) -- here
@@ -107,6 +114,7 @@ class LiveResult:
     rectangles: list = field(default_factory=list)   # their (x, y, width, height), as cv::Rect
     frame_number: int = 0                # global_frame_count_ of this callback (the log's frame column)
     vector_clusters: list = field(default_factory=list)   # getClusters' kept clusters, (n_k, 4) float64 each (no egomotion)
+    contours: list = field(default_factory=list)     # the clusters' convex hulls, (v_k, 2) int32 each (cluster_contours)
 
 
 class MotionDetectionNode:
@@ -129,7 +137,10 @@ class MotionDetectionNode:
                        "region_min_area": None, "region_open": True,
                        # the pair path's detector (detectOutliers, :112-160): off by default, the
                        # reference's call (:405) is commented out; include_zeros is findOutliers' argument
-                       "detect_outliers": False, "include_zeros": False}
+                       "detect_outliers": False, "include_zeros": False,
+                       # showClusterContours' convex hull of every kept cluster (node.cpp:393, :510):
+                       # off by default, the reference's writeContour loop (:426-429) is commented out
+                       "cluster_contours": False}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -174,6 +185,21 @@ class MotionDetectionNode:
         for k, rect in enumerate(rects):
             self.logger.writeBoundingBox(rect, self.global_frame_count, k)
 
+    def _contours(self, fc, log: bool = True) -> list:
+        """showClusterContours' cv::convexHull of every kept cluster of fc's last call (node.cpp:393, :510)
+        under ``cluster_contours``, on the device; each is logged with MotionLogger::writeContour(hull,
+        frame, i) (:426-429) behind the rectangles' lines when log_contours and a log_path are set (log False:
+        run(), which writes no motion.log)."""
+        if not self.params.get("cluster_contours"):
+            return []
+        hulls = fc.hulls()
+        if log and self.params.get("log_contours") and self.params.get("log_path"):
+            if self.logger is None:
+                self.logger = MotionLogger(self.params["log_path"])
+            for k, hull in enumerate(hulls):
+                self.logger.writeContour(hull, self.global_frame_count, k)
+        return hulls
+
     @property
     def trajectory_size(self) -> int:
         # node.cpp:241-245
@@ -213,7 +239,7 @@ class MotionDetectionNode:
                                                       None, float(self.params["min_vector_size"]))
         ego = bool(self.params["egomotion"])
         thr, athr = self.params.get("distance_threshold"), self.params.get("angular_threshold")
-        outliers, subspace, vector_clusters, rectangles = [], [], [], []
+        outliers, subspace, vector_clusters, rectangles, contours = [], [], [], [], []
         if trajectories and ego:                                                                      # :341-348
             subspace = self._detector().fitSubspace(trajectories, outliers, int(self.params["num_motions"]),
                                                     float(self.params["sigma"]))
@@ -227,9 +253,10 @@ class MotionDetectionNode:
         if clusters is not None:
             rectangles = bounding_rects(clusters)                                                     # :395
             self._log_rectangles(rectangles)                                                          # :431-434
+            contours = self._contours(self._clusterer())                                              # :393
         self.frames_processed += 1
         res = LiveResult(num, vec, trajectories, outliers, subspace, clusters or [], rectangles, self.global_frame_count,
-                         vector_clusters)
+                         vector_clusters, contours)
         if self.on_result is not None:
             self.on_result(res)
         return res
@@ -275,7 +302,7 @@ class MotionDetectionNode:
         trajectories: list = []
         num = self.ofc.ring_trajectory(w, h, len(msgs), vec, trajectories, int(self.params["pixel_step"]),
                                        float(self.params["min_vector_size"]))                        # :488
-        outliers, subspace, clusters, rectangles = [], [], [], []
+        outliers, subspace, clusters, rectangles, contours = [], [], [], [], []
         thr = self.params.get("distance_threshold")
         if trajectories:
             subspace = self._detector().fitSubspace(trajectories, outliers, 2,
@@ -284,8 +311,10 @@ class MotionDetectionNode:
                 clusters = self._clusterer().clusterEuclidean(np.asarray(outliers, np.float32).reshape(-1, 2),
                                                               float(thr))                            # :497
                 rectangles = bounding_rects(clusters)
+                contours = self._contours(self._clusterer(), log=False)                              # :510
         self.frames_processed += 1
-        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters, rectangles, self.global_frame_count)
+        res = LiveResult(num, vec, trajectories, outliers, subspace, clusters, rectangles, self.global_frame_count,
+                         contours=contours)
         if self.on_result is not None:
             self.on_result(res)
         return res
@@ -324,6 +353,7 @@ class MotionDetectionNode:
         res.clusters = [c[:, :2].astype(np.float32) for c in res.vector_clusters]
         res.rectangles = bounding_rects(res.clusters)
         self._log_rectangles(res.rectangles)
+        res.contours = self._contours(fc)
 
     def run_optical_flow(self, image1: np.ndarray, image2: np.ndarray):
         """runOpticalFlow (node.cpp:76-92)."""
