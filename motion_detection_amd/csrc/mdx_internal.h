@@ -227,9 +227,12 @@ struct TrajChain {
 hipError_t launch_lk_chain(hipStream_t s, const LkArgs& a, const TrajChain& t, int ppw);
 // Trajectory subspace RANSAC (fitSubspace): mean-subtracted data, nhyp hypotheses of d columns
 // (cols: [nhyp][d]), winner's residuals / outlier flags; best[0] = winner or -1.  Scratch: data
-// [N][2T] floats + 2 (the means), qbuf [nhyp][2T][2T-d] doubles (MDX_SUBSPACE_F32: [nhyp][2T][2T] floats), counts [nhyp].
+// [N][2T] floats + 2 (the means), basis [nhyp] x subspace_basis_bytes(2T, d, precision), counts [nhyp].
+// One hypothesis kernel and one final kernel, instantiated for the mode precision selects.
+// subspace_basis_bytes: one hypothesis' basis, [2T][2T-d] doubles (MDX_SUBSPACE_F32: [2T][2T] floats).
+size_t subspace_basis_bytes(int n, int d, int precision);
 hipError_t launch_subspace(hipStream_t s, const float* traj, int N, int T, int d, const int* cols, int nhyp,
-                           double sigma, float* data, double* qbuf, int* counts, double* residuals,
+                           double sigma, float* data, void* basis, int* counts, double* residuals,
                            uint8_t* is_outlier, int* best, int precision);
 // Greedy Euclidean clustering (clusterEuclidean, mdx_cluster.hip): root[i] = index of the first point
 // of point i's cluster.  pts [N][2]; slim: a squared distance s joins iff its float bits < slim

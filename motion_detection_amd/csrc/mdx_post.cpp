@@ -56,7 +56,7 @@ extern "C" int mdx_fit_subspace(mdx_ctx* c, const float* traj, int ntraj, int tr
     std::vector<int> cols((size_t)kHyp * d);
     for (auto& v : cols) v = mdx_rand(rng) % ntraj;   // fillSubset, hypothesis by hypothesis (:223-230)
     const size_t N = (size_t)ntraj;
-    const size_t qb = std::max((size_t)n * std::max(n - d, 1) * 8, (size_t)n * n * 4);   // F64 basis / F32 Pnd
+    const size_t qb = subspace_basis_bytes(n, d, c->prm.subspace_precision);
     const int rc = ensure_all(c, {{&c->straj, N * n * 4}, {&c->sdata, (N * n + 2) * 4},   // + the two means
                                   {&c->sq, (size_t)kHyp * qb}, {&c->scnt, kHyp * 4}, {&c->scols, cols.size() * 4},
                                   {&c->sres, N * 8}, {&c->sout, N}, {&c->sbest, 4}});
@@ -65,7 +65,7 @@ extern "C" int mdx_fit_subspace(mdx_ctx* c, const float* traj, int ntraj, int tr
     HIP_OR_RETURN(c, hipMemcpyAsync(c->straj.p, traj, N * n * 4, hipMemcpyHostToDevice, s));
     HIP_OR_RETURN(c, hipMemcpyAsync(c->scols.p, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, s));
     HIP_OR_RETURN(c, launch_subspace(s, c->straj.as<float>(), ntraj, traj_len, d, c->scols.as<int>(), kHyp, sigma,
-                                     c->sdata.as<float>(), c->sq.as<double>(), c->scnt.as<int>(), c->sres.as<double>(),
+                                     c->sdata.as<float>(), c->sq.p, c->scnt.as<int>(), c->sres.as<double>(),
                                      c->sout.as<uint8_t>(), c->sbest.as<int>(), c->prm.subspace_precision));
     std::vector<uint8_t> out(N);
     int best = -1;

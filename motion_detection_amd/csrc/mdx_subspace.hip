@@ -12,11 +12,12 @@
 //             > sigma^2 chi2_99[n - d] (:312-323)                            -> k_subspace_final
 //
 // Precision MDX_SUBSPACE_F64 (default) as above; MDX_SUBSPACE_F32 follows the reference's float
-// arithmetic shape instead (explicit float Pnd, see k_subspace_hyp_f32).
-// One workgroup per hypothesis: lane 0 factors the tiny n x d sample (n <= 32) in double, the
-// workgroup then streams all N columns (2n MACs each) and reduces its inlier count.  The double
-// arithmetic follows the oracle's restatement (oracle/mdx_oracle.c subspace_basis /
-// subspace_residual) operation for operation, un-fused, so both round identically.
+// arithmetic shape instead (explicit float Pnd, residual |x' (Pnd x)|).  The two modes are the
+// policies SubF64 / SubF32 (element type, basis size, build, residual); k_subspace_hyp<P> and
+// k_subspace_final<P> are written once, and so are the Householder factorisation and the columns
+// of Q (householder_wave<T>, q_column<T>) both modes' bases come from.  The arithmetic follows the
+// oracle's restatement (oracle/mdx_oracle.c) operation for operation, un-fused, so both round
+// identically.
 #include "mdx_internal.h"
 
 #include <algorithm>
@@ -129,14 +130,8 @@ __global__ __launch_bounds__(256) void k_subspace_center(const float* __restrict
     }
 }
 
-// Householder QR of the n x d sample and the last n - d columns of Q (the oracle's subspace_basis
-// statement for statement); A, V column-major with leading dimension n.
-// The same statements on the 64 lanes of one wave: lane 0 forms each reflector (norm, v, beta) as
-// above, then every lane applies it to its own columns c = k + lane, k + lane + 64, ... and
-// builds its own columns of Q2 -- each column's dot product and update in the order above, so
-// the results are identical; only the independent columns run side by side (the factorisation
-// by one lane was the hypothesis kernel's serial critical path).  A wave's LDS accesses complete
-// in order; the fences keep the compiler from moving them across the hand-offs.
+// A wave's LDS accesses complete in order; the fences keep the compiler from moving them across the
+// hand-offs between lane 0 and the other lanes.
 __device__ __forceinline__ void lane_lds_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -144,179 +139,154 @@ __device__ __forceinline__ void lane_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ void subspace_basis_wave(double* A, int n, int d, double* V, double* beta, double* q2, int lane)
+__device__ __forceinline__ double sqrt_of(double v) { return __builtin_sqrt(v); }
+__device__ __forceinline__ float sqrt_of(float v) { return __builtin_sqrtf(v); }
+
+// Householder QR of the n x d sample in T, the oracle's subspace_basis / subspace_pnd_f32 statement
+// for statement; A, V column-major with leading dimension n, reflector k in column k of V (rows
+// k..n-1), beta[k] = v'v.  On the 64 lanes of one wave: lane 0 forms each reflector (norm, v, beta),
+// then every lane applies it to its own columns c = k + lane, k + lane + 64, ... -- each column's
+// dot product and update in the serial order, so the results are identical; only the independent
+// columns run side by side (the factorisation by one lane was the hypothesis kernel's serial
+// critical path).
+template <typename T>
+__device__ void householder_wave(T* A, int n, int d, T* V, T* beta, int lane)
 {
     for (int k = 0; k < d; k++) {
         if (lane == 0) {
-            double nrm2 = 0.0;
+            T nrm2 = T(0);
             for (int r = k; r < n; r++) nrm2 = nrm2 + A[k * n + r] * A[k * n + r];
-            const double nrm = __builtin_sqrt(nrm2);
-            const double x0 = A[k * n + k];
-            const double alpha = x0 >= 0.0 ? -nrm : nrm;
+            const T nrm = sqrt_of(nrm2);
+            const T x0 = A[k * n + k];
+            const T alpha = x0 >= T(0) ? -nrm : nrm;
             for (int r = k; r < n; r++) V[k * n + r] = A[k * n + r];
             V[k * n + k] = x0 - alpha;
-            double b = 0.0;
+            T b = T(0);
             for (int r = k; r < n; r++) b = b + V[k * n + r] * V[k * n + r];
             beta[k] = b;
         }
         lane_lds_sync();
-        const double b = beta[k];
-        if (b != 0.0) {
+        const T b = beta[k];
+        if (b != T(0)) {
             for (int c = k + lane; c < d; c += 64) {
-                double dot = 0.0;
+                T dot = T(0);
                 for (int r = k; r < n; r++) dot = dot + V[k * n + r] * A[c * n + r];
-                const double f = 2.0 * dot / b;
+                const T f = T(2) * dot / b;
                 for (int r = k; r < n; r++) A[c * n + r] = A[c * n + r] - f * V[k * n + r];
             }
         }
         lane_lds_sync();
     }
-    for (int j = d + lane; j < n; j += 64) {
-        double* q = q2 + (j - d) * n;
-        for (int r = 0; r < n; r++) q[r] = r == j ? 1.0 : 0.0;
-        for (int k = d - 1; k >= 0; k--) {
-            if (beta[k] == 0.0) continue;
-            double dot = 0.0;
-            for (int r = k; r < n; r++) dot = dot + V[k * n + r] * q[r];
-            const double f = 2.0 * dot / beta[k];
-            for (int r = k; r < n; r++) q[r] = q[r] - f * V[k * n + r];
+}
+
+// Column j of Q = H_0 ... H_{d-1}: q = e_j, then the reflectors d-1 ... 0.  One lane per column.
+template <typename T>
+__device__ void q_column(const T* V, const T* beta, int n, int d, int j, T* q)
+{
+    for (int r = 0; r < n; r++) q[r] = r == j ? T(1) : T(0);
+    for (int k = d - 1; k >= 0; k--) {
+        if (beta[k] == T(0)) continue;
+        T dot = T(0);
+        for (int r = k; r < n; r++) dot = dot + V[k * n + r] * q[r];
+        const T f = T(2) * dot / beta[k];
+        for (int r = k; r < n; r++) q[r] = q[r] - f * V[k * n + r];
+    }
+}
+
+// The two precision modes: the element type, the size of a hypothesis' basis, how one wave builds
+// it from the sample A (n x d, factored in place; V, beta: the reflectors) and a trajectory's
+// residual against it.  Both follow the oracle (oracle/mdx_oracle.c) operation for operation.
+
+// MDX_SUBSPACE_F64: basis = Q2, the last n - d columns of Q (column-major, n x (n-d));
+// residual = ||Q2' x||^2 in double (the oracle's subspace_basis / subspace_residual).
+struct SubF64 {
+    using T = double;
+    static __host__ __device__ int basis_elems(int n, int d) { return n * (n - d); }
+    static __device__ __forceinline__ void build(T* A, int n, int d, T* V, T* beta, T* q2, int lane)
+    {
+        householder_wave(A, n, d, V, beta, lane);
+        for (int j = d + lane; j < n; j += 64) q_column(V, beta, n, d, j, q2 + (j - d) * n);
+    }
+    static __device__ __forceinline__ double residual(const T* q2, int n, int d, const float* x)
+    {
+        double res = 0.0;
+        for (int j = 0; j < n - d; j++) {
+            double p = 0.0;
+            for (int r = 0; r < n; r++) p = p + q2[j * n + r] * (double)x[r];
+            res = res + p * p;
+        }
+        return res;
+    }
+};
+
+// MDX_SUBSPACE_F32: the reference's float arithmetic shape -- basis = Pnd = I - sum_j u_j u_j' formed
+// explicitly (outlier_detector.cpp:272-282; n x n row-major), u_j the first d columns of Q; residual
+// = |x' (Pnd x)| as the two float products of :286 (the oracle's subspace_pnd_f32 /
+// subspace_residual_f32).
+struct SubF32 {
+    using T = float;
+    static __host__ __device__ int basis_elems(int n, int d) { return n * n; }
+    static __device__ __forceinline__ void build(T* A, int n, int d, T* V, T* beta, T* P, int lane)
+    {
+        householder_wave(A, n, d, V, beta, lane);
+        // the factored sample is not read again: its n x d storage takes the d columns of Q
+        T* Q = A;
+        for (int j = lane; j < d; j += 64) q_column(V, beta, n, d, j, Q + j * n);
+        lane_lds_sync();
+        // one entry per lane, each summed over j in ascending order from 0 as the oracle's
+        // Pnd = Pnd + u_j u_j' does entry by entry
+        for (int e = lane; e < n * n; e += 64) {
+            const int a = e / n, b = e - a * n;
+            T p = 0.0f;
+            for (int j = 0; j < d; j++) p = p + Q[j * n + a] * Q[j * n + b];
+            P[e] = (a == b ? 1.0f : 0.0f) - p;
         }
     }
-}
-
-__device__ __forceinline__ double subspace_residual(const double* q2, int n, int m, const float* x)
-{
-    double res = 0.0;
-    for (int j = 0; j < m; j++) {
-        double p = 0.0;
-        for (int r = 0; r < n; r++) p = p + q2[j * n + r] * (double)x[r];
-        res = res + p * p;
-    }
-    return res;
-}
-
-// Float mode (MDX_SUBSPACE_F32): the reference's float arithmetic shape -- the sample's Householder
-// basis in float, Pnd = I - sum_idx u u' formed explicitly (outlier_detector.cpp:272-282) and the
-// residual |x' (Pnd x)| as the two float products of :286.  Statement for statement the oracle's
-// subspace_pnd_f32 / subspace_residual_f32 (oracle/mdx_oracle.c), un-fused.  P: n x n row-major.
-__device__ void subspace_pnd_f32(float* A, int n, int d, float* V, float* beta, float* q, float* P)
-{
-    for (int k = 0; k < d; k++) {
-        float nrm2 = 0.0f;
-        for (int r = k; r < n; r++) nrm2 = nrm2 + A[k * n + r] * A[k * n + r];
-        const float nrm = __builtin_sqrtf(nrm2);
-        const float x0 = A[k * n + k];
-        const float alpha = x0 >= 0.0f ? -nrm : nrm;
-        for (int r = k; r < n; r++) V[k * n + r] = A[k * n + r];
-        V[k * n + k] = x0 - alpha;
-        float b = 0.0f;
-        for (int r = k; r < n; r++) b = b + V[k * n + r] * V[k * n + r];
-        beta[k] = b;
-        if (b == 0.0f) continue;
-        for (int c = k; c < d; c++) {
-            float dot = 0.0f;
-            for (int r = k; r < n; r++) dot = dot + V[k * n + r] * A[c * n + r];
-            const float f = 2.0f * dot / b;
-            for (int r = k; r < n; r++) A[c * n + r] = A[c * n + r] - f * V[k * n + r];
+    static __device__ __forceinline__ double residual(const T* P, int n, int d, const float* x)
+    {
+        float res = 0.0f;
+        for (int a = 0; a < n; a++) {
+            float y = 0.0f;
+            for (int b = 0; b < n; b++) y = y + P[a * n + b] * x[b];
+            res = res + x[a] * y;
         }
+        return (double)__builtin_fabsf(res);
     }
-    for (int e = 0; e < n * n; e++) P[e] = 0.0f;
-    for (int j = 0; j < d; j++) {
-        for (int r = 0; r < n; r++) q[r] = r == j ? 1.0f : 0.0f;
-        for (int k = d - 1; k >= 0; k--) {
-            if (beta[k] == 0.0f) continue;
-            float dot = 0.0f;
-            for (int r = k; r < n; r++) dot = dot + V[k * n + r] * q[r];
-            const float f = 2.0f * dot / beta[k];
-            for (int r = k; r < n; r++) q[r] = q[r] - f * V[k * n + r];
-        }
-        for (int a = 0; a < n; a++)
-            for (int b = 0; b < n; b++) P[a * n + b] = P[a * n + b] + q[a] * q[b];
-    }
-    for (int a = 0; a < n; a++)
-        for (int b = 0; b < n; b++) P[a * n + b] = (a == b ? 1.0f : 0.0f) - P[a * n + b];
-}
+};
 
-__device__ __forceinline__ float subspace_residual_f32(const float* P, int n, const float* x)
+size_t subspace_basis_bytes(int n, int d, int precision)
 {
-    float res = 0.0f;
-    for (int a = 0; a < n; a++) {
-        float y = 0.0f;
-        for (int b = 0; b < n; b++) y = y + P[a * n + b] * x[b];
-        res = res + x[a] * y;
-    }
-    return __builtin_fabsf(res);
+    return precision == MDX_SUBSPACE_F32 ? SubF32::basis_elems(n, d) * sizeof(SubF32::T)
+                                         : SubF64::basis_elems(n, d) * sizeof(SubF64::T);
 }
 
-// float mode of k_subspace_hyp: pbuf [nhyp][n][n] floats (each hypothesis' Pnd)
-__global__ __launch_bounds__(256) void k_subspace_hyp_f32(const float* __restrict__ data, int N, int n, int d,
-                                                           const int* __restrict__ cols, double inlier_thr,
-                                                           float* __restrict__ pbuf, int* __restrict__ counts)
-{
-    __shared__ float sA[kMaxSub * kMaxSub], sV[kMaxSub * kMaxSub], sbeta[kMaxSub], sq[kMaxSub];
-    __shared__ float sP[kMaxSub * kMaxSub];
-    __shared__ int s_cnt[4];
-    const int h = blockIdx.x, tid = threadIdx.x;
-    const int i0 = (int)((long long)N * blockIdx.y / gridDim.y), i1 = (int)((long long)N * (blockIdx.y + 1) / gridDim.y);
-    for (int e = tid; e < n * d; e += 256) {
-        const int k = e / n, r = e - k * n;
-        sA[e] = data[(long long)cols[h * d + k] * n + r];
-    }
-    __syncthreads();
-    if (tid == 0) subspace_pnd_f32(sA, n, d, sV, sbeta, sq, sP);
-    __syncthreads();
-    if (blockIdx.y == 0)
-        for (int e = tid; e < n * n; e += 256) pbuf[(long long)h * n * n + e] = sP[e];
-    int cnt = 0;
-    for (int i = i0 + tid; i < i1; i += 256)
-        if ((double)subspace_residual_f32(sP, n, data + (long long)i * n) < inlier_thr) cnt++;
-    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) atomicAdd(counts + h, s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
-}
-
-__global__ __launch_bounds__(256) void k_subspace_final_f32(const float* __restrict__ data, int N, int n, int nhyp,
-                                                             const int* __restrict__ counts,
-                                                             const float* __restrict__ pbuf, double out_thr,
-                                                             double* __restrict__ residuals,
-                                                             uint8_t* __restrict__ is_outlier, int* __restrict__ best)
-{
-    int bh = -1, bc = 0;
-    for (int h = 0; h < nhyp; h++)
-        if (counts[h] > bc) { bc = counts[h]; bh = h; }
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) best[0] = bh;
-    if (i >= N) return;
-    double r = 0.0;
-    if (bh >= 0) r = (double)subspace_residual_f32(pbuf + (long long)bh * n * n, n, data + (long long)i * n);
-    if (residuals) residuals[i] = r;
-    is_outlier[i] = (uint8_t)(bh >= 0 && r > out_thr);
-}
-
-// grid: one workgroup per hypothesis.  cols: [nhyp][d] sample indices; qbuf: [nhyp][n][n-d];
-// counts: [nhyp] inliers.
+// grid: (hypothesis, slice of the trajectories), one workgroup each.  cols: [nhyp][d] sample
+// indices; basis: [nhyp][P::basis_elems] (written by slice 0); counts: [nhyp] inliers, zeroed.
+// Wave 0 builds the basis of the tiny n x d sample (n <= 32) in LDS, the workgroup then streams its
+// slice's columns and adds its inlier count.
+template <class P>
 __global__ __launch_bounds__(256) void k_subspace_hyp(const float* __restrict__ data, int N, int n, int d,
                                                        const int* __restrict__ cols, double inlier_thr,
-                                                       double* __restrict__ qbuf, int* __restrict__ counts)
+                                                       typename P::T* __restrict__ basis, int* __restrict__ counts)
 {
-    __shared__ double sA[kMaxSub * kMaxSub], sV[kMaxSub * kMaxSub], sbeta[kMaxSub];
-    __shared__ double sq[kMaxSub * kMaxSub];
+    using T = typename P::T;
+    __shared__ T sA[kMaxSub * kMaxSub], sV[kMaxSub * kMaxSub], sbeta[kMaxSub];
+    __shared__ T sB[kMaxSub * kMaxSub];
     __shared__ int s_cnt[4];
-    const int h = blockIdx.x, tid = threadIdx.x, m = n - d;
+    const int h = blockIdx.x, tid = threadIdx.x, nb = P::basis_elems(n, d);
     const int i0 = (int)((long long)N * blockIdx.y / gridDim.y), i1 = (int)((long long)N * (blockIdx.y + 1) / gridDim.y);
     for (int e = tid; e < n * d; e += 256) {
         const int k = e / n, r = e - k * n;
-        sA[e] = (double)data[(long long)cols[h * d + k] * n + r];
+        sA[e] = (T)data[(long long)cols[h * d + k] * n + r];
     }
     __syncthreads();
-    if (tid < 64) subspace_basis_wave(sA, n, d, sV, sbeta, sq, tid);
+    if (tid < 64) P::build(sA, n, d, sV, sbeta, sB, tid);
     __syncthreads();
     if (blockIdx.y == 0)
-        for (int e = tid; e < n * m; e += 256) qbuf[(long long)h * n * m + e] = sq[e];
+        for (int e = tid; e < nb; e += 256) basis[(long long)h * nb + e] = sB[e];
     int cnt = 0;
     for (int i = i0 + tid; i < i1; i += 256)
-        if (subspace_residual(sq, n, m, data + (long long)i * n) < inlier_thr) cnt++;
+        if (P::residual(sB, n, d, data + (long long)i * n) < inlier_thr) cnt++;
     for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
     if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
     __syncthreads();
@@ -325,9 +295,10 @@ __global__ __launch_bounds__(256) void k_subspace_hyp(const float* __restrict__ 
 
 // Winner = the first hypothesis with the largest positive count; its residual per trajectory and
 // the outlier flags.  best[0] = winner index or -1 (no hypothesis had an inlier).
+template <class P>
 __global__ __launch_bounds__(256) void k_subspace_final(const float* __restrict__ data, int N, int n, int d,
                                                          int nhyp, const int* __restrict__ counts,
-                                                         const double* __restrict__ qbuf, double out_thr,
+                                                         const typename P::T* __restrict__ basis, double out_thr,
                                                          double* __restrict__ residuals,
                                                          uint8_t* __restrict__ is_outlier, int* __restrict__ best)
 {
@@ -337,15 +308,14 @@ __global__ __launch_bounds__(256) void k_subspace_final(const float* __restrict_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) best[0] = bh;
     if (i >= N) return;
-    const int m = n - d;
     double r = 0.0;
-    if (bh >= 0) r = subspace_residual(qbuf + (long long)bh * n * m, n, m, data + (long long)i * n);
+    if (bh >= 0) r = P::residual(basis + (long long)bh * P::basis_elems(n, d), n, d, data + (long long)i * n);
     if (residuals) residuals[i] = r;
     is_outlier[i] = (uint8_t)(bh >= 0 && r > out_thr);
 }
 
 hipError_t launch_subspace(hipStream_t s, const float* traj, int N, int T, int d, const int* cols, int nhyp,
-                           double sigma, float* data, double* qbuf, int* counts, double* residuals,
+                           double sigma, float* data, void* basis, int* counts, double* residuals,
                            uint8_t* is_outlier, int* best, int precision)
 {
     const int n = 2 * T;
@@ -364,17 +334,15 @@ hipError_t launch_subspace(hipStream_t s, const float* traj, int N, int T, int d
     // left 50 of 256 CUs streaming ~20K trajectories each at one wave per SIMD, latency-bound
     const int S = std::max(1, std::min(16, N / 1024));
     if (hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)nhyp, s)) return e;
-    if (precision == MDX_SUBSPACE_F32) {
-        float* pbuf = reinterpret_cast<float*>(qbuf);
-        hipLaunchKernelGGL(k_subspace_hyp_f32, dim3(nhyp, S), dim3(256), 0, s, data, N, n, d, cols, inlier_thr, pbuf,
-                           counts);
-        hipLaunchKernelGGL(k_subspace_final_f32, dim3((N + 255) / 256), dim3(256), 0, s, data, N, n, nhyp, counts,
-                           pbuf, out_thr, residuals, is_outlier, best);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_subspace_hyp, dim3(nhyp, S), dim3(256), 0, s, data, N, n, d, cols, inlier_thr, qbuf, counts);
-    hipLaunchKernelGGL(k_subspace_final, dim3((N + 255) / 256), dim3(256), 0, s, data, N, n, d, nhyp, counts, qbuf,
-                       out_thr, residuals, is_outlier, best);
+    auto fit = [&](auto mode) {
+        using P = decltype(mode);
+        auto* b = static_cast<typename P::T*>(basis);
+        hipLaunchKernelGGL(k_subspace_hyp<P>, dim3(nhyp, S), dim3(256), 0, s, data, N, n, d, cols, inlier_thr, b, counts);
+        hipLaunchKernelGGL(k_subspace_final<P>, dim3((N + 255) / 256), dim3(256), 0, s, data, N, n, d, nhyp, counts, b,
+                           out_thr, residuals, is_outlier, best);
+    };
+    if (precision == MDX_SUBSPACE_F32) fit(SubF32{});
+    else fit(SubF64{});
     return hipGetLastError();
 }
 

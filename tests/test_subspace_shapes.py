@@ -347,6 +347,19 @@ def test_gpu_slice_edges(mdx, ctxs, oracle, N, precision):
     assert r["counts"].max() > N // 2        # most trajectories are inliers: an edge one is, too
 
 
+@pytest.mark.gpu
+def test_gpu_modes_alternate_on_one_context(mdx, oracle):
+    """One context, subspace_precision switched between calls: the basis scratch is sized per call
+    from the mode's own layout.  Per hypothesis (T = 5, nm = 2) needs 160 B in F64 and 400 B in F32,
+    (T = 16, nm = 1) 7168 B and 4096 B; each mode's larger need follows its smaller one, and the
+    first three calls each outgrow the buffer the call before left."""
+    with mdx.Context(0, 64, 64, 1) as c:
+        for precision, (T, nm) in [(0, (5, 2)), (1, (5, 2)), (0, (16, 1)), (1, (16, 1))]:
+            c.set_params(subspace_precision=precision)
+            _, r = gpu_vs_oracle_counts(mdx, c, oracle, shape_scene(T)[:300], nm, SIGMA, 1, precision)
+            assert r["counts"].max() > 0 and r["columns"].min() >= 0      # a winner's basis was read back
+
+
 # --- float edges
 @pytest.mark.gpu
 def test_gpu_float_mode_subnormal_residuals(mdx, ctxs, oracle):
