@@ -1,6 +1,7 @@
-// mdx_dev.h -- device-only helpers shared by the stage kernel files (mdx_front.hip,
-// mdx_lk_point.hip, mdx_fit.hip, mdx_hull.hip): reflect-101 indexing, 4-byte-aligned vector loads, the
-// gray conversion, a workgroup scan.  Nothing host-visible: mdx_internal.h is the one host/device interface.
+// mdx_dev.h -- device-only helpers shared by the stage kernel files (mdx_front.hip, mdx_lk.hip,
+// mdx_lk_point.hip, mdx_hull.hip): reflect-101 indexing, 4-byte-aligned vector loads, the gray
+// conversion, the per-pixel Scharr stencil (k_scharr, k_scharr_levels, k_lk_class_fused), a workgroup
+// scan.  Nothing host-visible: mdx_internal.h is the one host/device interface.
 #pragma once
 
 #include "mdx_internal.h"
@@ -65,6 +66,25 @@ __device__ __forceinline__ int block_scan_exclusive(int v, int* wsum, int& total
     __syncthreads();
     total = tot;
     return off + inc - v;
+}
+
+// ---- the Scharr stencil (lkpyramid.cpp calcSharrDeriv), one pixel.  Vertical t0 = 3(a+c)+10b, t1 = c-a
+// over the rows above / at / below; horizontal Ix = t0[x+1]-t0[x-1], Iy = 3(t1[x-1]+t1[x+1])+10 t1[x].
+// OpenCV clamps the row/col neighbours as reflect-101 (row -1 -> 1, col cols -> cols-2), which is exactly
+// the padded level's border, so the stencil reads the padded image directly.  ra / rb / rc: three aligned
+// words of the three rows, the pixel at byte bc (1 <= bc <= 10).  Returns (uint16)Ix | (uint16)Iy << 16.
+__device__ __forceinline__ int u8_at(const uint32_t (&w)[3], int b) { return (int)((w[b >> 2] >> (8 * (b & 3))) & 255u); }
+
+__device__ __forceinline__ uint32_t scharr_word(const uint32_t (&ra)[3], const uint32_t (&rb)[3], const uint32_t (&rc)[3],
+                                                int bc)
+{
+    const int bm = bc - 1, bp = bc + 1;                              // bytes x-1, x+1
+    const int t0m = (u8_at(ra, bm) + u8_at(rc, bm)) * 3 + u8_at(rb, bm) * 10;
+    const int t0p = (u8_at(ra, bp) + u8_at(rc, bp)) * 3 + u8_at(rb, bp) * 10;
+    const int t1m = u8_at(rc, bm) - u8_at(ra, bm), t1c = u8_at(rc, bc) - u8_at(ra, bc), t1p = u8_at(rc, bp) - u8_at(ra, bp);
+    const int ix = t0p - t0m;
+    const int iy = (t1m + t1p) * 3 + t1c * 10;
+    return (uint32_t)(uint16_t)(int16_t)ix | ((uint32_t)(uint16_t)(int16_t)iy << 16);
 }
 
 __device__ __forceinline__ int gray_of(const uint8_t* s, int fmt)

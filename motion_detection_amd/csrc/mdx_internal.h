@@ -368,7 +368,7 @@ hipError_t launch_band_fit(hipStream_t s, int nrec, const mdx_band_cand* cands, 
 // Row bands: frame-1 gray rows [fit->src_y0, fit->src_y1) into the padded level 0 of pyr1 (the
 // band's warp may read rows its own pyramid build skipped), except the rows [built0, built1) the
 // pyramid build wrote.  gray1_l0: level-0 core, pitch bytes.
-hipError_t launch_gray_rows(hipStream_t s, const uint8_t* img1, int w, int h, int stride, int fmt, uint8_t* gray1_l0,
+hipError_t launch_gray_rows(hipStream_t s, const uint8_t* img1, int w, int stride, int fmt, uint8_t* gray1_l0,
                             int pitch, const PairFit* fit, int built0 = 0, int built1 = 0);
 hipError_t launch_set_fit_external(hipStream_t s, int batch, const double* H_external, PairFit* fits);
 // Destination rows [row0, row1) of every pair (row1 <= h); mask row y is at mask + (y - row0) * w.

@@ -39,7 +39,7 @@
 // product)).  Products/sums never go through a contracted FMA (-ffp-contract=off); k_lk_A's
 // explicit FMAs multiply operands whose product is exact in float (|Ix|, |Iy| <= 4080), so they
 // round like the separate multiply and add.
-#include "mdx_internal.h"
+#include "mdx_dev.h"
 
 #include <float.h>
 
@@ -52,9 +52,6 @@ namespace mdx {
 
 typedef short s2 __attribute__((ext_vector_type(2)));
 typedef float f2 __attribute__((ext_vector_type(2)));
-// 4-B aligned 8-byte loads (global_load_dwordx2 at dword-aligned addresses)
-struct __attribute__((aligned(4))) u2a4 { uint32_t x, y; };
-struct __attribute__((aligned(4))) u3a4 { uint32_t x, y, z; };
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int v3u __attribute__((ext_vector_type(3)));
 // raw buffer descriptor over [base, base + bytes) (cdna_hip_programming.md T8: built from
@@ -85,6 +82,8 @@ __device__ __forceinline__ int residue_of(const int16_t* rlist, int level, int a
     return rlist[(level * 2 + axis) * 128 + cls];
 }
 
+// The W_BITS 14 bilinear weights of (fa, fb).  mdx_lk_point.hip keeps its int4 form: with either form
+// shared, the other side's kernels change registers and opcodes (profiles/front_refactor_codegen_check.txt).
 __device__ __forceinline__ void lk_weights(float fa, float fb, int& w00, int& w01, int& w10, int& w11)
 {
     w00 = __float2int_rn((1.f - fa) * (1.f - fb) * 16384.f);
@@ -243,7 +242,7 @@ __global__ __launch_bounds__(256) void k_lk_class(const uint8_t* __restrict__ py
         uint32_t ib[2][2], dw[2][5];
 #pragma unroll
         for (int r = 0; r < 2; r++) {
-            const u2a4 bi = *reinterpret_cast<const u2a4*>(ip + (long long)r * p);
+            const u2a4k bi = *reinterpret_cast<const u2a4k*>(ip + (long long)r * p);
             ib[r][0] = bi.x; ib[r][1] = bi.y;
             const uint4 d4 = *reinterpret_cast<const uint4*>(dp + (long long)r * p);
             dw[r][0] = d4.x; dw[r][1] = d4.y; dw[r][2] = d4.z; dw[r][3] = d4.w;
@@ -270,13 +269,10 @@ __global__ __launch_bounds__(256) void k_lk_class(const uint8_t* __restrict__ py
 
 // Levels with at most 4 residue classes (the finest ones, whose Scharr planes are the largest):
 // the same elements, with the Scharr derivatives computed here from the padded level image instead
-// of read back from k_scharr's planes (lkpyramid.cpp calcSharrDeriv: t0 = 3(a+c)+10b, t1 = c-a,
-// Ix = t0[x+1]-t0[x-1], Iy = 3(t1[x-1]+t1[x+1])+10 t1[x]; the padded level's reflect-101 rows and
-// columns are OpenCV's neighbour clamping; 0 outside the level, the derivative planes' CONSTANT
-// border).  One thread serves every class of its pair from one set of row loads, and the level's
-// k_scharr launch (its plane writes and their reads) is skipped.
-__device__ __forceinline__ int u8_at(const uint32_t (&w)[3], int b) { return (int)((w[b >> 2] >> (8 * (b & 3))) & 255u); }
-
+// of read back from k_scharr's planes (scharr_word, mdx_dev.h: the stencil k_scharr applies; 0
+// outside the level, the derivative planes' CONSTANT border).  One thread serves every class of its
+// pair from one set of row loads, and the level's k_scharr launch (its plane writes and their reads)
+// is skipped.
 __global__ __launch_bounds__(256) void k_lk_class_fused(const uint8_t* __restrict__ pyr1, uint8_t* __restrict__ cls_out,
                                                         LkClassArgs a)
 {
@@ -301,7 +297,7 @@ __global__ __launch_bounds__(256) void k_lk_class_fused(const uint8_t* __restric
     for (int r = 0; r < 4; r++) {
         const int yy = y - 1 + r;
         const int ys = (yy < -kPad || yy >= L.h + kPad) ? y : yy;
-        const u3a4 t = *reinterpret_cast<const u3a4*>(I + (long long)ys * p + x0 - 4);
+        const u3a4k t = *reinterpret_cast<const u3a4k*>(I + (long long)ys * p + x0 - 4);
         rw[r][0] = t.x; rw[r][1] = t.y; rw[r][2] = t.z;
     }
     // derivative words at columns x0 .. x0+4 of rows y, y+1 (k_lk_class's dw)
@@ -312,17 +308,8 @@ __global__ __launch_bounds__(256) void k_lk_class_fused(const uint8_t* __restric
 #pragma unroll
         for (int c = 0; c < 5; c++) {
             const int x = x0 + c;
-            uint32_t d = 0;
-            if (yy >= 0 && yy < L.h && x >= 0 && x < L.w) {
-                const int bm = 3 + c, bc = 4 + c, bp = 5 + c;          // bytes x-1, x, x+1
-                const int t0m = (u8_at(rw[r], bm) + u8_at(rw[r + 2], bm)) * 3 + u8_at(rw[r + 1], bm) * 10;
-                const int t0p = (u8_at(rw[r], bp) + u8_at(rw[r + 2], bp)) * 3 + u8_at(rw[r + 1], bp) * 10;
-                const int t1m = u8_at(rw[r + 2], bm) - u8_at(rw[r], bm), t1c = u8_at(rw[r + 2], bc) - u8_at(rw[r], bc);
-                const int t1p = u8_at(rw[r + 2], bp) - u8_at(rw[r], bp);
-                const int ix = t0p - t0m, iy = (t1m + t1p) * 3 + t1c * 10;
-                d = (uint32_t)(uint16_t)(int16_t)ix | ((uint32_t)(uint16_t)(int16_t)iy << 16);
-            }
-            dw[r][c] = d;
+            const bool in = yy >= 0 && yy < L.h && x >= 0 && x < L.w;
+            dw[r][c] = in ? scharr_word(rw[r], rw[r + 1], rw[r + 2], 4 + c) : 0u;   // x is byte 4 + c
         }
     }
     // the image bytes of rows y, y+1 at columns x0 .. x0+4 (k_lk_class's ib): bytes 4 .. 8

@@ -596,9 +596,8 @@ extern "C" int mdx_band_fit_warp_dev(mdx_ctx* c, int nrec, const mdx_band_cand* 
     HIP_OR_RETURN(c, launch_band_fit(s, nrec, d_cands, fits, w, h, y0, y1));
     // the band's flow built frame 1's pyramid for its own rows only: the rows this band's warp
     // reads beyond them (the fit is known now) are converted from the frame
-    HIP_OR_RETURN(c, launch_gray_rows(s, c->band_img1, w, h, c->band_stride, c->band_fmt,
-                                      level0_core(c->band_pyr1, g), g.lv[0].pitch, fits, c->band_built[0],
-                                      c->band_built[1]));
+    HIP_OR_RETURN(c, launch_gray_rows(s, c->band_img1, w, c->band_stride, c->band_fmt, level0_core(c->band_pyr1, g),
+                                      g.lv[0].pitch, fits, c->band_built[0], c->band_built[1]));
     const WarpArgs wa = {pyr_gray(c->band_pyr1, g), pyr_gray(c->band_pyr2, g), w, h, fits, d_mask_band,
                          (long long)w * (y1 - y0), c->prm.thresh, y0, y1};
     if (const int rc = run_warp_diff(c, 1, wa); rc != MDX_OK) return rc;
