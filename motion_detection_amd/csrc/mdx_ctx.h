@@ -1,5 +1,5 @@
 // mdx_ctx.h -- the context behind the C-ABI (include/mdx.h) and what every host file (mdx_api.cpp, mdx_pair.cpp,
-// mdx_traj.cpp, mdx_post.cpp) needs of it: owning types, errors, workspace growth, geometry, the frame check.
+// mdx_traj.cpp, mdx_post.cpp) needs of it: owning types, errors, workspace growth, the frame check.
 #pragma once
 
 #include "../../include/mdx.h"
@@ -176,33 +176,6 @@ inline void mark(mdx_ctx* c, int i, hipStream_t st = nullptr)
         c->ncalls++;
     }
     if (c->cur >= 0) (void)hipEventRecord(c->ev[c->cur * 7 + i], st ? st : c->stream);
-}
-
-// buildOpticalFlowPyramid level count and the padded slab layout for a w x h frame.
-inline Geometry make_geometry(int w, int h, int max_level)
-{
-    Geometry g{};
-    int sw = w, sh = h;
-    long long img = 0, der = 0;
-    int lvl;
-    for (lvl = 0; lvl <= max_level; lvl++) {
-        Level& L = g.lv[lvl];
-        L.w = sw;
-        L.h = sh;
-        L.pitch = (kXOff + sw + kPad + 16 + 63) / 64 * 64;   // +16: slack for 16-B row loads
-        L.rows = kPad + sh + kPad;
-        L.img_off = img;
-        L.der_off = der;
-        img += (long long)L.pitch * L.rows;
-        der += (long long)L.pitch * L.rows;
-        g.nlev = lvl + 1;
-        sw = (sw + 1) / 2;
-        sh = (sh + 1) / 2;
-        if (sw <= kWin || sh <= kWin) break;
-    }
-    g.img_bytes = (img + 255) / 256 * 256;
-    g.der_words = (der + 63) / 64 * 64;
-    return g;
 }
 
 inline int ensure(mdx_ctx* c, DevBuf& b, size_t need)

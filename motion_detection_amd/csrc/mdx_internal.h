@@ -10,37 +10,17 @@
 #include <algorithm>
 
 #include "mdx.h"
+#include "mdx_plan.h"   // constants, Level / Geometry, the class plan: everything the host plans without a device
 
 namespace mdx {
 
-constexpr int kMaxLevels = 8;
+static_assert(sizeof(float4) == kFloat4Bytes, "lk_scratch sizes the A sums by it");
 // LK debug buffer (MDX_LK_DEBUG=1): after the per-point records, the traced point's iterations
 // (kMaxLevels * 64 float4), then per level and persistent wave of k_lk_iter its {start, end}
 // s_memrealtime stamps (100 MHz), for the wave-occupancy profile (scripts/lk_tail.py)
 constexpr int kLkDbgStampOff = kMaxLevels * 64 + 64;
 constexpr int kLkDbgWaves = 16384;
-constexpr int kWin = 40;     // LK window side (reference optical_flow_calculator.cpp:41)
-constexpr int kPad = 40;     // border rows/cols every pyramid level carries (= win)
-constexpr int kXOff = 64;    // left margin of a level row: the core starts 64-B aligned
 
-// One pyramid level inside a per-pair slab.  Images are u8; derivatives are uint32 words
-// holding (Ix int16 | Iy int16 << 16), the little-endian image of OpenCV's interleaved
-// CV_16SC2 derivative Mat.  Both use the same pitch (elements) and origin.
-struct Level {
-    int w, h;              // core size
-    int pitch;             // elements per row (>= kXOff + w + kPad, multiple of 64)
-    int rows;              // kPad + h + kPad
-    long long img_off;     // byte offset of the level's padded buffer in the u8 slab
-    long long der_off;     // word offset of the level's padded buffer in the deriv slab
-    __host__ __device__ long long core() const { return (long long)kPad * pitch + kXOff; }
-};
-
-struct Geometry {
-    int nlev;                // attained maxLevel + 1
-    Level lv[kMaxLevels];
-    long long img_bytes;     // bytes of one pyramid slab (all levels)
-    long long der_words;     // words of one derivative slab (all levels)
-};
 // the gray frame of a pair's pyramid slab: level 0's core, lv[0].pitch bytes per row
 inline uint8_t* level0_core(uint8_t* slab, const Geometry& g) { return slab + g.lv[0].img_off + g.lv[0].core(); }
 
@@ -53,57 +33,10 @@ struct PairFit {
     int src_y0, src_y1;   // row bands (k_band_fit): frame-1 rows the band's warp reads
 };
 
-// Residue-class planes of LK v2 (mdx_lk.hip): per level, one plane set per class of
-// (P_x mod 2^L, P_y mod 2^L) present in the grid.  Each class holds one row-major UH x PW array of
-// 8-B (D, C) pairs: D (uint32, Ix | Iy << 16) and C (int32, 256 - 512*I: the J-chain bias, see
-// mdx_lk.hip).
-struct ClassLevel {
-    int nrx, nry;            // residue classes per axis
-    int UH, PW;              // plane rows (h + 79), plane width in elements (multiple of 4)
-    long long off;           // byte offset of this level inside a pair's class slab
-    long long class_bytes;   // UH * PW * 8
-    int nxp;                 // length of the padded class-grouped column order (multiple of G)
-    int ord_off;             // offset of this level's order tables in LkArgs::ord
-    int G;                   // points per LK group (4 or 8)
-    int UW;                  // union columns per group (64, 128, 256 or 512)
-    int vlo, vhi;            // plane rows the planned grid rows' windows reach (k_lk_class range)
-    // A sums per row strip (k_lk_A_rows): the level's grid rows, in class order, cut into strips of
-    // at most kAStripRows rows of one y-class whose windows start every `asp` plane rows; 0: the
-    // per-group k_lk_A instead (spacing not uniform, or below 5 rows: too many windows overlap)
-    int asp;
-    int nstrip;              // strips (table at LkArgs::ord + strip_off: (first row index, rows) pairs)
-    int strip_off;
-};
-constexpr int kAStripRows = 16;
-
-// Floor of the LK window origin of grid index gi (column or row) at a level: the reference's
-// prevPt * 2^-level - 19.5 in float.  The host plan (which plane rows and columns exist) and the
-// kernels (which are read) must agree on it bit for bit: floorf of the same float operands.
-__host__ __device__ inline int lk_win_origin(int gi, int pixel_step, int level)
-{
-    return (int)floorf((float)(gi * pixel_step) * (float)(1. / (1 << level)) - 19.5f);
-}
-// First class-plane row of the window with origin row ipy: planes carry kPad rows above the level,
-// and a window is clamped into the UH plane rows.
-__host__ __device__ inline int lk_win_row0(int ipy, int UH) { return std::min(std::max(ipy + kPad, 0), UH - kWin); }
-
-// (G, UW) shapes of the LK level kernels (mdx_lk.hip instantiates these; the host plan picks the
-// smallest UW >= a level's union span among the shapes of its G)
-#define LK_SHAPES LK_CASE(4, 48) LK_CASE(4, 56) LK_CASE(4, 64) LK_CASE(4, 72) LK_CASE(4, 80) LK_CASE(4, 96) \
-    LK_CASE(4, 128) LK_CASE(8, 80) LK_CASE(8, 112) LK_CASE(8, 128) LK_CASE(8, 256) LK_CASE(8, 512)
-constexpr int kLkUW4[] = {48, 56, 64, 72, 80, 96, 128};
-constexpr int kLkUW8[] = {80, 112, 128, 256, 512};
-
-struct ClassPlan {
-    ClassLevel lv[kMaxLevels];
-    long long bytes_per_pair;
-    int nch;                 // 0: some group's union is wider than 512 columns (single-kernel LK)
-};
-
 struct LkClassArgs {
     Geometry g;
     ClassPlan plan;
-    const int16_t* rlist;    // [level][axis][128] class index -> residue
+    const int16_t* rlist;    // [level][axis][kTabStride] class index -> residue
     int level;
 };
 
@@ -125,8 +58,8 @@ struct LkArgs {
     long long carry_lstride; // floats between two levels' carried-point arrays
     uint8_t* status;         // [batch][npts]
     ClassPlan plan;          // LK v2 only
-    const int16_t* cmap;     // [level][axis][128] residue -> class index
-    const int16_t* rlist;    // [level][axis][128] class index -> residue
+    const int16_t* cmap;     // [level][axis][kTabStride] residue -> class index
+    const int16_t* rlist;    // [level][axis][kTabStride] class index -> residue
     const int16_t* ord;      // per level: nxp padded grid columns (-1 = empty), then ny grid rows,
                              // both grouped by residue class (ClassLevel::ord_off)
     const float* prev_pts;   // k_lk only: [batch][npts][2] start points (trajectories); null = the grid
@@ -152,32 +85,14 @@ struct LkArgs {
                              // row body: [level][0] exact, [level][1] fused
 };
 
-// LK counters (queue heads per level and XCD, dataflow retire counts per level and pair): one per
-// 128-B line.  Packed, a line held the counters of several levels (or pairs) that concurrently
-// running launches update and poll, and the dataflow ran 1.4-3x slower wherever the batch did not
-// fill whole lines (8, 16, 24, 40 pairs) -- the concurrent launches contending on shared lines.
-constexpr int kCtrPad = 32;
 // default dataflow wait bound: s_sleep(8) polls, ~0.1 s
 constexpr int kLkSpinDefault = 1 << 19;
-// Dataflow fallback flags of one call (LkArgs::lflags, ints kCtrPad apart, zeroed with the retire
-// counters): level l's give-ups (a group wait or the gate before it gave up: the level's results may
-// be wrong), whether level l was recomputed (so every finer level must be too), and the queue heads
-// of the recompute launches ([level][XCD]).
-constexpr int kLkFlagGiveup = 0;
-constexpr int kLkFlagRedone = kMaxLevels;
-constexpr int kLkFlagQueue = 2 * kMaxLevels;
-constexpr int kLkFlagInts = kLkFlagQueue + 8 * kMaxLevels;
 // persistent waves of a recompute launch: cheap when it exits at once (the common case), and a
 // recompute of the finest level at 1080p x 32 still takes only tens of ms
 #ifndef MDX_LK_REDO_WAVES
 #define MDX_LK_REDO_WAVES 512
 #endif
 constexpr int kLkRedoWaves = MDX_LK_REDO_WAVES;
-
-// Core rows [lo, hi) of one pyramid level (row-band mode: what a band's LK reads)
-struct RowSpan {
-    int lo, hi;
-};
 
 // Launchers (mdx_front.hip; launch_lk: mdx_lk_point.hip).  All enqueue on `s`.
 // fsel: 0 both frames of every pair, 1 the first frame only, 2 the second frame only

@@ -72,14 +72,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc32(const void* base, u
     return __builtin_amdgcn_make_buffer_rsrc(p, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
-// residue-class tables: [level][axis][128]
+// residue-class tables: [level][axis][kTabStride]
 __device__ __forceinline__ int class_of(const int16_t* cmap, int level, int axis, int res)
 {
-    return cmap[(level * 2 + axis) * 128 + res];
+    return cmap[(level * 2 + axis) * kTabStride + res];
 }
 __device__ __forceinline__ int residue_of(const int16_t* rlist, int level, int axis, int cls)
 {
-    return rlist[(level * 2 + axis) * 128 + cls];
+    return rlist[(level * 2 + axis) * kTabStride + cls];
 }
 
 // The W_BITS 14 bilinear weights of (fa, fb).  mdx_lk_point.hip keeps its int4 form: with either form

@@ -8,159 +8,34 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <new>
 
 using namespace mdx;
 
-// Residue classes of the grid at each level (see mdx_lk.hip), the class-grouped point order and
-// the class-plane layout.  Rebuilt and uploaded only when frame size / pixel_step / levels change.
-// plan.nch == 0 means some group's union is wider than 512 columns (pixel_step >~ 66) or a pair's
-// class slab exceeds 2 GB: the caller then runs the single-kernel LK instead.
+// The context's class plan (mdx_plan.h build_class_plan) and its device side: the tables in ctab and
+// the class slab of `batch` pairs.  Rebuilt and uploaded only when frame size / pixel_step / levels /
+// band change.  plan.nch == 0: the caller runs the single-kernel LK instead.
 static int ensure_class_plan(mdx_ctx* c, const Geometry& g, int w, int h, int ps, int batch, int gy0, int gy1)
 {
     int rc;
     const std::array<int, 6> key = {w, h, ps, g.nlev, gy0, gy1};
     if (c->plan_key != key) {
-        const int nx = (w + ps - 1) / ps, ny = (h + ps - 1) / ps;
-        static_assert(kMaxLevels <= 8, "residue tables sized for 2^7 residues");
-        std::vector<int16_t> tab(2 * kMaxLevels * 2 * 128, (int16_t)-1);
-        std::vector<int16_t> ord;
-        int16_t* cmap = tab.data();
-        int16_t* rlist = tab.data() + kMaxLevels * 2 * 128;
-        ClassPlan P{};
-        bool usable = true;
-        for (int l = 0; l < g.nlev; l++) {
-            const int m = (1 << l) - 1;
-            int n[2] = {0, 0};
-            for (int axis = 0; axis < 2; axis++) {
-                const int cnt = axis == 0 ? nx : ny;
-                for (int i = 0; i < cnt; i++) {
-                    const int r = (i * ps) & m;
-                    int16_t& slot = cmap[(l * 2 + axis) * 128 + r];
-                    if (slot < 0) {
-                        slot = (int16_t)n[axis];
-                        rlist[(l * 2 + axis) * 128 + n[axis]] = (int16_t)r;
-                        n[axis]++;
-                    }
-                    if (n[axis] == m + 1) break;
-                }
-            }
-            ClassLevel& C = P.lv[l];
-            C.nrx = n[0];
-            C.nry = n[1];
-            // columns: each class's members in x order.  Group size per level: 4 points when a
-            // 4-group's union fits 64 columns (no extra union loads), else 8 (MDX_LK_G forces one)
-            C.ord_off = (int)ord.size();
-            const int16_t* cmx = cmap + (l * 2 + 0) * 128;
-            auto ipx_of = [&](int gx) { return lk_win_origin(gx, ps, l); };
-            std::vector<std::vector<int16_t>> runs(n[0]);
-            for (int i = 0; i < nx; i++) runs[cmx[(i * ps) & m]].push_back((int16_t)i);
-            auto union_of = [&](int G) {
-                int u = 0;
-                for (const auto& r : runs)
-                    for (size_t q = 0; q < r.size(); q += G)
-                        u = std::max(u, ipx_of(r[std::min(r.size(), q + G) - 1]) - ipx_of(r[q]) + kWin);
-                return u;
-            };
-            // group size 4 (less lockstep) unless 8 stages a row with fewer DMA pieces; union
-            // width = the smallest kernel shape that fits (MDX_LK_G=4/8 forces the group size)
-            const int u4 = union_of(4), u8 = union_of(8);
-            auto fit = [](const int* uws, int n, int u) {
-                for (int i = 0; i < n; i++)
-                    if (uws[i] >= u) return uws[i];
-                return 0;
-            };
-            const int uw4 = fit(kLkUW4, (int)(sizeof(kLkUW4) / sizeof(int)), u4);
-            const int uw8 = fit(kLkUW8, (int)(sizeof(kLkUW8) / sizeof(int)), u8);
-            // a row's staging cost goes by LDS-DMA pieces (1 KiB, one per 64 lanes x 16 B): the
-            // wave's union row is 4 slots x uw4 or 2 slots x uw8 pairs of 8 B
-            auto pieces = [](int slots, int uw) { return (slots * uw * 8 + 1023) / 1024; };
-            const bool g4 = c->lk_g == 4 ? uw4 > 0
-                          : c->lk_g == 8 ? false
-                          : uw4 > 0 && (uw8 == 0 || pieces(4, uw4) <= pieces(2, uw8));
-            if (g4) {
-                C.G = 4;
-                C.UW = uw4;
-            } else {
-                C.G = 8;
-                C.UW = uw8;
-            }
-            if (C.UW == 0) usable = false;
-            for (const auto& r : runs) {   // each run padded to a multiple of G with -1
-                ord.insert(ord.end(), r.begin(), r.end());
-                for (size_t q = r.size(); q % C.G; q++) ord.push_back((int16_t)-1);
-            }
-            C.nxp = (int)ord.size() - C.ord_off;
-            // rows of the band [gy0, gy1): grouped by class the same way (no padding: a group is
-            // one row)
-            const size_t r0 = ord.size();
-            for (int i = gy0; i < gy1; i++) ord.push_back((int16_t)i);
-            const int16_t* cmy = cmap + (l * 2 + 1) * 128;
-            std::stable_sort(ord.begin() + r0, ord.end(),
-                             [&](int16_t u, int16_t v) { return cmy[(u * ps) & m] < cmy[(v * ps) & m]; });
-            // A-sum strips (k_lk_A_rows): runs of one y-class cut into kAStripRows rows; the first
-            // window rows v0 = ipy + 40 of a class's rows must be evenly spaced (asp rows apart)
-            const size_t r1 = ord.size();
-            auto v0_row = [&](int gy) { return lk_win_origin(gy, ps, l) + kPad; };
-            int asp = 0;
-            bool uniform = true;
-            std::vector<int16_t> strips;
-            for (size_t i = r0; i < r1;) {
-                size_t e = i + 1;
-                const int cls = cmy[(ord[i] * ps) & m];
-                while (e < r1 && cmy[(ord[e] * ps) & m] == cls) {
-                    const int d = v0_row(ord[e]) - v0_row(ord[e - 1]);
-                    if (asp == 0) asp = d;
-                    if (d != asp) uniform = false;
-                    e++;
-                }
-                // small-batch contexts (C4 row bands: one pair per call) take short strips: more
-                // waves in flight for the few pairs' A sums, which then finish sooner (one band
-                // 1.196-1.197 against 1.217-1.226 ms at 16, profiles/r05_ab_astrip.txt); at batch 32
-                // 4..16 rows measured within noise
-                const size_t srows = c->lk_astrip > 0 ? (size_t)c->lk_astrip
-                                                      : (size_t)(c->max_batch <= 4 ? 4 : kAStripRows);
-                for (size_t s = i; s < e; s += srows) {
-                    strips.push_back((int16_t)(s - r0));
-                    strips.push_back((int16_t)std::min<size_t>(srows, e - s));
-                }
-                i = e;
-            }
-            if (asp == 0) asp = kWin;   // one row per class: windows never overlap
-            C.asp = uniform && asp >= 5 ? asp : 0;
-            C.nstrip = (int)strips.size() / 2;
-            C.strip_off = (int)ord.size();
-            ord.insert(ord.end(), strips.begin(), strips.end());
+        BuiltPlan B;
+        try {
+            B = build_class_plan(g, w, h, ps, gy0, gy1, PlanTuning{c->lk_g, c->lk_astrip, c->max_batch});
+        } catch (const std::bad_alloc&) {
+            return set_err(c, MDX_ENOMEM, "class plan: out of host memory");
         }
-        (void)ny;
-        long long off = 0;
-        for (int l = 0; l < g.nlev; l++) {
-            ClassLevel& C = P.lv[l];
-            C.UH = g.lv[l].h + 79;
-            C.PW = (g.lv[l].w + kPad + std::max(C.UW, 64) + 3) & ~3;
-            // plane rows the band's windows read: the first rows (lk_win_row0) of its first and
-            // last grid rows (the window origin is monotone in gy), 40 rows each
-            C.vlo = lk_win_row0(lk_win_origin(gy0, ps, l), C.UH);
-            C.vhi = lk_win_row0(lk_win_origin(gy1 - 1, ps, l), C.UH) + kWin;
-            C.class_bytes = (long long)C.UH * C.PW * 8;
-            C.off = off;
-            off += (long long)C.nrx * C.nry * C.class_bytes;
-        }
-        // the kernels address a pair's slab with 32-bit buffer offsets
-        if (off > 0x7fff0000LL) usable = false;
-        P.nch = usable ? 1 : 0;
-        P.bytes_per_pair = (off + 255) / 256 * 256;
-        tab.insert(tab.end(), ord.begin(), ord.end());
-        if ((rc = ensure(c, c->ctab, tab.size() * sizeof(int16_t))) != MDX_OK) return rc;
+        if ((rc = ensure(c, c->ctab, B.tab.size() * sizeof(int16_t))) != MDX_OK) return rc;
         // kernels of earlier calls may still read the old tables: the copy waits for them (the
         // stream is non-blocking, so a plain hipMemcpy would not)
         HIP_OR_RETURN(c, hipStreamSynchronize(c->stream));
-        HIP_OR_RETURN(c, hipMemcpy(c->ctab.p, tab.data(), tab.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-        c->plan = P;
+        HIP_OR_RETURN(c, hipMemcpy(c->ctab.p, B.tab.data(), B.tab.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        c->plan = B.plan;
         c->plan_key = key;
     }
     if (c->plan.nch == 0) return MDX_OK;
-    if ((rc = ensure(c, c->cls, (size_t)c->plan.bytes_per_pair * batch + 64)) != MDX_OK) return rc;
-    return MDX_OK;
+    return ensure(c, c->cls, (size_t)c->plan.bytes_per_pair * batch + 64);
 }
 
 // The next device call's first stage waits for the caller's input event (mdx_input_ready), once.
@@ -171,27 +46,6 @@ static int wait_input(mdx_ctx* c, hipStream_t st)
     c->input_ev = nullptr;
     HIP_OR_RETURN(c, hipStreamWaitEvent(st, e, 0));
     return MDX_OK;
-}
-
-// The class-plane LK's scratch (mdx_ctx::Abuf), byte offsets: the A sums ([level][pair][point] float4,
-// from 0), the queue heads ([sub-batch][level][XCD] counters), the dataflow counters and flags
-// ([level][pair] + kLkFlagInts counters) and the points carried between levels (per level a
-// [pair][point] float2 array of carry_level bytes, a multiple of 128: with the counter regions whole
-// 128-B lines and npts a multiple of 16 the arrays start on 128-B lines, which the dataflow requires),
-// then the product certificates ([level][pair][point] bytes, written and read with the A sums).
-struct LkScratch {
-    size_t qctr, done, carry, carry_level, cert, bytes;
-};
-static LkScratch lk_scratch(int nlev, int batch, int npts)
-{
-    LkScratch s;
-    s.qctr = (size_t)nlev * batch * npts * sizeof(float4);
-    s.done = s.qctr + (size_t)batch * kMaxLevels * 8 * kCtrPad * sizeof(int);
-    s.carry = s.done + ((size_t)kMaxLevels * batch + kLkFlagInts) * kCtrPad * sizeof(int);
-    s.carry_level = ((size_t)batch * npts * 8 + 127) / 128 * 128;
-    s.cert = s.carry + s.carry_level * nlev;
-    s.bytes = s.cert + (size_t)nlev * batch * npts;
-    return s;
 }
 
 // The LK of a batch of pairs on the context's stream.  Grid start points (a.prev_pts null) on a
@@ -222,8 +76,8 @@ int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int 
     a.flow_cap = c->lk_cap;
     a.fma = c->lk_fma ? 1 : 0;
     a.cmap = c->ctab.as<int16_t>();
-    a.rlist = c->ctab.as<int16_t>() + kMaxLevels * 2 * 128;
-    a.ord = c->ctab.as<int16_t>() + 2 * kMaxLevels * 2 * 128;
+    a.rlist = c->ctab.as<int16_t>() + kTabRlist;
+    a.ord = c->ctab.as<int16_t>() + kTabOrd;
     const int npts = a.npts;
     if (c->lk_debug) {
         if ((rc = ensure(c, c->dbg, ((size_t)npts * g.nlev * batch + kLkDbgStampOff + kMaxLevels * kLkDbgWaves) * 16)) !=
@@ -260,28 +114,6 @@ int mdx::run_lk(mdx_ctx* c, const Geometry& g, LkArgs& a, int batch, int w, int 
     L.prev_ready = prev_ready;
     HIP_OR_RETURN(c, launch_lk_v2(L, batch, a));
     return MDX_OK;
-}
-
-// Row-band mode: the previous frame's (pyr1) core rows a band's class planes read at each level --
-// padded rows [vlo - 1, vhi + 2) of the planes' source (k_lk_class_fused reads y-1 .. y+2, the
-// Scharr planes behind k_lk_class the same), reflect-101 border rows folded onto the core rows they
-// mirror -- and the rows the next level's pyrDown reads from it (pyramids.cpp: dst row r reads rows
-// 2r-2 .. 2r+2).  Only those rows of pyr1 are built; the next frame's pyramid stays whole, since J
-// may be read anywhere in it.
-static void band_rows(const Geometry& g, const ClassPlan& P, RowSpan* rows)
-{
-    for (int l = g.nlev - 1; l >= 0; l--) {
-        const int h = g.lv[l].h;
-        const int lo = P.lv[l].vlo - 1 - kPad, hi = P.lv[l].vhi + 2 - kPad;   // core coordinates
-        int clo = std::max(lo, 0), chi = std::min(hi, h);
-        if (lo < 0) chi = std::max(chi, std::min(h, 1 - lo));                 // rows lo..-1 mirror 1..-lo
-        if (hi > h) clo = std::min(clo, std::max(0, 2 * h - 1 - hi));         // rows h..hi-1 mirror down to 2h-1-hi
-        if (l + 1 < g.nlev) {
-            clo = std::min(clo, std::max(0, 2 * rows[l + 1].lo - 2));
-            chi = std::max(chi, std::min(h, 2 * rows[l + 1].hi + 2));
-        }
-        rows[l] = RowSpan{clo, std::max(clo, chi)};
-    }
 }
 
 // The warp+diff stage of every entry, on c->stream: k_warp_prep's scratch, the launch, and its
@@ -374,7 +206,7 @@ static int run_pipeline(mdx_ctx* c, const PipelineArgs& A)
     const uint8_t *d_img1 = A.d_img1, *d_img2 = A.d_img2;
     const long long fs = (long long)A.frame_stride;
     // a row band (batch 1): the rows of the previous frame's pyramid its class planes read
-    RowSpan rows[kMaxLevels];
+    RowSpan rows[kMaxLevels] = {};   // band_built_rows reads rows[1] on a one-level pyramid too
     const RowSpan* prows = nullptr;
     if (cand && c->lk_impl == 2 && npts > 0 && nyb > 0 && nyb < ny) {
         if ((rc = ensure_class_plan(c, g, w, h, P.pixel_step, batch, gy0, gy1)) != MDX_OK) return rc;
@@ -383,15 +215,10 @@ static int run_pipeline(mdx_ctx* c, const PipelineArgs& A)
             prows = rows;
         }
     }
-    // level-0 rows of frame 1 this call builds (mdx_band_fit_warp_dev converts the others it needs);
-    // k_front writes whole level-1 bands, i.e. level-0 rows 2*lo1 .. 2*hi1 of the widened range
-    c->band_built[0] = 0;
-    c->band_built[1] = h;
-    if (prows) {
-        const int lo1 = std::min(rows[1].lo, rows[0].lo / 2), hi1 = std::max(rows[1].hi, (rows[0].hi + 1) / 2);
-        c->band_built[0] = std::max(0, 2 * lo1);
-        c->band_built[1] = std::min(h, 2 * hi1);
-    }
+    // level-0 rows of frame 1 this call builds (mdx_band_fit_warp_dev converts the others it needs)
+    const RowSpan built = prows ? band_built_rows(rows, h) : RowSpan{0, h};
+    c->band_built[0] = built.lo;
+    c->band_built[1] = built.hi;
     if (c->aux && c->lk_impl == 2) {
         HIP_OR_RETURN(c, launch_front(fs_, batch, d_img1, d_img2, w, h, stride, fs, fmt, pyr1, pyr2, g, 1, prows));
         mark(c, 1, fs_);
