@@ -198,11 +198,28 @@ void MotionDetectionNode::stage_regions(FrameResult* r)
     const int cap = (int)std::min<long long>((long long)w * h / p_.region_min_area, (long long)((w + 1) / 2) * ((h + 1) / 2));
     int nkept = 0;
     r->regions.assign((size_t)8 * cap, 0);
-    const int rc = mdx_mask_regions(ctx_, r->mask.data(), w, h, w, p_.region_open ? MDX_REGIONS_OPEN3 : 0,
-                                    p_.region_min_area, reinterpret_cast<mdx_region*>(r->regions.data()), cap,
-                                    &r->num_regions_all, &nkept, nullptr, nullptr);
-    if (rc < 0) throw std::runtime_error(std::string("mdx_mask_regions: ") + mdx_last_error(ctx_));
-    r->regions.resize((size_t)8 * std::min(nkept, cap));
+    const int flags = p_.region_open ? MDX_REGIONS_OPEN3 : 0;
+    mdx_region* recs = reinterpret_cast<mdx_region*>(r->regions.data());
+    if (!p_.region_contours) {
+        const int rc = mdx_mask_regions(ctx_, r->mask.data(), w, h, w, flags, p_.region_min_area, recs, cap,
+                                        &r->num_regions_all, &nkept, nullptr, nullptr);
+        if (rc < 0) throw std::runtime_error(std::string("mdx_mask_regions: ") + mdx_last_error(ctx_));
+        r->regions.resize((size_t)8 * std::min(nkept, cap));
+        return;
+    }
+    // the records and their convex hulls in one call; every hull of `cap` regions fits maxv vertices
+    const int maxv = (int)std::min<long long>((long long)w * h, 2ll * std::min(w, h) * cap);
+    int total = 0;
+    r->region_contour_offsets.assign((size_t)cap + 1, 0);
+    r->region_contours.resize((size_t)2 * maxv);
+    const int rc = mdx_mask_region_hulls(ctx_, r->mask.data(), w, h, w, flags, p_.region_min_area, recs, cap,
+                                         &r->num_regions_all, &nkept, r->region_contour_offsets.data(),
+                                         r->region_contours.data(), maxv, &total);
+    if (rc < 0) throw std::runtime_error(std::string("mdx_mask_region_hulls: ") + mdx_last_error(ctx_));
+    const int n = std::min(nkept, cap);
+    r->regions.resize((size_t)8 * n);
+    r->region_contour_offsets.resize((size_t)n + 1);
+    r->region_contours.resize((size_t)2 * std::min(total, maxv));
 }
 
 // One clustering entry's call and trim: the result vectors sized for n members and max_kept = n / 6 clusters (a

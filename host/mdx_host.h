@@ -81,6 +81,9 @@ struct Params {
     // DESIGN.md §7j).  Off by default: the reference's writeContour loop (:426-429) is commented out, and
     // drawing the hulls (drawContours, the published cluster_image) is out of scope
     bool cluster_contours = false;
+    // the convex hull of every kept mask region (regions_on(); mdx_mask_region_hulls): the
+    // records and the hulls in one call, the label image staying on the device.  Off by default
+    bool region_contours = false;
 
     // Whether each optional stage runs on a processed frame (the conditions documented above, written
     // once: the node's stages and mdx_node's output files both ask here)
@@ -103,6 +106,10 @@ struct StageOutputs {
     // pair path
     int num_regions_all = 0;                   // region_min_area > 0: every component of the (opened) mask
     std::vector<int32_t> regions;              // x, y, width, height, area, seed_x, seed_y, id of each kept one
+    // region_contours: region i's convex hull is region_contours[2 * region_contour_offsets[i] ..
+    // 2 * region_contour_offsets[i + 1]), (x, y) pairs in mdx_region_hulls_dev's order (include/mdx.h)
+    std::vector<int32_t> region_contour_offsets;    // regions.size() / 8 + 1 entries
+    std::vector<int32_t> region_contours;
     // detect_outliers: the grid vectors' flags (bit 0 angle, bit 1 magnitude; image rows outer) and their
     // statistics; the clusters of the outlier vectors fill num_clusters, cluster_labels (per grid vector,
     // -1 for a vector that is no outlier or has no flow), kept_clusters, rectangles and

@@ -21,6 +21,7 @@
 //            [residual_threshold=0.2] (use_all_frames=0: fitSubspace's threshold (:491); its num_motions is 2 there)
 //            [cluster_contours=0]     (the convex hull of every kept cluster, showClusterContours' (:393, :510),
 //                                      behind each clustering stage that ran)
+//            [region_contours=0]      (pair path with region_min_area > 0: the convex hull of every kept region)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -53,7 +54,12 @@
 //   regions_<k>.bin               pair path with region_min_area > 0: i32 num_all, num_kept; i32
 //                                 records[num_kept][8] (x, y, width, height, area, seed_x, seed_y, id);
 //                                 with log_contours=1 each record's rectangle goes to motion.log too
-//   motion.log                    log_contours=1: created at start; MotionLogger::writeBoundingBox of
+//   region_hulls_<k>.bin          the same with region_contours=1: i32 k (the records of regions_<k>.bin); i32
+//                                 offsets[k + 1]; i32 xy[offsets[k]][2] -- record i's convex hull is
+//                                 xy[offsets[i] .. offsets[i + 1]), in mdx_region_hulls_dev's order (include/mdx.h);
+//                                 with log_contours=1 each hull goes to motion.log too (writeContour), behind
+//                                 the frame's region rectangles
+//   motion.log                   log_contours=1: created at start; MotionLogger::writeBoundingBox of
 //                                 every kept cluster's rectangle (node.cpp:431-434), "frame, id, tl.x,
 //                                 tl.y, br.x, br.y" with frame = the node's global_frame_count_ during
 //                                 that callback and id the index among the kept clusters; with
@@ -158,6 +164,7 @@ int main(int argc, char** argv)
         p.use_all_frames = geti("use_all_frames", 1) != 0;
         p.residual_threshold = getd("residual_threshold", 0.2);
         p.cluster_contours = geti("cluster_contours", 0) != 0;
+        p.region_contours = geti("region_contours", 0) != 0;
         const bool polling = !p.use_all_frames;
         const int device = geti("device", 0);
         const std::string out = argv[2];
@@ -182,6 +189,13 @@ int main(int argc, char** argv)
                 ml->write_bounding_box(q[0], q[1], q[2], q[3], frame, (int)i);
             }
         };
+        // MotionLogger::writeContour of every hull (xy[2 * offsets[i] .. 2 * offsets[i + 1])), same frame
+        auto log_hulls = [&](const std::vector<int32_t>& offsets, const std::vector<int32_t>& xy) {
+            if (!ml || polling) return;   // run() logs nothing
+            for (size_t i = 0; i + 1 < offsets.size(); i++)
+                ml->write_contour(std::vector<int>(xy.begin() + 2 * offsets[i], xy.begin() + 2 * offsets[i + 1]),
+                                  (int)node.global_frame_count() - 1, (int)i);
+        };
         for (size_t fi = 0; fi < frames.size(); fi++) {
             FrameResult r;
             if (polling) {
@@ -204,11 +218,7 @@ int main(int argc, char** argv)
                 if (r.contour_offsets.empty()) r.contour_offsets.assign(1, 0);   // the stage did not run: no cluster
                 b.put(r.contour_offsets);
                 b.put(r.contours);
-                if (!ml || polling) return;   // run() logs nothing
-                for (size_t i = 0; i + 1 < r.contour_offsets.size(); i++)
-                    ml->write_contour(std::vector<int>(r.contours.begin() + 2 * r.contour_offsets[i],
-                                                       r.contours.begin() + 2 * r.contour_offsets[i + 1]),
-                                      (int)node.global_frame_count() - 1, (int)i);
+                log_hulls(r.contour_offsets, r.contours);
             };
             const int traj_len = r.trajectories.empty() ? 0 : (int)r.trajectories[0].size() / 2;
             ByteBuffer res{r.num_vectors, r.rc, r.w, r.h, r.npts, (int32_t)r.trajectories.size(), traj_len,
@@ -243,6 +253,13 @@ int main(int argc, char** argv)
                 b.put(r.regions);
                 b.write(out + "/regions" + sfx);
                 log_rectangles(r.regions.data(), 8, r.regions.size() / 8);
+                if (p.region_contours) {
+                    ByteBuffer hb{(int32_t)(r.regions.size() / 8)};
+                    hb.put(r.region_contour_offsets);
+                    hb.put(r.region_contours);
+                    hb.write(out + "/region_hulls" + sfx);
+                    log_hulls(r.region_contour_offsets, r.region_contours);
+                }
             }
             if (!polling && p.detect_outliers_on()) {
                 const mdx_outlier_stats& st = r.outlier_stats;

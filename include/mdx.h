@@ -41,7 +41,9 @@ extern "C" {
                                    unchanged, 80 bytes).
                                 10: mdx_half_size, mdx_resize_half_dev, mdx_resize_half and
                                    mdx_ring_push_half (new entries; mdx_params is unchanged, 80 bytes).
-                                11: mdx_cluster_hulls (a new entry; mdx_params is unchanged, 80 bytes). */
+                                11: mdx_cluster_hulls (a new entry; mdx_params is unchanged, 80 bytes).
+                                   mdx_region_hulls_dev and mdx_mask_region_hulls joined under 11: two
+                                   more entries, nothing existing changes. */
 
 /* Return codes */
 #define MDX_OK           0
@@ -598,6 +600,63 @@ int mdx_mask_regions(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int stride
                      mdx_region* regions, int max_regions, int* num_all, int* num_kept,
                      int32_t* labels, uint8_t* mask_out);
 
+/*
+ * Convex hulls of the mask regions: the second thing the node takes from a blob next
+ * to its boundingRect (cv::convexHull, optical_flow_visualizer.cpp:204-240), for the regions of
+ * mdx_mask_regions_dev, on the device.  The hull of a blob's contour is the hull of its pixels, so
+ * the vertex set is determined mathematically.
+ *   Inputs: what mdx_mask_regions_dev wrote -- d_labels, d_regions and d_num_kept.  Per image b the
+ *   first r = min(max(num_kept[b], 0), max_regions) records take part.
+ *   Members of record j: the pixels (x, y) inside the record's rectangle whose label equals the
+ *   record's id.  The rectangle is clamped to the frame first: the entry cannot validate device
+ *   records and never touches memory outside the frame because of one.  Pixels of other regions inside
+ *   the rectangle (nested or interleaved blobs) take no part.  A record whose id matches no pixel
+ *   gives 0 vertices.  A nested blob's hull is reported like any other: no hierarchy, no RETR_EXTERNAL
+ *   filtering, and no contour polylines -- the hull only.  (A record edited so that its area
+ *   understates its members may have its hull cut short at min(area, 2*width, 2*height) vertices.)
+ *   Vertices, order, start: mdx_cluster_hulls' contract, minus the conversion (members are integers
+ *   already).  Extreme points only: collinear boundary points are excluded, one pixel gives 1 vertex,
+ *   a straight run its 2 end points.  The first vertex is the lexicographically greatest (greatest x,
+ *   then greatest y); the hull runs along its max-y side to the lexicographically smallest vertex and
+ *   along its min-y side back.  Not closed.  As there, the start and the orientation are restated from
+ *   OpenCV 2.4's documentation and unpinned against a real build.  Integer and exact throughout.
+ * Outputs:
+ *   d_offsets      [batch][max_regions + 1] hull j's vertices are xy[b][offsets[b][j] ..
+ *                  offsets[b][j+1]); always complete and monotone, entries past r repeat the total
+ *   d_xy           [batch][max_vertices][2] int32 x, y: the first max_vertices vertices of image b,
+ *                  packed in record order; nothing past them is written, and nothing at all when
+ *                  max_vertices is 0 (d_xy may then be NULL)
+ *   d_num_vertices [batch] (may be NULL) offsets[b][r]; may exceed max_vertices
+ * mdx_region_hulls_dev is asynchronous on the context stream and never synchronises with the host: it
+ * chains behind mdx_mask_regions_dev (itself behind mdx_flow_warp_diff_batch_dev) with no round trip,
+ * and it honours mdx_input_ready like the other device entries.  Every pointer is a device pointer.
+ * Three launches per call for any batch up to 65,535 images (a per-image scan of the records' vertex
+ * bounds, one workgroup per record, a per-image scan of the counts that packs xy); no workgroup waits
+ * for another.  max_regions == 0 is MDX_OK with offsets[b][0] = 0 and num_vertices[b] = 0.
+ * Scratch belongs to the context, is a function of (batch, w, h, max_regions) alone and only grows:
+ *   batch * (12 * max_regions + 8 * min(w*h, 2*min(w, h)*max_regions)) bytes (+ 255 of alignment)
+ * -- per record a staging slice and a count, per image a staging block that holds every hull, a hull
+ * having at most min(area, 2*width, 2*height) vertices.  No allocation after the first call at a
+ * given (batch, w, h, max_regions).
+ * MDX_EINVAL: a null context; batch < 1; w or h < 1; w*h > 2^30; w > MDX_HULL_MAX_SPAN (8192 covers an
+ * 8K frame); max_regions < 0 or max_vertices < 0; d_labels or d_offsets NULL; d_regions or d_num_kept
+ * NULL with max_regions > 0; d_xy NULL with max_vertices > 0.
+ */
+int mdx_region_hulls_dev(mdx_ctx* ctx, int batch, const int32_t* d_labels /* [batch][h][w] */, int w, int h,
+                         const mdx_region* d_regions /* [batch][max_regions] */, int max_regions,
+                         const int32_t* d_num_kept /* [batch] */,
+                         int32_t* d_offsets /* [batch][max_regions + 1] */,
+                         int32_t* d_xy /* [batch][max_vertices][2] or NULL */, int max_vertices,
+                         int32_t* d_num_vertices /* [batch] or NULL */);
+/* mdx_mask_regions and the hulls of its records for one mask in host memory, synchronous: the label
+ * image stays on the device and never crosses PCIe; of xy only the min(offsets[r], max_vertices)
+ * vertices that exist are copied back.  regions, num_all, num_kept as mdx_mask_regions; offsets, xy,
+ * num_vertices as above for one image.  Errors: mdx_mask_regions', plus w > MDX_HULL_MAX_SPAN, negative
+ * max_vertices, NULL offsets, NULL xy with max_vertices > 0. */
+int mdx_mask_region_hulls(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                          mdx_region* regions, int max_regions, int* num_all, int* num_kept,
+                          int32_t* offsets /* [max_regions + 1] */, int32_t* xy, int max_vertices, int* num_vertices);
+
 /* Page-locked host memory for frames and outputs (e.g. the node's rgb8 staging buffer and its
  * trajectory outputs): copies between it and the device run as DMA at full link rate, while a
  * pageable buffer is staged by the runtime through bounce buffers.  Any entry taking host pointers
@@ -618,7 +677,8 @@ int mdx_memcpy_d2h(mdx_ctx* ctx, void* dst, const void* src, size_t bytes);
  * milliseconds, of stage: 0 gray+pad, 1 pyramids, 2 Scharr, 3 LK, 4 classify+fit,
  * 5 warp+diff, 6 whole call; mdx_timing_calls returns how many calls were recorded.
  * mdx_cluster_hulls records a set too: stage 0 its upload, 3 k_hull, 4 its readback, 6 the three
- * together (1, 2 and 5 are empty). */
+ * together (1, 2 and 5 are empty); mdx_region_hulls_dev too: stage 2 its scan of the records' bounds, 3
+ * k_region_hull, 4 the scan that packs xy, 6 the three together (0, 1 and 5 are empty). */
 int mdx_enable_timing(mdx_ctx* ctx, int on);
 int mdx_timing_calls(const mdx_ctx* ctx);
 int mdx_stage_ms(mdx_ctx* ctx, int stage, float* ms);

@@ -48,7 +48,7 @@ EXPORTED = [
     "mdx_debug_div32", "mdx_debug_warp_paths", "mdx_trajectory_layout", "mdx_abi_version", "mdx_params_size",
     "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions", "mdx_cluster_vectors",
     "mdx_find_outliers", "mdx_half_size", "mdx_resize_half_dev", "mdx_resize_half", "mdx_ring_push_half",
-    "mdx_cluster_hulls",
+    "mdx_cluster_hulls", "mdx_region_hulls_dev", "mdx_mask_region_hulls",
 ]
 ABI_VERSION = 11  # include/mdx.h MDX_ABI_VERSION
 
@@ -270,6 +270,11 @@ def lib() -> C.CDLL:
     L.mdx_mask_regions.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                    C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp]
     L.mdx_mask_regions.restype = C.c_int
+    L.mdx_region_hulls_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.mdx_region_hulls_dev.restype = C.c_int
+    L.mdx_mask_region_hulls.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.mdx_mask_region_hulls.restype = C.c_int
     _lib = L
     return L
 

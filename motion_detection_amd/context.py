@@ -163,6 +163,7 @@ class RegionResult:
     num_kept: int               # those with area >= min_area, also when max_regions cut `regions` short
     labels: np.ndarray | None = None    # (h, w) int32: id among all components, -1 background (want_labels)
     mask_out: np.ndarray | None = None  # (h, w) uint8: the opened mask as 0 / 255 (want_mask)
+    hulls: list | None = None           # one (v_j, 2) int32 array per returned record: its convex hull (want_hulls, §7k)
 
     @property
     def rectangles(self) -> list:
@@ -408,8 +409,10 @@ class Context:
 
     # -- the motion mask labelled into regions (getMotionContours' recipe: opening, 8-connected blobs, boundingRect)
     def mask_regions(self, mask: np.ndarray, open3: bool = True, min_area: int = 1, max_regions: int | None = None,
-                     want_labels: bool = False, want_mask: bool = False) -> "RegionResult":
-        """max_regions (default: every component the frame can hold) caps how many records are returned."""
+                     want_labels: bool = False, want_mask: bool = False, want_hulls: bool = False) -> "RegionResult":
+        """max_regions (default: every component the frame can hold) caps how many records are returned.
+        want_hulls: the records and each one's convex hull in one call (mdx_mask_region_hulls: the label
+        image stays on the device); labels or the mask asked for next to the hulls cost a second call."""
         mask = np.asarray(mask, dtype=np.uint8)
         if mask.ndim != 2 or mask.strides[1] != 1 or mask.strides[0] < mask.shape[1]:
             mask = np.ascontiguousarray(mask)
@@ -423,11 +426,31 @@ class Context:
         labels = np.empty((h, w), np.int32) if want_labels else None
         mout = np.empty((h, w), np.uint8) if want_mask else None
         nall, nkept = C.c_int(0), C.c_int(0)
-        self._check(lib().mdx_mask_regions(self._h, _ptr(mask), w, h, mask.strides[0],
-                                           _lib.REGIONS_OPEN3 if open3 else 0, int(min_area),
-                                           _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
-                                           _ptr(labels), _ptr(mout)))
-        return RegionResult(regs[:min(nkept.value, max(cap, 0))].copy(), nall.value, nkept.value, labels, mout)
+        flags = _lib.REGIONS_OPEN3 if open3 else 0
+        if not want_hulls or want_labels or want_mask:
+            self._check(lib().mdx_mask_regions(self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area),
+                                               _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
+                                               _ptr(labels), _ptr(mout)))
+        hulls = None
+        if want_hulls:
+            maxv = min(w * h, 2 * min(w, h) * max(cap, 0))    # what the hulls of `cap` regions can hold (include/mdx.h)
+            offsets = np.zeros(max(cap, 0) + 1, np.int32)
+            xy = np.empty((maxv, 2), np.int32)
+            nv = C.c_int(0)
+            self._check(lib().mdx_mask_region_hulls(self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area),
+                                                    _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
+                                                    _ptr(offsets), _ptr(xy) if maxv > 0 else None, maxv, C.byref(nv)))
+            hulls = [xy[offsets[j]:offsets[j + 1]].copy() for j in range(min(nkept.value, max(cap, 0)))]
+        return RegionResult(regs[:min(nkept.value, max(cap, 0))].copy(), nall.value, nkept.value, labels, mout, hulls)
+
+    def region_hulls_dev(self, batch: int, d_labels: int, w: int, h: int, d_regions: int, max_regions: int,
+                         d_num_kept: int, d_offsets: int, d_xy: int = 0, max_vertices: int = 0,
+                         d_num_vertices: int = 0) -> int:
+        """Asynchronous on the context stream (include/mdx.h mdx_region_hulls_dev); pointers are ints.
+        Takes what mask_regions_dev wrote: d_labels, d_regions, d_num_kept."""
+        return self._check(lib().mdx_region_hulls_dev(
+            self._h, batch, _v(d_labels), w, h, _v(d_regions), max_regions, _v(d_num_kept), _v(d_offsets), _v(d_xy),
+            max_vertices, _v(d_num_vertices)))
 
     def mask_regions_dev(self, batch: int, d_mask: int, w: int, h: int, stride: int, frame_stride: int,
                          open3: bool = True, min_area: int = 1, d_regions: int = 0, max_regions: int = 0,

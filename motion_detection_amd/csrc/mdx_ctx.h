@@ -127,6 +127,8 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     std::vector<uint8_t> ol_flags;           // the flags when the caller takes only the vectors
     DevBuf rgscr;                            // mdx_mask_regions_dev: labels, block counts, component records
     DevBuf rgin, rgout;                      // mdx_mask_regions (host entry): the mask, every output
+    DevBuf rhscr;                            // mdx_region_hulls_dev: staging slices, vertex counts, staged hulls
+    DevBuf rhout;                            // mdx_mask_region_hulls (host entry): counts, records, labels, offsets, xy
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
     DevBuf rfull;                            // mdx_ring_push_half: the full-size frame, halved into rin
     DevBuf hsrc, hdst;                       // mdx_resize_half (host entry): the frame and its half

@@ -353,6 +353,21 @@ size_t hull_lds_bytes(int ncols);
 hipError_t launch_hull(hipStream_t s, int k, const HullCluster* recs, const float* pts, int max_ncols,
                        int32_t* counts, int32_t* staging);
 
+// Convex hulls of the mask regions (mdx_hull.hip k_region_hull): three launches on s, no
+// host synchronisation, every pointer a device pointer, w <= MDX_HULL_MAX_SPAN.  scratch:
+// region_hulls_scratch_bytes(batch, w, h, max_regions) of device memory, a function of those four alone:
+// per record its staging slice (8 B) and vertex count (4 B), per image a staging block of
+// min(w*h, 2*min(w, h)*max_regions) vertices of 8 B; `lay`, when given, receives its layout.
+constexpr int kRegionHullGridX = 1 << 21;   // records per k_region_hull launch (grid x of 1,024-lane workgroups)
+struct RegionHullScratch {
+    size_t slices, counts, staging;   // byte offsets
+};
+size_t region_hulls_scratch_bytes(int batch, int w, int h, int max_regions, RegionHullScratch* lay = nullptr);
+hipError_t launch_region_hulls(hipStream_t s, int batch, const int32_t* labels, int w, int h, const mdx_region* regions,
+                               int max_regions, const int32_t* num_kept, int32_t* offsets, int32_t* xy,
+                               int max_vertices, int32_t* num_vertices, void* scratch,
+                               hipEvent_t hull_begin = nullptr, hipEvent_t hull_end = nullptr);   // around k_region_hull
+
 // Half-size ingest (mdx_resize.hip k_half): `batch` frames of w x h pixels of `channels`
 // (1 or 3) interleaved bytes halved to mdx_half_size(w, h), one launch on s (per kHalfMaxBatch frames).
 // A lane owns kHalfPx adjacent destination pixels of kHalfRows rows; a wave 64 * kHalfPx and a

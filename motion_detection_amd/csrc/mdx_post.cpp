@@ -1,7 +1,8 @@
 // mdx_post.cpp -- what follows the flow: the reference's random stream, the trajectory subspace
 // fit (OutlierDetector::fitSubspace), Euclidean clustering (FlowClusterer::clusterEuclidean), flow
 // vectors clustered by distance and angle (getClusters), the kept clusters' convex hulls
-// (showClusterContours), the flow vectors' median / MAD outliers (findOutliers) and the pair path's mask labelled into regions (BackgroundSubtractor::getMotionContours' recipe).
+// (showClusterContours), the flow vectors' median / MAD outliers (findOutliers), the pair path's mask labelled
+// into regions (BackgroundSubtractor::getMotionContours' recipe) and those regions' convex hulls.
 #include "mdx_ctx.h"
 
 #include <cfloat>
@@ -524,5 +525,107 @@ extern "C" int mdx_mask_regions(mdx_ctx* c, const uint8_t* mask, int w, int h, i
         HIP_OR_RETURN(c, hipMemcpy(regions, out + o_rec, (size_t)nrec * sizeof(mdx_region), hipMemcpyDeviceToHost));
     if (num_all) *num_all = cnt[0];
     if (num_kept) *num_kept = cnt[1];
+    return MDX_OK;
+}
+
+// The convex hull of each region record's pixels: what the node takes from a blob next to
+// its boundingRect (optical_flow_visualizer.cpp:204-240).  All of it runs on the device (mdx_hull.hip);
+// the call only queues three launches on the context's stream.
+static int check_region_hulls(mdx_ctx* c, const char* who, int w, const void* offsets, const void* xy, int max_vertices)
+{
+    if (w > MDX_HULL_MAX_SPAN) return set_err(c, MDX_EINVAL, "%s: w %d is more than %d columns", who, w, MDX_HULL_MAX_SPAN);
+    if (max_vertices < 0) return set_err(c, MDX_EINVAL, "%s: negative max_vertices", who);
+    if (!offsets || (max_vertices > 0 && !xy)) return set_err(c, MDX_EINVAL, "%s: a needed pointer is NULL", who);
+    return MDX_OK;
+}
+
+extern "C" int mdx_region_hulls_dev(mdx_ctx* c, int batch, const int32_t* d_labels, int w, int h,
+                                    const mdx_region* d_regions, int max_regions, const int32_t* d_num_kept,
+                                    int32_t* d_offsets, int32_t* d_xy, int max_vertices, int32_t* d_num_vertices)
+{
+    if (!c) return MDX_EINVAL;
+    const char* who = "mdx_region_hulls_dev";
+    if (batch < 1 || w < 1 || h < 1) return set_err(c, MDX_EINVAL, "%s: bad batch or size", who);
+    if ((long long)w * h > (1ll << 30)) return set_err(c, MDX_EINVAL, "%s: more than 2^30 pixels", who);
+    if (max_regions < 0) return set_err(c, MDX_EINVAL, "%s: negative max_regions", who);
+    if (const int rc = check_region_hulls(c, who, w, d_offsets, d_xy, max_vertices); rc != MDX_OK) return rc;
+    if (!d_labels || (max_regions > 0 && (!d_regions || !d_num_kept)))
+        return set_err(c, MDX_EINVAL, "%s: a needed pointer is NULL", who);
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const int chunk = std::min(batch, kRegionsMaxBatch);
+    if (const int rc = ensure(c, c->rhscr, region_hulls_scratch_bytes(chunk, w, h, max_regions)); rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    if (c->input_ev) {      // mdx_input_ready: one-shot
+        hipEvent_t e = c->input_ev;
+        c->input_ev = nullptr;
+        HIP_OR_RETURN(c, hipStreamWaitEvent(s, e, 0));
+    }
+    const size_t N = (size_t)w * h;
+    // (mdx_enable_timing: stage 2 k_region_hull_slices, 3 k_region_hull, 4 k_region_hull_pack, 6 the three together)
+    for (int i = 0; i <= 2; i++) mark(c, i);
+    hipEvent_t* ev = c->timing && c->cur >= 0 ? c->ev.data() + c->cur * 7 : nullptr;
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+        const int nb = std::min(chunk, batch - b0);
+        HIP_OR_RETURN(c, launch_region_hulls(s, nb, d_labels + b0 * N, w, h,
+                                             d_regions ? d_regions + (size_t)b0 * max_regions : nullptr, max_regions,
+                                             d_num_kept ? d_num_kept + b0 : nullptr,
+                                             d_offsets + (size_t)b0 * ((size_t)max_regions + 1),
+                                             d_xy ? d_xy + (size_t)b0 * max_vertices * 2 : nullptr, max_vertices,
+                                             d_num_vertices ? d_num_vertices + b0 : nullptr, c->rhscr.p,
+                                             ev ? ev[3] : nullptr, ev ? ev[4] : nullptr));
+    }
+    if (max_regions == 0)
+        for (int i = 3; i <= 4; i++) mark(c, i);     // no record, no k_region_hull: its stage is empty
+    for (int i = 5; i <= 6; i++) mark(c, i);
+    return MDX_OK;
+}
+
+extern "C" int mdx_mask_region_hulls(mdx_ctx* c, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                                     mdx_region* regions, int max_regions, int* num_all, int* num_kept,
+                                     int32_t* offsets, int32_t* xy, int max_vertices, int* num_vertices)
+{
+    if (!c) return MDX_EINVAL;
+    const char* who = "mdx_mask_region_hulls";
+    const size_t fs = (size_t)std::max(h, 0) * (size_t)std::max(stride, 0);
+    if (const int rc = check_regions(c, who, 1, mask, w, h, stride, fs, flags, regions, max_regions, nullptr); rc != MDX_OK)
+        return rc;
+    if (const int rc = check_region_hulls(c, who, w, offsets, xy, max_vertices); rc != MDX_OK) return rc;
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    // one output block: counts (num_all, num_kept, num_vertices), records, offsets, labels, xy; the labels
+    // stay on the device
+    const size_t N = (size_t)w * h, M = (size_t)max_regions, o_rec = 256,
+                 o_off = o_rec + (M * sizeof(mdx_region) + 255) / 256 * 256, o_lab = o_off + ((M + 1) * 4 + 255) / 256 * 256,
+                 o_xy = o_lab + (N * 4 + 255) / 256 * 256;
+    const size_t in_bytes = (size_t)(h - 1) * stride + w;     // the caller's last row holds w bytes, not stride
+    if (const int rc = ensure_all(c, {{&c->rgin, fs}, {&c->rhout, o_xy + (size_t)max_vertices * 8}}); rc != MDX_OK)
+        return rc;
+    hipStream_t s = c->stream;
+    char* out = c->rhout.as<char>();
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->rgin.p, mask, in_bytes, hipMemcpyHostToDevice, s));
+    int32_t* d_cnt = reinterpret_cast<int32_t*>(out);
+    mdx_region* d_rec = max_regions ? reinterpret_cast<mdx_region*>(out + o_rec) : nullptr;
+    int32_t* d_lab = reinterpret_cast<int32_t*>(out + o_lab);
+    if (const int rc = mdx_mask_regions_dev(c, 1, c->rgin.as<uint8_t>(), w, h, stride, fs, flags, min_area, d_rec,
+                                            max_regions, d_cnt, d_cnt + 1, d_lab, nullptr);
+        rc != MDX_OK)
+        return rc;
+    if (const int rc = mdx_region_hulls_dev(c, 1, d_lab, w, h, d_rec, max_regions, d_cnt + 1,
+                                            reinterpret_cast<int32_t*>(out + o_off),
+                                            max_vertices ? reinterpret_cast<int32_t*>(out + o_xy) : nullptr, max_vertices,
+                                            d_cnt + 2);
+        rc != MDX_OK)
+        return rc;
+    int32_t cnt[3] = {0, 0, 0};
+    HIP_OR_RETURN(c, hipMemcpyAsync(cnt, d_cnt, 12, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(offsets, out + o_off, (M + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    const int nrec = std::min(cnt[1], max_regions);
+    if (nrec > 0)
+        HIP_OR_RETURN(c, hipMemcpy(regions, out + o_rec, (size_t)nrec * sizeof(mdx_region), hipMemcpyDeviceToHost));
+    const int nxy = std::min(cnt[2], max_vertices);           // only the vertices that exist come back
+    if (nxy > 0) HIP_OR_RETURN(c, hipMemcpy(xy, out + o_xy, (size_t)nxy * 8, hipMemcpyDeviceToHost));
+    if (num_all) *num_all = cnt[0];
+    if (num_kept) *num_kept = cnt[1];
+    if (num_vertices) *num_vertices = cnt[2];
     return MDX_OK;
 }

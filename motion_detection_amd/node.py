@@ -42,7 +42,10 @@ showClusterContours' convex hull of each kept cluster (:393, :510; optical_flow_
 computed on the device (mdx_cluster_hulls): the result carries them as ``contours``, and
 under ``log_contours`` each is written with MotionLogger::writeContour behind the frame's rectangle
 lines (the reference's loop at :426-429 is commented out, hence the opt-in).  Drawing them
-(drawContours, the published cluster_image) is out of scope.
+(drawContours, the published cluster_image) is out of scope.  With ``region_contours`` (off by default)
+and ``region_min_area`` set, the regions come with the convex hull of each (mdx_mask_region_hulls,
+DESIGN.md §7k: the label image stays on the device) as ``regions.hulls``, logged the same way behind
+the frame's region rectangles.
 
 With ``use_all_frames=False`` the callback only fills the ring (:262) and the reference's polling caller
 run() (:457-553) does the work: ``run_once()`` is one pass of its body (:464-529) and ``run()`` the loop.
@@ -140,7 +143,10 @@ class MotionDetectionNode:
                        "detect_outliers": False, "include_zeros": False,
                        # showClusterContours' convex hull of every kept cluster (node.cpp:393, :510):
                        # off by default, the reference's writeContour loop (:426-429) is commented out
-                       "cluster_contours": False}
+                       "cluster_contours": False,
+                       # the convex hull of every kept mask region (region_min_area set): off by
+                       # default; logged with writeContour behind the frame's region rectangles
+                       "region_contours": False}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -193,12 +199,18 @@ class MotionDetectionNode:
         if not self.params.get("cluster_contours"):
             return []
         hulls = fc.hulls()
-        if log and self.params.get("log_contours") and self.params.get("log_path"):
-            if self.logger is None:
-                self.logger = MotionLogger(self.params["log_path"])
-            for k, hull in enumerate(hulls):
-                self.logger.writeContour(hull, self.global_frame_count, k)
+        if log:
+            self._log_contours(hulls)
         return hulls
+
+    def _log_contours(self, hulls):
+        """MotionLogger::writeContour(hull, frame, i) of each hull when log_contours and a log_path are set."""
+        if not (self.params.get("log_contours") and self.params.get("log_path")):
+            return
+        if self.logger is None:
+            self.logger = MotionLogger(self.params["log_path"])
+        for k, hull in enumerate(hulls):
+            self.logger.writeContour(hull, self.global_frame_count, k)
 
     @property
     def trajectory_size(self) -> int:
@@ -362,9 +374,13 @@ class MotionDetectionNode:
         min_area = self.params.get("region_min_area")
         if min_area is not None and res.mask is not None:
             # the mask is labelled on the device; what comes back is the records
+            # (region_contours: and each record's convex hull; the labels stay on the device)
+            want_hulls = bool(self.params.get("region_contours"))
             res.regions = self.ofc.context.mask_regions(res.mask, open3=bool(self.params.get("region_open", True)),
-                                                        min_area=int(min_area))
+                                                        min_area=int(min_area), want_hulls=want_hulls)
             self._log_rectangles(res.regions.rectangles)
+            if want_hulls:
+                self._log_contours(res.regions.hulls)
         thr, athr = self.params.get("distance_threshold"), self.params.get("angular_threshold")
         if self.params.get("detect_outliers") and thr is not None and athr is not None:
             self.detect_outliers(image1.shape[0], image1.shape[1], res, float(thr), float(athr))
