@@ -54,23 +54,41 @@ typedef short s2 __attribute__((ext_vector_type(2)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int v3u __attribute__((ext_vector_type(3)));
-// raw buffer descriptor over [base, base + bytes) (cdna_hip_programming.md T8: built from
-// wave-uniform values only); loads then take a 32-bit per-lane byte offset
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, long long bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0,
-                                             (int)min(bytes, (long long)0x7fffffff), 0x00020000);
-}
-// the same for wave-uniform inputs and a size the host keeps below 2 GB: the inputs pass through
-// readfirstlane so that the compiler can prove the descriptor uniform (scalar instructions, no
-// waterfall loop around the memory op; cdna_hip_programming.md T8)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc32(const void* base, uint32_t bytes)
-{
-    const unsigned long long b = (unsigned long long)(uintptr_t)base;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-    void* p = (void*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(p, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
+// A raw buffer descriptor over [base, base + bytes) that walks through its range: [base + n * step,
+// base + bytes) after n advances; loads take a 32-bit per-lane byte offset.  Base and size are
+// wave-uniform and below 2 GB (host), and pass through readfirstlane so that the compiler can prove the
+// descriptor uniform (scalar instructions, no waterfall loop around the memory op;
+// cdna_hip_programming.md T8).  Kept as its words, so that an advance is one add-with-carry on the base
+// and one subtract on the size, in place in the descriptor's SGPRs; the shrinking size keeps the range
+// check at the same end.  The base is a 48-bit address: word 1's stride and swizzle bits stay 0.
+struct LkRunRsrc {
+    unsigned long long base;
+    uint32_t bytes;
+
+    __device__ __forceinline__ LkRunRsrc(const void* p, uint32_t n)
+    {
+        const unsigned long long b = (unsigned long long)(uintptr_t)p;
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
+        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) & 0xffffu;
+        base = ((unsigned long long)hi << 32) | lo;
+        bytes = __builtin_amdgcn_readfirstlane(n);
+    }
+    __device__ __forceinline__ void advance(uint32_t step)
+    {
+        base += step;
+        bytes -= step;
+        // opaque: otherwise a rolled loop's descriptors are rebuilt, each row, from the loop counter
+        asm("" : "+s"(base), "+s"(bytes));
+    }
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc() const
+    {
+        const v4u w = {(uint32_t)base, (uint32_t)(base >> 32), bytes, 0x00020000u};
+        __amdgpu_buffer_rsrc_t r;
+        static_assert(sizeof(r) == sizeof(w), "descriptor words");
+        __builtin_memcpy(&r, &w, sizeof(r));
+        return r;
+    }
+};
 
 // residue-class tables: [level][axis][kTabStride]
 __device__ __forceinline__ int class_of(const int16_t* cmap, int level, int axis, int res)
@@ -355,9 +373,9 @@ __global__ __launch_bounds__(256) void k_lk_class_fused(const uint8_t* __restric
 //             all its groups.  So the waves are persistent and each slot, when its group retires,
 //             takes the next group from a work queue: slots of one wave run out of step, only the
 //             group-internal lockstep remains.
-// UW is the exact-fit union width (even: a 16-B load carries two pairs); the last load of a
-// slot's row and the last LDS-DMA piece of the wave's row are partial (lane-masked), so no byte
-// beyond the union is moved.
+// UW is the exact-fit union width (even: a 16-B load carries two pairs); the lanes of the last
+// LDS-DMA piece of the wave's row that lie past the image fetch nothing (an offset outside the
+// descriptor), so no byte beyond the union is read from memory.
 template <int G, int UW>
 struct LkShape {
     static constexpr int UWIDTH = UW;                         // union columns per slot
@@ -413,7 +431,7 @@ __device__ __forceinline__ GroupGeom group_geom(const LkArgs& a, const ClassLeve
 // [slot][UW][D, C] row image, i.e. slot sp's union bytes wb: its source is that slot's union row
 // (`mine`: this lane's slot's byte offset in the class slab, uniform over the slot) plus wb.  The last
 // piece may reach past the image (sp >= S): those lanes get some slot's offset, and the caller keeps
-// them from fetching it (k_lk_iter masks them at the DMA, the A kernels: LkRowImages::mask_past).
+// them from fetching it (an offset outside the descriptor: k_lk_iter's kNoFetch, LkRowImages::mask_past).
 template <typename Sh>
 __device__ __forceinline__ void lk_piece_offsets(uint32_t mine, int lane, uint32_t (&uoff)[Sh::ND])
 {
@@ -428,11 +446,11 @@ __device__ __forceinline__ void lk_piece_offsets(uint32_t mine, int lane, uint32
 // The A kernels' three row images, filled by LDS-DMA like k_lk_iter's (two rows in flight ahead of
 // the one being summed).  One __shared__ array per image (the kernel's: img0 .. img2), so that no
 // compiler wait ties a row's reads to later rows' DMA.  uoff: the kernel's lk_piece_offsets of the
-// next row to fetch.
+// first row; crs walks down the rows (LkRunRsrc), so the offsets stay as they are.
 template <typename Sh>
 struct LkRowImages {
     lds_u32 *img0, *img1, *img2;  // [slot][UW][D, C]
-    __amdgpu_buffer_rsrc_t crs;   // the pair's class slab
+    LkRunRsrc crs;                // the pair's class slab, from the next row to fetch
     uint32_t rowb;                // bytes per plane row
 
     template <int B>
@@ -449,16 +467,16 @@ struct LkRowImages {
         for (int c = 0; c < Sh::ND; c++)
             if (1024 * c + 16 * lane >= Sh::BYTES) uoff[c] = 0x80000000u;
     }
-    // the next row into image B; the offsets move on to the row after it
+    // the next row into image B; the descriptor moves on to the row after it
     template <int B>
-    __device__ __forceinline__ void dma(uint32_t (&uoff)[Sh::ND]) const
+    __device__ __forceinline__ void dma(const uint32_t (&uoff)[Sh::ND])
     {
         lds_u32* I = ibuf<B>();
+        const __amdgpu_buffer_rsrc_t r = crs.rsrc();
 #pragma unroll
-        for (int c = 0; c < Sh::ND; c++) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(crs, (lds_ptr)(I + 256 * c), 16, (int)uoff[c], 0, 0, 0);
-            uoff[c] += rowb;
-        }
+        for (int c = 0; c < Sh::ND; c++)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr)(I + 256 * c), 16, (int)uoff[c], 0, 0, 0);
+        crs.advance(rowb);
     }
 };
 
@@ -531,7 +549,8 @@ __global__ __launch_bounds__(64) void k_lk_A(LkArgs a, const uint8_t* __restrict
     bool ok = q.valid && !(q.ipx < -kWin || q.ipx >= L.w || q.ipy < -kWin || q.ipy >= L.h);
 
     LkRowImages<Sh> im{(lds_u32*)img0, (lds_u32*)img1, (lds_u32*)img2,
-                       buf_rsrc(cls + (long long)pair * a.plan.bytes_per_pair, a.plan.bytes_per_pair),
+                       LkRunRsrc(cls + (long long)pair * a.plan.bytes_per_pair,
+                                 (uint32_t)min(a.plan.bytes_per_pair, (long long)0x7fffffff)),
                        (uint32_t)C.PW * 8};
     uint32_t uoff[ND];
     lk_piece_offsets<Sh>(q.ubase + (uint32_t)q.v0 * im.rowb, lane, uoff);
@@ -630,7 +649,8 @@ __global__ __launch_bounds__(64) void k_lk_A_rows(LkArgs a, const uint8_t* __res
     const int R = (nr - 1) * asp + kWin;                           // plane rows of the strip
 
     LkRowImages<Sh> im{(lds_u32*)img0, (lds_u32*)img1, (lds_u32*)img2,
-                       buf_rsrc(cls + (long long)pair * a.plan.bytes_per_pair, a.plan.bytes_per_pair),
+                       LkRunRsrc(cls + (long long)pair * a.plan.bytes_per_pair,
+                                 (uint32_t)min(a.plan.bytes_per_pair, (long long)0x7fffffff)),
                        (uint32_t)C.PW * 8};
     uint32_t uoff[ND];
     lk_piece_offsets<Sh>(ubase + (uint32_t)v00 * im.rowb, lane, uoff);
@@ -763,8 +783,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
     // it put a vmcnt(0) -- a wait for the DMA just issued -- in front of every read that followed a
     // DMA, and no row overlapped its fetch.
     static_assert(kWin % 2 == 0, "row schedule (row pairs)");
-    __shared__ __attribute__((aligned(16))) uint32_t dU0[2 * UB];   // [slot][UW][D, C]
-    __shared__ __attribute__((aligned(16))) uint32_t dU1[2 * UB];
+    // Where the wave's LDS stays within 6.5 KB (two pieces per row: the bench's shapes), the union buffers
+    // hold whole DMA pieces: the last piece's lanes past the image are masked by offset (below) and
+    // still write their 16 B of zeros, which land past every el and are never read.  Wider shapes
+    // with a partial last piece keep exact-fit buffers and an exec mask around that piece.
+    constexpr bool WHOLE = 2 * ND * 1024 + 2 * 1024 <= 6656;
+    constexpr int UWORDS = WHOLE ? ND * 256 : 2 * UB;
+    static_assert(UWORDS >= 2 * UB, "the buffer covers the union image");
+    __shared__ __attribute__((aligned(16))) uint32_t dU0[UWORDS];   // [slot][UW][D, C] (WHOLE: then the last piece's slack)
+    __shared__ __attribute__((aligned(16))) uint32_t dU1[UWORDS];
     __shared__ __attribute__((aligned(16))) uint32_t dJ0[256];      // [quad][16]
     __shared__ __attribute__((aligned(16))) uint32_t dJ1[256];
 
@@ -814,6 +841,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
     const uint32_t j_bytes = (uint32_t)(np * a.g.img_bytes);
     const uint32_t jbase = (uint32_t)(L.img_off + L.core());
     const float scale = (float)(1. / (1 << level));
+    // Lanes that must not fetch get an offset no descriptor covers (every size is below 2 GB): the
+    // load runs with full exec and puts zeros into the lane's fixed LDS destination, which nothing
+    // reads.  An exec mask around the DMA cost a saveexec, a branch and a restore per row.
+    constexpr uint32_t kNoFetch = 0x80000000u;
 
     // slot state (uniform over the slot's lanes)
     bool live = false, dead = false;
@@ -976,11 +1007,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
         const s2 W1 = {(short)v10, (short)v11};
         const int o = (inx & 3) + k;
         const unsigned sel = (unsigned)o | 0x0c00u | ((unsigned)(o + 1) << 16) | 0x0c000000u;
-        // this lane's 16 J bytes: the quad's first 12 dwords cover every lane's taps
-        uint32_t joff = jrel + jbase + (uint32_t)(iny * pitch + (inx & ~3) + 16 * k);
-        // union sources (the lanes past the image are masked at the DMA)
+        // this lane's 16 J bytes: the quad's taps span 44 bytes, so lanes 0-2 carry them and lane 3
+        // fetches nothing (its zeros land in dwords 12-15 of the quad's 16, which read_j leaves alone)
+        const uint32_t joff = k < 3 ? jrel + jbase + (uint32_t)(iny * pitch + (inx & ~3) + 16 * k) : kNoFetch;
+        // union sources; the last piece's lanes past the image fetch nothing (WHOLE: by offset, else by exec)
         uint32_t uoff[ND];
         lk_piece_offsets<Sh>(q.ubase + (uint32_t)q.v0 * rowb, lane, uoff);
+        if (WHOLE && 1024 * (ND - 1) + 16 * lane >= Sh::BYTES) uoff[ND - 1] = kNoFetch;
         auto ubuf = [&](auto bc) -> uint32_t* {
             if constexpr (decltype(bc)::value == 0) return dU0;
             else return dU1;
@@ -989,24 +1022,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
             if constexpr (decltype(bc)::value == 0) return dJ0;
             else return dJ1;
         };
-        // window row yr of the union / J images: the per-lane offsets stay fixed and the row
-        // advance moves the descriptor's base (and shrinks its size by as much, so the range check
-        // keeps the same end): scalar work instead of a VALU add per piece and row
-        auto dma_union = [&](auto bc, int yr) {
+        // The next window row of the union / J images: the per-lane offsets stay fixed and the row
+        // advance moves the stream's descriptor (LkRunRsrc: base up, size down by as much, so the
+        // range check keeps the same end): three scalar instructions per stream and row, no VALU.
+        LkRunRsrc ur(cls_base, cls_bytes), jr(j_base, j_bytes);
+        auto dma_union = [&](auto bc) {
             uint32_t* U = ubuf(bc);
-            const uint32_t adv = (uint32_t)yr * rowb;
-            const __amdgpu_buffer_rsrc_t r = buf_rsrc32(cls_base + adv, cls_bytes - adv);
+            const __amdgpu_buffer_rsrc_t r = ur.rsrc();
 #pragma unroll
             for (int c = 0; c < ND; c++) {
-                if (c < ND - 1 || 1024 * c + 16 * lane < Sh::BYTES)
+                if (WHOLE || c < ND - 1 || 1024 * c + 16 * lane < Sh::BYTES)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr)(U + 256 * c), 16, (int)uoff[c], 0, 0, 0);
             }
+            ur.advance(rowb);
         };
-        auto dma_j = [&](auto bc, int yr) {
-            // the quad's taps span 44 bytes: lanes 0-2 carry them, lane 3 stays idle
-            const uint32_t adv = (uint32_t)(yr * pitch);
-            const __amdgpu_buffer_rsrc_t r = buf_rsrc32(j_base + adv, j_bytes - adv);
-            if (k < 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr)jbuf(bc), 16, (int)joff, 0, 0, 0);
+        auto dma_j = [&](auto bc) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(jr.rsrc(), (lds_ptr)jbuf(bc), 16, (int)joff, 0, 0, 0);
+            jr.advance((uint32_t)pitch);
         };
         const int jl = (lane >> 2) * 16, el = 2 * (slot * UW + q.off + k);
         auto read_j = [&](auto bc, uint32_t (&rj)[11]) {
@@ -1021,9 +1053,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
         using I1 = std::integral_constant<int, 1>;
         // taps of the current window row (pa) are the previous row's lower taps (pb)
         s2 pa[10], pb[10];
-        dma_union(I0{}, 0);
-        dma_j(I0{}, 0);
-        dma_j(I1{}, 1);
+        dma_union(I0{});
+        dma_j(I0{});
+        dma_j(I1{});
         lk_vmcnt0();
         {
             uint32_t rj[11];
@@ -1031,18 +1063,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
 #pragma unroll
             for (int gi = 0; gi < 10; gi++) pa[gi] = __builtin_bit_cast(s2, __builtin_amdgcn_perm(rj[gi + 1], rj[gi], sel));
         }
-        // row y (in buffer R = y % 2): wait until union row y and J row y+1 have landed, fetch
-        // union row y+1 and J row y+2 into the buffers rows y-1 / y (already summed) used, and sum
-        // the row.  An opaque use of acc pins each row's arithmetic before the next row's wait.
+        // row y (in buffer R = y % 2; union row y and J row y+1 have landed): fetch union row y+1
+        // and J row y+2 into the buffers rows y-1 / y (already summed) used, sum the row, and wait
+        // for what was fetched.  An opaque use of acc pins each row's arithmetic before that wait.
+        // The wait stands at the row's end, not at its start, so that row 0 (whose data the wait
+        // above covers) needs no test; after the last row, which fetches nothing, it is empty.
         // Two bodies (Fc): the exact one rounds each product to float and then adds, as the
         // reference does; the fused one is one fma per element, the same bits wherever the product
         // is exact -- every product of a certified window (kLkCertMax).
         auto row = [&](auto Fc, int y, auto Rc, s2 (&up)[10], s2 (&lo)[10]) {
             constexpr bool FUSED = decltype(Fc)::value;
             constexpr int R = decltype(Rc)::value;
-            if (y) lk_vmcnt0();
-            if (y + 1 < kWin) dma_union(std::integral_constant<int, 1 - R>{}, y + 1);
-            if (y + 2 <= kWin) dma_j(Rc, y + 2);
+            if (y + 1 < kWin) dma_union(std::integral_constant<int, 1 - R>{});
+            if (y + 2 <= kWin) dma_j(Rc);
             __builtin_amdgcn_sched_barrier(0);
             // the row's LDS reads back to back (their latencies overlap), then the arithmetic
             uint32_t rj[11];
@@ -1064,25 +1097,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
                 else acc = acc + f * fd;
             }
             asm volatile("" : "+v"(acc));
+            lk_vmcnt0();
         };
         // The fused body runs iff every iterating point of the wave is certified: lanes that are
         // not iterating drop their sums, so they never veto, and a wave moves to the fused body once
         // its uncertified points have converged.
         const bool fused = a.fma && __all(!act || certd);
         if (a.body_cnt) (fused ? n_fused : n_exact)++;
-        if (fused) {
+        // row pairs; only the last row (kWin - 1) has nothing left to fetch: one test per pair
+        auto rows = [&](auto Fc) {
 #pragma unroll 1
             for (int y = 0; y < kWin; y += 2) {
-                row(std::true_type{}, y, I0{}, pa, pb);
-                row(std::true_type{}, y + 1, I1{}, pb, pa);
+                row(Fc, y, I0{}, pa, pb);
+                row(Fc, y + 1, I1{}, pb, pa);
             }
-        } else {
-#pragma unroll 1
-            for (int y = 0; y < kWin; y += 2) {
-                row(std::false_type{}, y, I0{}, pa, pb);
-                row(std::false_type{}, y + 1, I1{}, pb, pa);
-            }
-        }
+        };
+        if (fused) rows(std::true_type{});
+        else rows(std::false_type{});
         if (!act) acc = f2{0.f, 0.f};
         // b = (P0+P2) + (P1+P3) across the quad; inactive quads compute values they ignore
         const float b1s = (quad_bcast<0>(acc.x) + quad_bcast<2>(acc.x)) + (quad_bcast<1>(acc.x) + quad_bcast<3>(acc.x));
