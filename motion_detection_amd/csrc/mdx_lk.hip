@@ -11,7 +11,8 @@
 //              (P mod 2^L), so all points of a residue class share the bilinear weights: the
 //              16x-overlapping per-window interpolation of the reference becomes one
 //              interpolation per class and pixel.  Row-major (D, C) pairs per class and plane
-//              column: D = (Ix | Iy << 16) and C = 256 - 512*I (the J-chain bias, see below).
+//              column: D = (Ix | Iy << 16) and C = B + 256 - 512*I (the J-chain bias and the float
+//              bias word B = 0x4B400000, see below).
 //  k_lk_A      Per point: the gradient matrix sums A11/A12/A22 over the window and the minEig /
 //              determinant tests.
 //  k_lk_iter   The Newton iterations, on persistent waves fed from per-XCD work queues.
@@ -33,12 +34,17 @@
 // segment is loaded once per lane quad and read back from LDS by the quad's lanes.
 //
 // Arithmetic: J taps via v_perm_b32 + v_dot2_i32_i16 (signed weights: w11 may be -1);
-// dot2(pa, W0, dot2(pb, W1, C)) >> 9 == ((S + 256) >> 9) - I exactly, because C = 256 - 512*I
-// is a multiple-of-512 shift of the rounding bias.  Products are float multiplies of exactly
-// converted integers (one rounding of the exact product == the reference's (float)(int
-// product)).  Products/sums never go through a contracted FMA (-ffp-contract=off); k_lk_A's
-// explicit FMAs multiply operands whose product is exact in float (|Ix|, |Iy| <= 4080), so they
-// round like the separate multiply and add.
+// x = dot2(pa, W0, dot2(pb, W1, 256 - 512*I)) has x >> 9 == ((S + 256) >> 9) - I exactly, because
+// 256 - 512*I is a multiple-of-512 shift of the rounding bias.  The plane's C carries the float bias
+// word B on top of it, so the dot products give B + x, and jd = x >> 9 reaches float without a shift
+// or an integer convert: (B + x) & ~511 is the bit pattern of the float 12582912 + 512*jd, and
+// subtracting 12582912.f leaves 512*jd exactly (lk_jd512, mdx_plan.h, with the range proof; one
+// v_and_b32 and one v_sub_f32, both of the full-rate issue class, where v_cvt_f32_i32 is half rate).
+// The sums b thus run at 512 times the reference's, same roundings, and are scaled back by 2^-29
+// instead of 2^-20.  Products are float multiplies of exactly converted integers (one rounding of the
+// exact product == the reference's (float)(int product)).  Products/sums never go through a
+// contracted FMA (-ffp-contract=off); k_lk_A's explicit FMAs multiply operands whose product is exact
+// in float (|Ix|, |Iy| <= 4080), so they round like the separate multiply and add.
 #include "mdx_dev.h"
 
 #include <float.h>
@@ -115,6 +121,8 @@ __device__ __forceinline__ void lk_weights(float fa, float fb, int& w00, int& w0
 // evaluated with v_dot2 on 16-bit pairs (tap bytes, Ix / Iy halves; signed weights, w11 may be -1)
 // -- the same int32 sums without any 32-bit multiply (v_mul_lo_u32 is quarter rate).  (lo, hi)
 // hold the bytes of the tap rows y / y+1 with taps at bytes Q, Q+1; d* are the derivative words.
+// ival is the plain integer I*32 (shift, no float bias): the class kernels turn it into the plane's
+// C word (lk_class_c, mdx_plan.h); only k_lk_iter's J - I takes the biased route to float.
 template <int Q>
 __device__ __forceinline__ void lk_interp(uint32_t lo0, uint32_t hi0, uint32_t lo1, uint32_t hi1, uint32_t d00,
                                           uint32_t d01, uint32_t d10, uint32_t d11, s2 W0, s2 W1, int& ival, int& ixv,
@@ -269,16 +277,17 @@ __global__ __launch_bounds__(256) void k_lk_class(const uint8_t* __restrict__ py
         const s2 W0 = {(short)w00, (short)w01}, W1 = {(short)w10, (short)w11};
         static_for<0, 4>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
-            if (x0 + q >= L.w + kPad - 1) { cv[q] = 256; return; }
+            if (x0 + q >= L.w + kPad - 1) { cv[q] = lk_class_c(0); return; }
             int ival, ixv, iyv;
             lk_interp<q>(ib[0][0], ib[0][1], ib[1][0], ib[1][1], dw[0][q], dw[0][q + 1], dw[1][q], dw[1][q + 1], W0, W1,
                          ival, ixv, iyv);
             dv[q] = ((uint32_t)ixv & 0xffffu) | ((uint32_t)iyv << 16);
-            cv[q] = 256 - 512 * ival;   // J-chain bias: (S + C) >> 9 == ((S + 256) >> 9) - I
+            // J-chain bias: (S + 256 - 512*I) >> 9 == ((S + 256) >> 9) - I, under the float bias word
+            cv[q] = lk_class_c(ival);
         });
     } else {
 #pragma unroll
-        for (int q = 0; q < 4; q++) cv[q] = 256;
+        for (int q = 0; q < 4; q++) cv[q] = lk_class_c(0);
     }
     // (D, C) pairs, row-major: one 8-B element per plane column
     uint4* o = reinterpret_cast<uint4*>(base) + ((long long)v * C.PW + 4 * j) / 2;
@@ -338,7 +347,7 @@ __global__ __launch_bounds__(256) void k_lk_class_fused(const uint8_t* __restric
         int w00, w01, w10, w11;
         lk_weights(fa, fb, w00, w01, w10, w11);
         uint32_t dv[4] = {0, 0, 0, 0};
-        int cv[4] = {256, 256, 256, 256};
+        int cv[4] = {lk_class_c(0), lk_class_c(0), lk_class_c(0), lk_class_c(0)};
         if (inside) {
             const s2 W0 = {(short)w00, (short)w01}, W1 = {(short)w10, (short)w11};
             static_for<0, 4>([&](auto qc) {
@@ -349,7 +358,7 @@ __global__ __launch_bounds__(256) void k_lk_class_fused(const uint8_t* __restric
                 lk_interp<q>(rw[1][1], rw[1][2], rw[2][1], rw[2][2], dw[0][q], dw[0][q + 1], dw[1][q], dw[1][q + 1], W0,
                              W1, ival, ixv, iyv);
                 dv[q] = ((uint32_t)ixv & 0xffffu) | ((uint32_t)iyv << 16);
-                cv[q] = 256 - 512 * ival;
+                cv[q] = lk_class_c(ival);
             });
         }
         uint8_t* base = cls_out + (long long)pair * a.plan.bytes_per_pair + C.off + (long long)cls * C.class_bytes;
@@ -775,7 +784,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
     using Sh = LkShape<G, UW>;
     constexpr int LPS = Sh::LPS, S = Sh::S, ND = Sh::ND;
     constexpr float HALFW = 19.5f;
-    constexpr float FLT_SCALE = 1.f / (1 << 20);
+    // the reference's 2^-20, and 2^-9 for the row body's sums, which run at 512 times its (lk_jd512)
+    constexpr float JD_UNSCALE = 1.f / kLkJScale;
+    constexpr float FLT_SCALE = 1.f / (1 << 20) * JD_UNSCALE;
+    static_assert(FLT_SCALE == 1.f / (1 << 29), "2^-20 * 2^-9");
     constexpr int UB = S * UW;                                    // (D, C) pairs per union buffer
     // Row buffers: two, a window row is fetched while the one before it is summed (three measured
     // slower, profiles/r05_ab_lk_nb3.txt).  One __shared__ array per buffer, so that the compiler
@@ -1088,10 +1100,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
             for (int gi = 0; gi < 10; gi++) {
                 const v2u dc = dcs[gi];
                 lo[gi] = __builtin_bit_cast(s2, __builtin_amdgcn_perm(rj[gi + 1], rj[gi], sel));
-                // (J*32 - I*32) exactly as the reference's CV_DESCALE(...) - I
-                const int jd = __builtin_amdgcn_sdot2(up[gi], W0, __builtin_amdgcn_sdot2(lo[gi], W1, (int)dc.y, false),
-                                                      false) >> 9;
-                const float fd = (float)jd;
+                // 512 * (J*32 - I*32), the difference exactly as the reference's CV_DESCALE(...) - I: the
+                // dot products on top of C give the biased word B + x, lk_jd512 the float of (x >> 9) * 512
+                const float fd = lk_jd512((uint32_t)__builtin_amdgcn_sdot2(
+                    up[gi], W0, __builtin_amdgcn_sdot2(lo[gi], W1, (int)dc.y, false), false));
                 const f2 f = {(float)(int16_t)dc.x, (float)((int)dc.x >> 16)};
                 if constexpr (FUSED) acc = lk_fma(f, fd, acc);
                 else acc = acc + f * fd;
@@ -1124,8 +1136,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLkIterWaves
             const float dy = (A12 * b1 - A11 * b2) * Dinv;
             if (a.dbg && pt == a.dbg_pt && pair == 0) {
                 float4* t = a.dbg + (long long)a.g.nlev * a.npts + (level * 16 + j) * 4;
-                if (k == 0) { t[0] = make_float4(b1s, b2s, dx, dy); t[1] = make_float4(nx, ny, A11, Dinv); }
-                t[2 + (k >> 1)] = make_float4(k & 1 ? 0.f : acc.x, k & 1 ? 0.f : acc.y, acc.x, acc.y);
+                // the trace keeps the reference's scale: sums as they stand before its 2^-20
+                const f2 tacc = acc * JD_UNSCALE;
+                if (k == 0) {
+                    t[0] = make_float4(b1s * JD_UNSCALE, b2s * JD_UNSCALE, dx, dy);
+                    t[1] = make_float4(nx, ny, A11, Dinv);
+                }
+                t[2 + (k >> 1)] = make_float4(k & 1 ? 0.f : tacc.x, k & 1 ? 0.f : tacc.y, tacc.x, tacc.y);
             }
             nx = nx + dx;
             ny = ny + dy;

@@ -107,6 +107,45 @@ MDX_HD inline int lk_win_origin(int gi, int pixel_step, int level)
 // and a window is clamped into the UH plane rows.
 MDX_HD inline int lk_win_row0(int ipy, int UH) { return std::min(std::max(ipy + kPad, 0), UH - kWin); }
 
+// ---------------------------------------------------------------------------------------------
+// J - I to float by mantissa bias (the class planes' C word and k_lk_iter's row body, mdx_lk.hip).
+// The row body's two dot products give the int32 x = S + 256 - 512*I, of which the reference wants
+// jd = x >> 9 as a float.  S is the sum of w*t over the four taps: bytes t, weights w that sum to 16384
+// with w00, w01, w10 >= 0 and w11 >= -1, so -255 <= S <= 16385 * 255; I*32 lies in [0, 8160].  Hence
+// |x| < 2^22, and with the bias word B = 0x4B400000 (the float 1.5 * 2^23) added -- in the class plane,
+// so at no cost in the loop -- the word B + x is the bit pattern of the float 12582912 + x: same
+// exponent, 2^22 + x in the mantissa field.  Clearing its low 9 bits floors that field to a multiple of
+// 512, which is the float 12582912 + 512 * (x >> 9) (arithmetic shift), and subtracting 12582912.f
+// is exact: 512 * jd, by one v_and_b32 and one v_sub_f32 in place of a shift and an integer convert.
+// The factor 512 is a power of two and no value comes near overflow or the subnormals
+// (|f * fd * 512| <= 4080 * 8160 * 512, below 2.8e13 over a window's 1600 terms), so every product and
+// running sum is 512 times the unscaled one with the same roundings; the final scale takes it back.
+// tests/lk_jbias_check.cpp checks the identity over the whole range of x.
+constexpr uint32_t kLkJBiasWord = 0x4B400000u;   // B: the bit pattern of kLkJBiasFloat
+constexpr float kLkJBiasFloat = 12582912.f;      // 1.5 * 2^23
+constexpr uint32_t kLkJMask = 0xFFFFFE00u;       // clears the 9 bits the reference shifts out
+constexpr int kLkJScale = 512;                   // what lk_jd512's result carries: 2^9
+constexpr int kLkJShift = 9;                     // W_BITS1 - 5
+constexpr int kLkSMin = -255, kLkSMax = 16385 * 255;   // the four-tap sum S
+constexpr int kLkIMax = 8160;                          // I*32 <= 255 * 32
+constexpr int kLkXMin = kLkSMin + 256 - 512 * kLkIMax, kLkXMax = kLkSMax + 256;   // x = S + 256 - 512*I
+static_assert(16385 * 255 + 256 < (1 << 22), "largest x stays inside the mantissa field's upper half");
+static_assert(512 * 8160 + 255 - 256 < (1 << 22), "smallest x stays inside its lower half");
+static_assert((kLkJBiasWord & 0x7FFFFFu) == (1u << 22), "the bias puts x = 0 in the middle of the mantissa field");
+static_assert(kLkJBiasWord >> 23 == 127 + 23, "exponent 2^23: one mantissa step is 1");
+static_assert((1 << kLkJShift) == kLkJScale && kLkJMask == ~(uint32_t)(kLkJScale - 1), "mask, shift and scale agree");
+// the class planes' C word: the J-chain rounding bias 256 - 512*I (mdx_lk.hip) plus the bias word
+constexpr int kLkCBias = (int)kLkJBiasWord + 256;
+MDX_HD inline int lk_class_c(int ival) { return kLkCBias - 512 * ival; }
+// the biased dot-product word B + x -> (float)(x >> 9) * 512
+MDX_HD inline float lk_jd512(uint32_t biased)
+{
+    const uint32_t w = biased & kLkJMask;
+    float f;
+    __builtin_memcpy(&f, &w, sizeof(f));
+    return f - kLkJBiasFloat;
+}
+
 // (G, UW) shapes of the LK level kernels (mdx_lk.hip instantiates these; the host plan picks the
 // smallest UW >= a level's union span among the shapes of its G)
 #define LK_SHAPES LK_CASE(4, 48) LK_CASE(4, 56) LK_CASE(4, 64) LK_CASE(4, 72) LK_CASE(4, 80) LK_CASE(4, 96) \

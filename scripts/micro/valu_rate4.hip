@@ -26,7 +26,15 @@
     X(16, "v_bfe_i32", "v_bfe_i32 %0, %0, 16, 16", a1)                          \
     X(17, "v_mad_i32_i24", "v_mad_i32_i24 %0, %0, %1, %1", a)                   \
     X(18, "v_cvt_f32_i32_e64", "v_cvt_f32_i32_e64 %0, %1", a2)                  \
-    X(19, "v_mul_f32_sdwa", "v_mul_f32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD", f)
+    X(19, "v_mul_f32_sdwa", "v_mul_f32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD", f) \
+    /* the J - I mantissa-bias pair of k_lk_iter (lk_jd512): with a 32-bit literal, a VGPR and an SGPR operand */ \
+    X(20, "v_and_b32_lit", "v_and_b32 %0, 0xfffffe00, %0", a1)                  \
+    X(21, "v_and_b32_vgpr", "v_and_b32 %0, %0, %1", a)                          \
+    X(22, "v_and_b32_sgpr", "v_and_b32 %0, %1, %0", a3)                         \
+    X(23, "v_add_f32_lit", "v_add_f32 %0, 0xcb400000, %0", f1)                  \
+    X(24, "v_add_f32_sgpr", "v_add_f32 %0, %1, %0", f2)                         \
+    X(25, "v_pk_fma_f32", "v_pk_fma_f32 %0, %0, %1, %1", d)                     \
+    X(26, "v_fmac_f32", "v_fmac_f32 %0, %1, %1", f)
 
 template <int OP>
 __global__ __launch_bounds__(256) void k(uint32_t* out, int iters, uint32_t seed)
@@ -53,6 +61,8 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, int iters, uint32_t seed
         if (#kind[0] == 'a' && #kind[1] == '2') asm volatile(text : "+v"(f[i]) : "v"(a[(i + 1) & 7])); \
         if (#kind[0] == 'f' && #kind[1] == '1') asm volatile(text : "+v"(f[i]));                      \
         if (#kind[0] == 'f' && #kind[1] == '3') asm volatile(text : "+v"(a[i]) : "v"(f[(i + 1) & 7])); \
+        if (#kind[0] == 'a' && #kind[1] == '3') asm volatile(text : "+v"(a[i]) : "s"(seed));          \
+        if (#kind[0] == 'f' && #kind[1] == '2') asm volatile(text : "+v"(f[i]) : "s"(seed));          \
     }
                 OPS(EMIT)
             }
