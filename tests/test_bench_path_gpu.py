@@ -15,9 +15,13 @@ from a producer on another stream is correct once the producer's event is passed
 mdx_input_ready.
 """
 import ctypes as C
+from contextlib import ExitStack
 
 import numpy as np
 import pytest
+
+from oracle_check import (NO_FALLBACKS, OutputSet, assert_batch_equals_oracle, lk_env, run_batch, uploaded,
+                          without)
 
 pytestmark = pytest.mark.gpu
 
@@ -39,40 +43,6 @@ def _stack(pairs, slot_seeds):
     return g1, g2
 
 
-def _alloc_out(c, n, w, h, batch, vectors):
-    sizes = dict(np=batch * n * 8, st=batch * n, mask=batch * w * h, H=batch * 72, num=batch * 4)
-    if vectors:
-        sizes["vec"] = batch * n * 32
-    return {k: c.dev_alloc(v) for k, v in sizes.items()}
-
-
-def _read_out(c, o, n, w, h, batch):
-    r = dict(np=np.empty((batch, n, 2), np.float32), st=np.empty((batch, n), np.uint8),
-             mask=np.empty((batch, h, w), np.uint8), H=np.empty((batch, 9)), num=np.empty(batch, np.int32))
-    if "vec" in o:
-        r["vec"] = np.empty((batch, n, 4))
-    for k, arr in r.items():
-        c.d2h(arr, o[k])
-    return r
-
-
-def _check_slot(got, i, ref, label):
-    assert got["num"][i] == ref["num_vectors"], label
-    np.testing.assert_array_equal(got["st"][i], ref["status"], err_msg=label)
-    bad = np.nonzero((got["np"][i].view(np.uint32) != ref["next_pts"].view(np.uint32)).any(axis=1))[0]
-    assert bad.size == 0, f"{label}: {bad.size} LK points differ, first {bad[:5]}"
-    np.testing.assert_array_equal(got["H"][i].view(np.uint64), ref["H"].ravel().view(np.uint64), err_msg=label)
-    nbad = int((got["mask"][i] != ref["mask"]).sum())
-    assert nbad == 0, f"{label}: {nbad} mask pixels differ"
-    if "vec" in got:
-        np.testing.assert_array_equal(got["vec"][i], ref["vectors"], err_msg=label)
-
-
-def _call(c, batch, d1, d2, o, w, h):
-    c.flow_warp_diff_batch_dev(batch, d1, d2, w, h, w, w * h, 0, d_next_pts=o["np"], d_status=o["st"],
-                               d_vectors=o.get("vec", 0), d_mask=o["mask"], d_H=o["H"], d_num_vectors=o["num"])
-
-
 def test_benchmarked_path_1080p_x32_pipelined(mdx, oracle):
     """bench.py's timed step, twice back to back on different inputs (16 distinct pairs, 8 per call,
     each in 4 of the 32 slots), call pipelining on, one sync at the end: every pair's next_pts
@@ -86,31 +56,18 @@ def test_benchmarked_path_1080p_x32_pipelined(mdx, oracle):
     slots_b = [seeds_b[(3 * i + 1) % 8] for i in range(B)]      # another spread over the slots
     n = mdx.grid_count(W, H, PS)
     assert n % 16 == 0 and B % 8 == 0 and B >= 16               # the dataflow's conditions hold
-    with mdx.Context(0, W, H, B, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c:
-        ins = []
-        for slots in (slots_a, slots_b):
-            g1, g2 = _stack(pairs, slots)
-            d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-            c.h2d(d1, g1)
-            c.h2d(d2, g2)
-            ins.append((d1, d2))
-        outs = [_alloc_out(c, n, W, H, B, vectors=False), _alloc_out(c, n, W, H, B, vectors=True)]
+    with mdx.Context(0, W, H, B, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c, ExitStack() as stack:
+        ins = [stack.enter_context(uploaded(c, *_stack(pairs, slots))) for slots in (slots_a, slots_b)]
+        outs = [stack.enter_context(OutputSet(c, B, W, H, n, vectors=v)).prefill() for v in (False, True)]
         # a warm-up call into the second output set first, so that the two checked calls run with
         # the previous call still in flight (the bench's steady state)
-        _call(c, B, *ins[1], outs[1], W, H)
-        _call(c, B, *ins[0], outs[0], W, H)
-        _call(c, B, *ins[1], outs[1], W, H)
+        outs[1].call(*ins[1])
+        outs[0].call(*ins[0])
+        outs[1].call(*ins[1])
         c.sync()                                                # also the hand-off timeout check
-        got = [_read_out(c, o, n, W, H, B) for o in outs]
-        for o in outs:
-            for p in o.values():
-                c.dev_free(p)
-        for d1, d2 in ins:
-            c.dev_free(d1)
-            c.dev_free(d2)
-    for j, slots in enumerate((slots_a, slots_b)):
-        for i, s in enumerate(slots):
-            _check_slot(got[j], i, refs[s], f"call {j} slot {i} seed {s}")
+        got = [o.read() for o in outs]
+    assert_batch_equals_oracle(got[0], [refs[s] for s in slots_a], "call 0", fields=without("vectors"))
+    assert_batch_equals_oracle(got[1], [refs[s] for s in slots_b], "call 1")
 
 
 def _small_batch(mdx, w=320, h=240, batch=16, seed0=900):
@@ -128,7 +85,7 @@ def test_dataflow_fallback_is_bit_exact(mdx, oracle, monkeypatch, spin):
     not.  Each abandoned level is recomputed in sequence within the same call (launch_lk_v2), so
     the sync reports MDX_OK and every output is bit-exact against the oracle; the fallback counts
     say what happened (for -1: every level below the coarsest recomputed, in every call)."""
-    monkeypatch.setenv("MDX_LK_SPIN_MAX", spin)
+    lk_env(monkeypatch, spin_max=spin)
     seeds_a = [20141105 + i for i in range(8)]
     seeds_b = [20141305 + i for i in range(8)]
     pairs = _pairs(mdx, seeds_a + seeds_b, W, H)
@@ -136,34 +93,21 @@ def test_dataflow_fallback_is_bit_exact(mdx, oracle, monkeypatch, spin):
     slots_a = [seeds_a[i % 8] for i in range(B)]
     slots_b = [seeds_b[(5 * i + 3) % 8] for i in range(B)]
     n = mdx.grid_count(W, H, PS)
-    with mdx.Context(0, W, H, B, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c:
-        ins = []
-        for slots in (slots_a, slots_b):
-            g1, g2 = _stack(pairs, slots)
-            d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-            c.h2d(d1, g1)
-            c.h2d(d2, g2)
-            ins.append((d1, d2))
-        outs = [_alloc_out(c, n, W, H, B, vectors=True), _alloc_out(c, n, W, H, B, vectors=True)]
-        _call(c, B, *ins[0], outs[0], W, H)
-        _call(c, B, *ins[1], outs[1], W, H)
+    with mdx.Context(0, W, H, B, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c, ExitStack() as stack:
+        ins = [stack.enter_context(uploaded(c, *_stack(pairs, slots))) for slots in (slots_a, slots_b)]
+        outs = [stack.enter_context(OutputSet(c, B, W, H, n)).prefill() for _ in range(2)]
+        outs[0].call(*ins[0])
+        outs[1].call(*ins[1])
         c.sync()                                                # MDX_OK: no exception
         fb = c.lk_fallbacks()
-        got = [_read_out(c, o, n, W, H, B) for o in outs]
-        for o in outs:
-            for p in o.values():
-                c.dev_free(p)
-        for d1, d2 in ins:
-            c.dev_free(d1)
-            c.dev_free(d2)
+        got = [o.read() for o in outs]
     print("fallbacks:", fb)
     if spin == "-1":
         nlev = 5                                                # 1080p: levels 0..4
         assert fb["group_giveups"] > 0 and fb["gate_giveups"] == 2 * (nlev - 1)
         assert fb["levels_recomputed"] == 2 * (nlev - 1)
     for j, slots in enumerate((slots_a, slots_b)):
-        for i, s in enumerate(slots):
-            _check_slot(got[j], i, refs[s], f"spin {spin} call {j} slot {i} seed {s}")
+        assert_batch_equals_oracle(got[j], [refs[s] for s in slots], f"spin {spin} call {j}")
 
 
 @pytest.mark.parametrize("spin,w,h,batch", [(None, 1920, 1080, 1), (None, 640, 480, 4), (None, 1920, 1080, 16),
@@ -173,34 +117,24 @@ def test_small_batches_pipelined_back_to_back(mdx, oracle, monkeypatch, spin, w,
     does not take (it needs a multiple of 8 and at least 16 -- their levels run in sequence, so no
     hand-off can give up: the fallback counts stay 0), and 16, the smallest it does.  Also 4 pairs
     with MDX_LK_SPIN_MAX=-1, which must change nothing where no dataflow runs.  Bit-exact."""
-    if spin:
-        monkeypatch.setenv("MDX_LK_SPIN_MAX", spin)
+    lk_env(monkeypatch, spin_max=spin)
     seeds = [31000 + i for i in range(min(batch, 4))]
     pairs = _pairs(mdx, seeds, w, h)
     refs = _oracle_refs(oracle, pairs)
     slots = [seeds[i % len(seeds)] for i in range(batch)]
     n = mdx.grid_count(w, h, PS)
-    with mdx.Context(0, w, h, batch, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c:
-        g1, g2 = _stack(pairs, slots)
-        d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-        c.h2d(d1, g1)
-        c.h2d(d2, g2)
-        outs = [_alloc_out(c, n, w, h, batch, vectors=True) for _ in range(2)]
+    with mdx.Context(0, w, h, batch, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c, ExitStack() as stack:
+        d1, d2 = stack.enter_context(uploaded(c, *_stack(pairs, slots)))
+        outs = [stack.enter_context(OutputSet(c, batch, w, h, n)).prefill() for _ in range(2)]
         for o in outs:
-            _call(c, batch, d1, d2, o, w, h)
+            o.call(d1, d2)
         c.sync()
         fb = c.lk_fallbacks()
-        got = [_read_out(c, o, n, w, h, batch) for o in outs]
-        for o in outs:
-            for p in o.values():
-                c.dev_free(p)
-        c.dev_free(d1)
-        c.dev_free(d2)
+        got = [o.read() for o in outs]
     if not spin and batch < 16:
-        assert fb == {"group_giveups": 0, "gate_giveups": 0, "levels_recomputed": 0}
+        assert fb == NO_FALLBACKS
     for j in range(2):
-        for i, sd in enumerate(slots):
-            _check_slot(got[j], i, refs[sd], f"{w}x{h} x{batch} spin {spin} call {j} slot {i}")
+        assert_batch_equals_oracle(got[j], [refs[sd] for sd in slots], f"{w}x{h} x{batch} spin {spin} call {j}")
 
 
 def test_smaller_batch_behind_larger_pipelined(mdx, oracle):
@@ -217,31 +151,20 @@ def test_smaller_batch_behind_larger_pipelined(mdx, oracle):
     refs = _oracle_refs(oracle, pairs)
     slots = [[seeds[i % 8] for i in range(b1)], [seeds[(3 * i + 5) % 8] for i in range(b2)]]
     n = mdx.grid_count(w, h, PS)
-    with mdx.Context(0, w, h, b1, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c:
-        ins, outs = [], []
-        for b, sl in zip((b1, b2), slots):
-            g1, g2 = _stack(pairs, sl)
-            d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-            c.h2d(d1, g1)
-            c.h2d(d2, g2)
-            ins.append((d1, d2))
-            outs.append(_alloc_out(c, n, w, h, b, vectors=True))
+    with mdx.Context(0, w, h, b1, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c, ExitStack() as stack:
+        ins = [stack.enter_context(uploaded(c, *_stack(pairs, sl))) for sl in slots]
+        outs = [stack.enter_context(OutputSet(c, b, w, h, n)) for b in (b1, b2)]
         # a warm-up call at the larger batch, so that the checked calls find every buffer allocated
-        _call(c, b1, *ins[0], outs[0], w, h)
+        outs[0].call(*ins[0])
         c.sync()
-        _call(c, b1, *ins[0], outs[0], w, h)
-        _call(c, b2, *ins[1], outs[1], w, h)
-        c.sync()
-        got = [_read_out(c, o, n, w, h, b) for o, b in zip(outs, (b1, b2))]
         for o in outs:
-            for p in o.values():
-                c.dev_free(p)
-        for d1, d2 in ins:
-            c.dev_free(d1)
-            c.dev_free(d2)
+            o.prefill()
+        outs[0].call(*ins[0])
+        outs[1].call(*ins[1])
+        c.sync()
+        got = [o.read() for o in outs]
     for j, sl in enumerate(slots):
-        for i, s in enumerate(sl):
-            _check_slot(got[j], i, refs[s], f"call {j} slot {i} seed {s}")
+        assert_batch_equals_oracle(got[j], [refs[s] for s in sl], f"call {j}")
 
 
 def test_default_run_fallbacks_are_recovered(mdx, monkeypatch):
@@ -249,22 +172,11 @@ def test_default_run_fallbacks_are_recovered(mdx, monkeypatch):
     device they stay 0 (the bench reports them per run), while on a shared, preempted or
     profiler-serialized device a wait may give up -- then every give-up must have been followed by
     a recompute within the same call (mdx_sync would otherwise return MDX_EHIP)."""
-    monkeypatch.delenv("MDX_LK_SPIN_MAX", raising=False)
+    lk_env(monkeypatch)
     w, h, batch = 640, 480, 16
     pairs, slots = _small_batch(mdx, w, h, batch, seed0=990)
-    n = mdx.grid_count(w, h, PS)
-    with mdx.Context(0, w, h, batch, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c:
-        g1, g2 = _stack(pairs, slots)
-        d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-        c.h2d(d1, g1)
-        c.h2d(d2, g2)
-        o = _alloc_out(c, n, w, h, batch, vectors=False)
-        for _ in range(4):
-            _call(c, batch, d1, d2, o, w, h)
-        c.sync()
-        fb = c.lk_fallbacks()
-        for p in list(o.values()) + [d1, d2]:
-            c.dev_free(p)
+    fb = run_batch(mdx, *_stack(pairs, slots), create=dict(pixel_step=PS, min_vector_size=1.0, call_pipelining=1),
+                   vectors=False, calls=4, back_to_back=True)["fallbacks"]
     print("lk_fallbacks", fb)
     if fb["group_giveups"] + fb["gate_giveups"] > 0:
         assert fb["levels_recomputed"] > 0, fb
@@ -315,27 +227,22 @@ def test_input_ready_event_from_producer_stream(mdx, oracle):
         hb[g1.nbytes:] = g2.ravel()
         with mdx.Context(0, w, h, batch, pixel_step=PS, min_vector_size=1.0, call_pipelining=1) as c:
             assert hip.hipMalloc(C.byref(big_d), BIG) == 0
-            d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
             z = np.zeros(g1.nbytes, np.uint8)
-            c.h2d(d1, z)
-            c.h2d(d2, z)
-            o = _alloc_out(c, n, w, h, batch, vectors=True)
-            assert hip.hipMemcpyAsync(big_d, big_h, BIG, 1, st) == 0          # keeps the producer busy
-            assert hip.hipMemcpyAsync(vp(d1), host, g1.nbytes, 1, st) == 0
-            assert hip.hipMemcpyAsync(vp(d2), vp(host.value + g1.nbytes), g2.nbytes, 1, st) == 0
-            assert hip.hipEventRecord(ev, st) == 0
-            c.input_ready(ev.value)
-            _call(c, batch, d1, d2, o, w, h)
-            c.sync()
-            got = _read_out(c, o, n, w, h, batch)
-            assert hip.hipStreamSynchronize(st) == 0
-            for p in list(o.values()) + [d1, d2]:
-                c.dev_free(p)
+            with uploaded(c, z, z) as (d1, d2), OutputSet(c, batch, w, h, n) as o:
+                o.prefill()
+                assert hip.hipMemcpyAsync(big_d, big_h, BIG, 1, st) == 0          # keeps the producer busy
+                assert hip.hipMemcpyAsync(vp(d1), host, g1.nbytes, 1, st) == 0
+                assert hip.hipMemcpyAsync(vp(d2), vp(host.value + g1.nbytes), g2.nbytes, 1, st) == 0
+                assert hip.hipEventRecord(ev, st) == 0
+                c.input_ready(ev.value)
+                o.call(d1, d2)
+                c.sync()
+                got = o.read()
+                assert hip.hipStreamSynchronize(st) == 0
             hip.hipFree(big_d)
     finally:
         hip.hipHostFree(host)
         hip.hipHostFree(big_h)
         hip.hipEventDestroy(ev)
         hip.hipStreamDestroy(st)
-    for i, s in enumerate(slots):
-        _check_slot(got, i, refs[s], f"slot {i}")
+    assert_batch_equals_oracle(got, [refs[s] for s in slots], "producer stream")

@@ -21,15 +21,15 @@ coarsest level, and the dataflow half of the launch descriptor (second iteration
 events, retire counters).  test_bench_path_gpu.py and test_parity_gpu.py run those on multi-level frames.
 """
 import ctypes as C
+from contextlib import ExitStack
 
 import numpy as np
 import pytest
 
 from motion_detection_amd import rowtile
-from test_bench_path_gpu import _alloc_out, _call, _check_slot, _read_out
+from oracle_check import (OutputSet, assert_batch_equals_oracle, assert_pair_equals_oracle, assert_traj_equals_oracle,
+                          uploaded)
 from test_cluster import same as same_clusters, uniform_points, uniform_reference
-from test_parity_gpu import _compare as same_pair
-from test_ring import _compare as same_trajectory
 from traj_seq import sequence
 
 W, H, PS, B = 96, 64, 10, 16
@@ -57,18 +57,16 @@ def _cycle(mdx, frames, slots):
 
         # two batched device calls back to back, one per pyramid half
         dev = []
-        obj["batch"] = []
-        ins = [(np.stack([frames[s] for s in sl]), np.stack([frames[s + 1] for s in sl])) for sl in slots]
-        for g1, g2 in ins:
-            d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-            c.h2d(d1, g1)
-            c.h2d(d2, g2)
-            o = _alloc_out(c, n, W, H, B, vectors=True)
-            dev += [d1, d2, *o.values()]
-            _call(c, B, d1, d2, o, W, H)
-            obj["batch"].append(o)
-        c.sync()
-        obj["batch"] = [_read_out(c, o, n, W, H, B) for o in obj["batch"]]
+        with ExitStack() as stack:
+            outs = []
+            for sl in slots:
+                d1, d2 = stack.enter_context(uploaded(c, np.stack([frames[s] for s in sl]),
+                                                      np.stack([frames[s + 1] for s in sl])))
+                outs.append(stack.enter_context(OutputSet(c, B, W, H, n)))
+                outs[-1].prefill()
+                outs[-1].call(d1, d2)
+            c.sync()
+            obj["batch"] = [o.read() for o in outs]
         for j, got in enumerate(obj["batch"]):
             out[f"batch{j}"] = _bytes(*(got[k] for k in sorted(got)))
 
@@ -129,12 +127,11 @@ def test_three_context_lifetimes_give_the_same_bytes(mdx, oracle):
     first, obj = _cycle(mdx, frames, slots)
     refs = [oracle.calculate_optical_flow(frames[s], frames[s + 1], pixel_step=PS, min_vector_size=1.0)
             for s in range(5)]
-    same_pair(obj["pair"], refs[0], "host pair")
+    assert_pair_equals_oracle(obj["pair"], refs[0], "host pair")
     for j, got in enumerate(obj["batch"]):
-        for i, s in enumerate(slots[j]):
-            _check_slot(got, i, refs[s], f"batched call {j} slot {i}")
-    same_trajectory(obj["traj"], oracle.flow_trajectory(frames[:5], pixel_step=PS), "list entry")
-    same_trajectory(obj["ring"], oracle.flow_trajectory(frames[1:6], pixel_step=PS), "ring")
+        assert_batch_equals_oracle(got, [refs[s] for s in slots[j]], f"batched call {j}")
+    assert_traj_equals_oracle(obj["traj"], oracle.flow_trajectory(frames[:5], pixel_step=PS), "list entry")
+    assert_traj_equals_oracle(obj["ring"], oracle.flow_trajectory(frames[1:6], pixel_step=PS), "ring")
     same_clusters(obj["cluster"], uniform_reference(300))
 
     for cycle in (2, 3):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import hostile_frames as hf
+from oracle_check import assert_batch_equals_oracle, assert_pair_equals_oracle, assert_traj_equals_oracle, run_batch
 
 # (w, h, pixel_step, channels): three levels; two; one (k_gray_pad); odd sizes; rgb; the batch shape
 HOST_SHAPES = [(330, 250, 10, 1), (165, 125, 5, 1), (64, 48, 4, 1), (333, 241, 7, 1), (320, 240, 10, 3)]
@@ -190,30 +191,6 @@ def test_trajectory_case_does_its_job(oracle, key):
 
 
 # ------------------------------------------------------------------------------------ GPU
-def _compare_pair(got, ref, label):
-    """got: dict(num, status, next_pts, vectors, H, mask) of one pair; everything bit for bit."""
-    assert int(got["num"]) == ref["num_vectors"], label
-    np.testing.assert_array_equal(got["status"], ref["status"], err_msg=label)
-    bad = np.nonzero((got["next_pts"].view(np.uint32) != ref["next_pts"].view(np.uint32)).any(axis=1))[0]
-    assert bad.size == 0, f"{label}: {bad.size} LK points differ, first {bad[:5]}: " \
-                          f"{got['next_pts'][bad[:3]]} vs {ref['next_pts'][bad[:3]]} why {ref['why'][bad[:3]]}"
-    np.testing.assert_array_equal(got["vectors"].view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
-    np.testing.assert_array_equal(got["H"].reshape(3, 3).view(np.uint64), ref["H"].view(np.uint64), err_msg=label)
-    nbad = int((got["mask"] != ref["mask"]).sum())
-    assert nbad == 0, f"{label}: {nbad} mask pixels differ"
-
-
-def _compare_traj(res, ref, label):
-    assert res.num_vectors == ref["num_vectors"], label
-    np.testing.assert_array_equal(res.traj_len, ref["traj_len"], err_msg=label)
-    for i in range(len(res.traj_len)):
-        k = int(ref["traj_len"][i])
-        a, b = res.traj[i, :k].view(np.uint32), ref["traj"][i, :k].view(np.uint32)
-        assert np.array_equal(a, b), f"{label}: point {i}: {res.traj[i, :k]} vs {ref['traj'][i, :k]}"
-    np.testing.assert_array_equal(res.start_pts.view(np.uint32), ref["start_pts"].view(np.uint32), err_msg=label)
-    np.testing.assert_array_equal(res.vectors.view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", HOST_SHAPES, ids=lambda s: "%dx%d_ps%d_ch%d" % s)
 @pytest.mark.parametrize("name", CASES)
@@ -225,35 +202,7 @@ def test_host_entry_hostile(mdx, ctx, oracle, name, shape):
         res = ctx.flow_warp_diff(a, b)
     finally:
         ctx.set_params(pixel_step=10)
-    got = dict(num=res.num_vectors, status=res.status, next_pts=res.next_pts, vectors=res.vectors, H=res.H,
-               mask=res.mask)
-    _compare_pair(got, ref, f"{name} {shape}")
-
-
-def _run_batch(mdx, g1, g2, w, h, ps):
-    B = len(g1)
-    n = mdx.grid_count(w, h, ps)
-    g1 = np.stack(g1)
-    g2 = np.stack(g2)
-    with mdx.Context(0, w, h, B) as c:
-        c.set_params(pixel_step=ps, min_vector_size=1.0)
-        bufs = {k: c.dev_alloc(s) for k, s in dict(i1=g1.nbytes, i2=g2.nbytes, np=B * n * 8, st=B * n,
-                                                    vec=B * n * 32, mask=B * w * h, H=B * 72, num=B * 4).items()}
-        try:
-            c.h2d(bufs["i1"], g1)
-            c.h2d(bufs["i2"], g2)
-            c.flow_warp_diff_batch_dev(B, bufs["i1"], bufs["i2"], w, h, w, w * h, mdx.FMT_GRAY8, bufs["np"],
-                                       bufs["st"], bufs["vec"], bufs["mask"], bufs["H"], 0, bufs["num"])
-            c.sync()
-            out = dict(np=np.empty((B, n, 2), np.float32), st=np.empty((B, n), np.uint8), vec=np.empty((B, n, 4)),
-                       mask=np.empty((B, h, w), np.uint8), H=np.empty((B, 3, 3)), num=np.empty(B, np.int32))
-            for k, arr in out.items():
-                c.d2h(arr, bufs[k])
-        finally:
-            for p in bufs.values():
-                c.dev_free(p)
-    return [dict(num=out["num"][i], status=out["st"][i], next_pts=out["np"][i], vectors=out["vec"][i], H=out["H"][i],
-                 mask=out["mask"][i]) for i in range(B)]
+    assert_pair_equals_oracle(res, ref, f"{name} {shape}")
 
 
 # hostile pairs in the even slots (the 1-px checkerboard among the first eight), ordinary ones between
@@ -285,8 +234,8 @@ def test_batch_dev_hostile(mdx, oracle, monkeypatch, B, env, shape):
                                                                   min_vector_size=1.0, why=True))
             a, b, ref = _refs[key]
         g1.append(a); g2.append(b); refs.append(ref)
-    for i, got in enumerate(_run_batch(mdx, g1, g2, w, h, ps)):
-        _compare_pair(got, refs[i], f"pair {i} of {B} {env}")
+    got = run_batch(mdx, np.stack(g1), np.stack(g2), set_params=dict(pixel_step=ps, min_vector_size=1.0))
+    assert_batch_equals_oracle(got, refs, f"{B} pairs {env}")
 
 
 @pytest.mark.gpu
@@ -307,7 +256,7 @@ def test_trajectory_hostile(mdx, oracle, monkeypatch, key, env):
     with mdx.Context(0, w, h, 1) as c:
         c.set_params(pixel_step=ps, min_vector_size=1.0)
         res = c.flow_trajectory(frames)
-    _compare_traj(res, ref, f"{key} {env}")
+    assert_traj_equals_oracle(res, ref, f"{key} {env}")
 
 
 @pytest.mark.gpu
@@ -341,5 +290,6 @@ def test_band_path_hostile(mdx, oracle):
         finally:
             for p in d.values():
                 c.dev_free(p)
-    got = dict(num=out["num"][0], status=out["st"], next_pts=out["np"], vectors=out["vec"], H=out["H"], mask=out["mask"])
-    _compare_pair(got, ref, "3 bands")
+    got = dict(num_vectors=out["num"][0], status=out["st"], next_pts=out["np"], vectors=out["vec"], H=out["H"],
+               mask=out["mask"])
+    assert_pair_equals_oracle(got, ref, "3 bands")

@@ -19,24 +19,19 @@ import functools
 import numpy as np
 import pytest
 
-import test_lk_fma_gpu as fma
+from lk_scenes import PS, H, W, board, smooth_pair
+from oracle_check import assert_batch_equals_oracle, lk_env, run_batch, without
 
 pytestmark = pytest.mark.gpu
 
-W, H, PS = fma.W, fma.H, fma.PS
 CASES = ("negative", "negative_dx3", "negative_dy3", "smooth")
-
-
-def _board():
-    yy, xx = np.mgrid[0:H + 3, 0:W + 3]
-    return ((((xx // 8) + (yy // 8)) & 1) * 255).astype(np.uint8)
 
 
 @functools.lru_cache(maxsize=None)
 def _pair(name):
     if name == "smooth":
-        return fma._smooth_pair(11)
-    b = _board()
+        return smooth_pair(11)
+    b = board()
     a = np.ascontiguousarray(b[:H, :W])
     moved = {"negative": b[:H, :W], "negative_dx3": b[:H, 3:3 + W], "negative_dy3": b[3:3 + H, :W]}[name]
     return a, np.ascontiguousarray(255 - moved)
@@ -57,39 +52,13 @@ def _grid():
 
 
 def _run(mdx, pair, batch, pipelined):
-    n = mdx.grid_count(W, H, PS)
-    g1 = np.stack([pair[0]] * batch)
-    g2 = np.stack([pair[1]] * batch)
-    with mdx.Context(0, W, H, batch, pixel_step=PS, min_vector_size=1.0, call_pipelining=int(pipelined)) as c:
-        d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-        c.h2d(d1, g1)
-        c.h2d(d2, g2)
-        o = dict(np=c.dev_alloc(batch * n * 8), st=c.dev_alloc(batch * n), mask=c.dev_alloc(batch * W * H),
-                 H=c.dev_alloc(batch * 72), num=c.dev_alloc(batch * 4))
-        for _ in range(2 if pipelined else 1):
-            c.flow_warp_diff_batch_dev(batch, d1, d2, W, H, W, W * H, 0, d_next_pts=o["np"], d_status=o["st"],
-                                       d_mask=o["mask"], d_H=o["H"], d_num_vectors=o["num"])
-        c.sync()
-        out = dict(next_pts=np.empty((batch, n, 2), np.float32), status=np.empty((batch, n), np.uint8),
-                   num_vectors=np.empty(batch, np.int32), H=np.empty((batch, 3, 3), np.float64),
-                   mask=np.empty((batch, H, W), np.uint8))
-        for k, d in (("next_pts", "np"), ("status", "st"), ("num_vectors", "num"), ("H", "H"), ("mask", "mask")):
-            c.d2h(out[k], o[d])
-        for p in list(o.values()) + [d1, d2]:
-            c.dev_free(p)
-    return out
+    return run_batch(mdx, np.stack([pair[0]] * batch), np.stack([pair[1]] * batch),
+                     create=dict(pixel_step=PS, min_vector_size=1.0, call_pipelining=int(pipelined)), vectors=False,
+                     calls=2 if pipelined else 1, back_to_back=True)
 
 
 def _check(got, ref, label):
-    for i in range(len(got["num_vectors"])):
-        where = f"{label} slot {i}"
-        assert got["num_vectors"][i] == ref["num_vectors"], where
-        np.testing.assert_array_equal(got["status"][i], ref["status"], err_msg=where)
-        bad = np.nonzero((got["next_pts"][i].view(np.uint32) != ref["next_pts"].view(np.uint32)).any(axis=1))[0]
-        assert bad.size == 0, f"{where}: {bad.size} LK points differ, first {bad[:5]}"
-        np.testing.assert_array_equal(got["H"][i].view(np.uint64), np.ascontiguousarray(ref["H"]).view(np.uint64),
-                                      err_msg=where)
-        np.testing.assert_array_equal(got["mask"][i], ref["mask"], err_msg=where)
+    assert_batch_equals_oracle(got, [ref] * len(got["num_vectors"]), label, fields=without("vectors"))
 
 
 @pytest.mark.parametrize("name", CASES[:3])
@@ -106,7 +75,7 @@ def test_negative_cases_iterate(oracle, name):
 @pytest.mark.parametrize("name", CASES)
 def test_bit_exact_vs_oracle(mdx, oracle, monkeypatch, name, fma_env):
     assert mdx.grid_count(W, H, PS) % 16 == 0                    # the dataflow's condition
-    fma._env(monkeypatch, fma_env, debug=False)
+    lk_env(monkeypatch, fma=fma_env)
     pair, ref = _pair(name), _ref(name)
     _check(_run(mdx, pair, 1, pipelined=False), ref, f"{name} fma={fma_env} batch 1")
     _check(_run(mdx, pair, 16, pipelined=True), ref, f"{name} fma={fma_env} batch 16")

@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 import hostile_frames as hf
+from oracle_check import NO_FALLBACKS, assert_batch_equals_oracle, lk_env, run_batch, without
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +41,6 @@ SHAPES = {
 }
 NPAIRS = 4            # distinct pairs; slot i of a batch holds pair i % NPAIRS
 NLEV = 3              # both frame sizes: levels 0 .. 2
-NO_FALLBACKS = {"group_giveups": 0, "gate_giveups": 0, "levels_recomputed": 0}
 
 
 def burst_pair(w, h, zoom, seed):
@@ -72,49 +72,21 @@ def _refs(w, h, ps):
             for a, b in _pairs(w, h)]
 
 
+CALLS = 2             # per _run
+
+
 def _run(mdx, w, h, ps, batch):
-    """The batch entry (call pipelining on, as the bench path has it; two calls, so the second one's
-    front end runs beside the first); every output prefilled with 0xAA before each call."""
-    n = mdx.grid_count(w, h, ps)
+    """The batch entry (call pipelining on, as the bench path has it), CALLS times, every output
+    prefilled with 0xAA before each call."""
     pairs = _pairs(w, h)
     g1 = np.stack([pairs[i % NPAIRS][0] for i in range(batch)])
     g2 = np.stack([pairs[i % NPAIRS][1] for i in range(batch)])
-    sizes = dict(np=batch * n * 8, st=batch * n, mask=batch * w * h, H=batch * 72, num=batch * 4)
-    with mdx.Context(0, w, h, batch, pixel_step=ps, min_vector_size=1.0, call_pipelining=1) as c:
-        d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-        o = {k: c.dev_alloc(s) for k, s in sizes.items()}
-        try:
-            c.h2d(d1, g1)
-            c.h2d(d2, g2)
-            for _ in range(2):
-                for k, s in sizes.items():
-                    c.h2d(o[k], np.full(s, 0xAA, np.uint8))
-                c.flow_warp_diff_batch_dev(batch, d1, d2, w, h, w, w * h, 0, d_next_pts=o["np"], d_status=o["st"],
-                                           d_mask=o["mask"], d_H=o["H"], d_num_vectors=o["num"])
-                c.sync()
-            out = dict(np=np.empty((batch, n, 2), np.float32), st=np.empty((batch, n), np.uint8),
-                       mask=np.empty((batch, h, w), np.uint8), H=np.empty((batch, 3, 3)), num=np.empty(batch, np.int32))
-            for k, arr in out.items():
-                c.d2h(arr, o[k])
-            out["fallbacks"] = c.lk_fallbacks()
-        finally:
-            for p in list(o.values()) + [d1, d2]:
-                c.dev_free(p)
-    return out
+    return run_batch(mdx, g1, g2, create=dict(pixel_step=ps, min_vector_size=1.0, call_pipelining=1), vectors=False,
+                     calls=CALLS)
 
 
 def _compare(got, refs, batch, label):
-    for i in range(batch):
-        ref = refs[i % NPAIRS]
-        lab = f"{label} pair {i}"
-        np.testing.assert_array_equal(got["st"][i], ref["status"], err_msg=lab)
-        bad = np.nonzero((got["np"][i].view(np.uint32) != ref["next_pts"].view(np.uint32)).any(axis=1))[0]
-        assert bad.size == 0, f"{lab}: {bad.size} LK points differ, first {bad[:5]}: " \
-                              f"{got['np'][i][bad[:3]]} vs {ref['next_pts'][bad[:3]]} why {ref['why'][bad[:3]]}"
-        assert got["num"][i] == ref["num_vectors"], lab
-        np.testing.assert_array_equal(got["H"][i].view(np.uint64), ref["H"].view(np.uint64), err_msg=lab)
-        nbad = int((got["mask"][i] != ref["mask"]).sum())
-        assert nbad == 0, f"{lab}: {nbad} mask pixels differ"
+    assert_batch_equals_oracle(got, [refs[i % NPAIRS] for i in range(batch)], label, fields=without("vectors"))
 
 
 @pytest.mark.parametrize("fma", ["1", "0"])
@@ -126,11 +98,7 @@ def test_rowloop_addressing(mdx, oracle, monkeypatch, shape, fma):
         assert n % 16 != 0                       # the dataflow's condition fails: levels in sequence
     elif batch >= 16:
         assert n % 16 == 0 and batch % 8 == 0    # the dataflow's conditions hold
-    if fma == "0":
-        monkeypatch.setenv("MDX_LK_FMA", "0")
-    else:
-        monkeypatch.delenv("MDX_LK_FMA", raising=False)
-    monkeypatch.delenv("MDX_LK_SPIN_MAX", raising=False)
+    lk_env(monkeypatch, fma=fma)
     got = _run(mdx, w, h, ps, batch)
     assert got["fallbacks"] == NO_FALLBACKS, got["fallbacks"]
     _compare(got, _refs(w, h, ps), batch, f"{shape} fma={fma}")
@@ -144,14 +112,12 @@ def test_which_shapes_take_the_dataflow(mdx, oracle, monkeypatch, shape):
     levels run in sequence counts nothing.  Bit-exact either way."""
     w, h, ps, batch = SHAPES[shape]
     flow = batch >= 16 and not shape.endswith("_seq")
-    monkeypatch.delenv("MDX_LK_FMA", raising=False)
-    monkeypatch.setenv("MDX_LK_SPIN_MAX", "-1")
+    lk_env(monkeypatch, spin_max="-1")
     got = _run(mdx, w, h, ps, batch)
     print(shape, "fallbacks", got["fallbacks"])
     if flow:
-        calls = 2                                # _run calls twice
-        assert got["fallbacks"]["gate_giveups"] == calls * (NLEV - 1), got["fallbacks"]
-        assert got["fallbacks"]["levels_recomputed"] == calls * (NLEV - 1), got["fallbacks"]
+        assert got["fallbacks"]["gate_giveups"] == CALLS * (NLEV - 1), got["fallbacks"]
+        assert got["fallbacks"]["levels_recomputed"] == CALLS * (NLEV - 1), got["fallbacks"]
     else:
         assert got["fallbacks"] == NO_FALLBACKS, got["fallbacks"]
     _compare(got, _refs(w, h, ps), batch, f"{shape} spin -1")

@@ -11,6 +11,8 @@ bit.
 import numpy as np
 import pytest
 
+from oracle_check import (OutputSet, assert_batch_equals_oracle, assert_pair_equals_oracle, assert_traj_equals_oracle,
+                          uploaded)
 from traj_seq import sequence
 
 W, H = 330, 250          # three pyramid levels, 825 points at pixel_step 10
@@ -40,25 +42,6 @@ def _embed(frames, stride, offset=0, frame_stride=None, seed=1):
             views.append(v)
         bufs.append(buf)
     return bufs, views
-
-
-def _compare(res, ref, label):
-    assert res.num_vectors == ref["num_vectors"], label
-    np.testing.assert_array_equal(res.status, ref["status"], err_msg=label)
-    np.testing.assert_array_equal(res.next_pts.view(np.uint32), ref["next_pts"].view(np.uint32), err_msg=label)
-    np.testing.assert_array_equal(res.vectors.view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
-    np.testing.assert_array_equal(res.H.view(np.uint64), ref["H"].view(np.uint64), err_msg=label)
-    assert int((res.mask != ref["mask"]).sum()) == 0, label
-
-
-def _compare_traj(res, ref, label):
-    assert res.num_vectors == ref["num_vectors"], label
-    np.testing.assert_array_equal(res.traj_len, ref["traj_len"], err_msg=label)
-    for i in range(len(res.traj_len)):
-        k = int(ref["traj_len"][i])
-        assert np.array_equal(res.traj[i, :k].view(np.uint32), ref["traj"][i, :k].view(np.uint32)), (label, i)
-    np.testing.assert_array_equal(res.start_pts.view(np.uint32), ref["start_pts"].view(np.uint32), err_msg=label)
-    np.testing.assert_array_equal(res.vectors.view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
 
 
 _shared = {}             # packed frames and their oracle results, computed once and left unchanged
@@ -112,7 +95,7 @@ def test_host_entry_gray_pitched(mdx, ctx, oracle, stride, offset):
     _, (va, vb) = _embed([a, b], stride, offset, seed=stride + offset)
     assert va.strides == (stride, 1)
     ctx.set_params(pixel_step=10, min_vector_size=1.0, fit_mode=mdx.FIT_FIRST4)
-    _compare(ctx.flow_warp_diff(va, vb), ref, f"gray stride {stride} offset {offset}")
+    assert_pair_equals_oracle(ctx.flow_warp_diff(va, vb), ref, f"gray stride {stride} offset {offset}")
 
 
 @pytest.mark.gpu
@@ -123,7 +106,7 @@ def test_host_entry_color_pitched(mdx, ctx, oracle, fmt_name, stride):
     _, (va, vb) = _embed([a, b], stride, seed=stride)
     ctx.set_params(pixel_step=10, min_vector_size=1.0, fit_mode=mdx.FIT_FIRST4)
     res = ctx.flow_warp_diff(va, vb, fmt=mdx.FMT_RGB8 if fmt_name == "rgb" else mdx.FMT_BGR8)
-    _compare(res, ref, f"{fmt_name} stride {stride}")
+    assert_pair_equals_oracle(res, ref, f"{fmt_name} stride {stride}")
 
 
 @pytest.mark.gpu
@@ -136,7 +119,7 @@ def test_host_entry_single_level_pitched(mdx, ctx, oracle):
         res = ctx.flow_warp_diff(va, vb)
     finally:
         ctx.set_params(pixel_step=10)
-    _compare(res, ref, "64x48 stride 67")
+    assert_pair_equals_oracle(res, ref, "64x48 stride 67")
 
 
 TRAJ_PITCH = [(1, 336, 0), (1, 333, 1), (3, 992, 0), (3, 1001, 2)]
@@ -148,7 +131,7 @@ def test_flow_trajectory_pitched(mdx, ctx, oracle, ch, stride, offset):
     frames, ref = _traj_ref(mdx, oracle, ch)
     _, views = _embed(frames, stride, offset, seed=stride)
     ctx.set_params(pixel_step=10, min_vector_size=1.0)
-    _compare_traj(ctx.flow_trajectory(views), ref, f"ch {ch} stride {stride} offset {offset}")
+    assert_traj_equals_oracle(ctx.flow_trajectory(views), ref, f"ch {ch} stride {stride} offset {offset}")
 
 
 @pytest.mark.gpu
@@ -164,7 +147,7 @@ def test_ring_pitched(mdx, ctx, oracle, ch, stride, offset):
         res = ctx.ring_trajectory(W, H, len(views))
     finally:
         ctx.ring_reset()
-    _compare_traj(res, ref, f"ring ch {ch} stride {stride} offset {offset}")
+    assert_traj_equals_oracle(res, ref, f"ring ch {ch} stride {stride} offset {offset}")
 
 
 @pytest.mark.gpu
@@ -189,31 +172,12 @@ def test_batch_dev_pitched(mdx, oracle, stride_px, fs_pad, base, ch):
     n = mdx.grid_count(W, H, 10)
     with mdx.Context(0, W, H, B) as c:
         c.set_params(pixel_step=10, min_vector_size=1.0)
-        bufs = {k: c.dev_alloc(s) for k, s in dict(i1=buf1.nbytes, i2=buf2.nbytes, np=B * n * 8, st=B * n,
-                                                    vec=B * n * 32, mask=B * W * H, H=B * 72, num=B * 4).items()}
-        try:
-            c.h2d(bufs["i1"], buf1)
-            c.h2d(bufs["i2"], buf2)
-            c.flow_warp_diff_batch_dev(B, bufs["i1"] + base, bufs["i2"] + base, W, H, stride, frame_stride,
-                                       mdx.FMT_GRAY8 if ch == 1 else mdx.FMT_RGB8, bufs["np"], bufs["st"],
-                                       bufs["vec"], bufs["mask"], bufs["H"], 0, bufs["num"])
+        with uploaded(c, buf1, buf2) as (d1, d2), OutputSet(c, B, W, H, n) as out:
+            out.prefill()
+            out.call(d1 + base, d2 + base, stride, frame_stride, mdx.FMT_GRAY8 if ch == 1 else mdx.FMT_RGB8)
             c.sync()
-            out = dict(np=np.empty((B, n, 2), np.float32), st=np.empty((B, n), np.uint8), vec=np.empty((B, n, 4)),
-                       mask=np.empty((B, H, W), np.uint8), H=np.empty((B, 3, 3)), num=np.empty(B, np.int32))
-            for k, arr in out.items():
-                c.d2h(arr, bufs[k])
-        finally:
-            for p in bufs.values():
-                c.dev_free(p)
-    for i in range(B):
-        ref = pairs[i][2]
-        label = f"pair {i} stride {stride} frame_stride {frame_stride} base {base}"
-        assert out["num"][i] == ref["num_vectors"], label
-        np.testing.assert_array_equal(out["st"][i], ref["status"], err_msg=label)
-        np.testing.assert_array_equal(out["np"][i].view(np.uint32), ref["next_pts"].view(np.uint32), err_msg=label)
-        np.testing.assert_array_equal(out["vec"][i].view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
-        np.testing.assert_array_equal(out["H"][i].view(np.uint64), ref["H"].view(np.uint64), err_msg=label)
-        assert int((out["mask"][i] != ref["mask"]).sum()) == 0, label
+            got = out.read()
+    assert_batch_equals_oracle(got, [p[2] for p in pairs], f"stride {stride} frame_stride {frame_stride} base {base}")
 
 
 @pytest.mark.gpu
@@ -248,9 +212,6 @@ def test_band_flow_pitched_rgb(mdx, oracle):
         finally:
             for p in d.values():
                 c.dev_free(p)
-    assert int(out["num"][0]) == ref["num_vectors"]
-    np.testing.assert_array_equal(out["st"], ref["status"])
-    np.testing.assert_array_equal(out["np"].view(np.uint32), ref["next_pts"].view(np.uint32))
-    np.testing.assert_array_equal(out["vec"].view(np.uint64), ref["vectors"].view(np.uint64))
-    np.testing.assert_array_equal(out["H"].view(np.uint64), ref["H"].view(np.uint64))
-    assert int((out["mask"] != ref["mask"]).sum()) == 0
+    got = dict(num_vectors=out["num"][0], status=out["st"], next_pts=out["np"], vectors=out["vec"], H=out["H"],
+               mask=out["mask"])
+    assert_pair_equals_oracle(got, ref, "3 bands, pitched rgb")

@@ -7,10 +7,13 @@ hypothesis solved by the reference's own 4-point solver.
 CPU: the oracle's restatement (ora_fit_ransac) against an independent numpy restatement of the
 draws and the inlier scoring, and known answers (an exact homography among outliers is found; on
 the synthetic pair the fit recovers the generator's true motion, which the first-4 rule does not).
-GPU: the k_ransac_* kernels equal the oracle bit for bit (H as float64 bits, num_vectors, mask).
+GPU: the k_ransac_* kernels equal the oracle bit for bit (H as float64 bits, num_vectors, mask, and
+the LK outputs in front of them).
 """
 import numpy as np
 import pytest
+
+from oracle_check import OutputSet, assert_pair_equals_oracle, uploaded, without
 
 M64 = (1 << 64) - 1
 
@@ -111,33 +114,18 @@ def test_ransac_gpu_bit_exact(mdx, oracle, w, h, batch, iters, thresh, seed):
     kw = dict(pixel_step=10, min_vector_size=1.0, fit_mode=2, ransac_iters=iters, ransac_thresh=thresh,
               ransac_seed=seed)
     with mdx.Context(0, w, h, batch, **kw) as c:
-        d1, d2 = c.dev_alloc(g1.nbytes), c.dev_alloc(g2.nbytes)
-        o = {k: c.dev_alloc(sz) for k, sz in dict(np=batch * n * 8, st=batch * n, mask=batch * w * h, H=batch * 72,
-                                                  num=batch * 4).items()}
-        c.h2d(d1, g1)
-        c.h2d(d2, g2)
-        c.flow_warp_diff_batch_dev(batch, d1, d2, w, h, w, w * h, 0, d_next_pts=o["np"], d_status=o["st"],
-                                   d_mask=o["mask"], d_H=o["H"], d_num_vectors=o["num"])
-        c.sync()
-        H = np.empty((batch, 9))
-        num = np.empty(batch, np.int32)
-        mask = np.empty((batch, h, w), np.uint8)
-        c.d2h(H, o["H"])
-        c.d2h(num, o["num"])
-        c.d2h(mask, o["mask"])
-        # the host entry too (one pair)
-        single = c.flow_warp_diff(g1[0], g2[0])
-        for p in list(o.values()) + [d1, d2]:
-            c.dev_free(p)
+        with uploaded(c, g1, g2) as (d1, d2), OutputSet(c, batch, w, h, n, vectors=False) as out:
+            out.prefill()
+            out.call(d1, d2)
+            c.sync()
+            got = out.read()
+        single = c.flow_warp_diff(g1[0], g2[0])         # the host entry too (one pair)
     for i, (a, b, _) in enumerate(pairs):
         ref = oracle.calculate_optical_flow(a, b, nthreads=16, ransac_iters=iters, ransac_thresh=thresh,
                                             ransac_seed=seed, **{k: v for k, v in kw.items() if not k.startswith("ransac")})
-        assert num[i] == ref["num_vectors"]
-        np.testing.assert_array_equal(H[i].view(np.uint64), ref["H"].ravel().view(np.uint64), err_msg=f"pair {i}")
-        assert int((mask[i] != ref["mask"]).sum()) == 0, f"pair {i}"
+        assert_pair_equals_oracle(OutputSet.slot(got, i), ref, f"pair {i}", fields=without("vectors"))
         if i == 0:
-            np.testing.assert_array_equal(single.H.ravel().view(np.uint64), ref["H"].ravel().view(np.uint64))
-            assert np.array_equal(single.mask, ref["mask"])
+            assert_pair_equals_oracle(single, ref, "host entry")
 
 
 def test_ransac_params_are_checked(mdx):

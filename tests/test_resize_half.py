@@ -369,7 +369,7 @@ def test_argument_checks(mdx, arena):
 def test_ring_push_half_matches_oracle(mdx, ctx, oracle, channels):
     """Five 647 x 483 frames pushed halved (324 x 242: both sides round up, partial column and row): the
     ring trajectory equals the oracle's on the checker's halved frames, bit for bit."""
-    from test_ring import _compare
+    from oracle_check import assert_traj_equals_oracle
     from traj_seq import sequence
     w, h = 647, 483
     frames = sequence(mdx, oracle, w, h, 5, seed=90 + channels, channels=channels)
@@ -379,14 +379,15 @@ def test_ring_push_half_matches_oracle(mdx, ctx, oracle, channels):
     ctx.ring_reset()
     for k, f in enumerate(frames):
         assert ctx.ring_push(f, 5, half=True) == k + 1
-    _compare(ctx.ring_trajectory(dw, dh, 5), oracle.flow_trajectory(halves, pixel_step=10, nthreads=8), "halved ring")
+    assert_traj_equals_oracle(ctx.ring_trajectory(dw, dh, 5),
+                              oracle.flow_trajectory(halves, pixel_step=10, nthreads=8), "halved ring")
 
 
 @pytest.mark.gpu
 def test_ring_mixes_halved_and_full_frames_of_one_size(mdx, ctx, oracle):
     """Frames pushed either way share a ring when their resulting sizes agree; a frame of another halved
     size empties it."""
-    from test_ring import _compare
+    from oracle_check import assert_traj_equals_oracle
     from traj_seq import sequence
     big = sequence(mdx, oracle, 640, 480, 3, seed=61, channels=3)
     small = sequence(mdx, oracle, 320, 240, 1, seed=62, channels=3)
@@ -395,7 +396,8 @@ def test_ring_mixes_halved_and_full_frames_of_one_size(mdx, ctx, oracle):
         assert ctx.ring_push(f, 5, half=True) == k + 1
     assert ctx.ring_push(small[0], 5) == 4                          # 320 x 240 as it is: the ring is kept
     ring = [half_ref(f) for f in big] + small
-    _compare(ctx.ring_trajectory(320, 240, 4), oracle.flow_trajectory(ring, pixel_step=10, nthreads=8), "mixed ring")
+    assert_traj_equals_oracle(ctx.ring_trajectory(320, 240, 4),
+                              oracle.flow_trajectory(ring, pixel_step=10, nthreads=8), "mixed ring")
     assert ctx.ring_push(frame_for(646, 480, 3), 5, half=True) == 1  # 323 x 240: another size, the ring starts over
     assert ctx.ring_push(big[0], 5, half=True) == 1
     ctx.ring_reset()

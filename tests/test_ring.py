@@ -11,17 +11,8 @@ every frame at :239-241) and a frame-size change.  CPU: argument checks of the e
 import numpy as np
 import pytest
 
+from oracle_check import assert_traj_equals_oracle
 from traj_seq import sequence
-
-
-def _compare(res, ref, label):
-    assert res.num_vectors == ref["num_vectors"], label
-    np.testing.assert_array_equal(res.traj_len, ref["traj_len"], err_msg=label)
-    for i in range(len(res.traj_len)):
-        k = int(ref["traj_len"][i])
-        assert np.array_equal(res.traj[i, :k].view(np.uint32), ref["traj"][i, :k].view(np.uint32)), (label, i)
-    np.testing.assert_array_equal(res.start_pts.view(np.uint32), ref["start_pts"].view(np.uint32), err_msg=label)
-    np.testing.assert_array_equal(res.vectors.view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
 
 
 def deque_sizes(keeps):
@@ -63,9 +54,9 @@ def test_ring_matches_oracle_frame_by_frame(mdx, ctx, oracle, w, h, ch, keeps):
         ring = frames[k + 1 - n:k + 1]
         res = ctx.ring_trajectory(w, h, n)
         ref = oracle.flow_trajectory(ring, pixel_step=10, nthreads=8)
-        _compare(res, ref, f"frame {k}, ring of {n}")
+        assert_traj_equals_oracle(res, ref, f"frame {k}, ring of {n}")
         if k == len(frames) - 1:     # the list entry on the same frames gives the same result
-            _compare(ctx.flow_trajectory(ring), ref, "list entry")
+            assert_traj_equals_oracle(ctx.flow_trajectory(ring), ref, "list entry")
 
 
 @pytest.mark.gpu
@@ -78,7 +69,8 @@ def test_ring_restarts_on_a_new_frame_size(mdx, ctx, oracle):
     assert ctx.ring_push(b[0], 5) == 1                    # another size: the ring starts over
     for f in b[1:]:
         ctx.ring_push(f, 5)
-    _compare(ctx.ring_trajectory(200, 150, 3), oracle.flow_trajectory(b, pixel_step=10), "after resize")
+    assert_traj_equals_oracle(ctx.ring_trajectory(200, 150, 3), oracle.flow_trajectory(b, pixel_step=10),
+                              "after resize")
     ctx.ring_reset()
     with pytest.raises(mdx.MdxError):
         ctx.ring_trajectory(200, 150, 2)                  # empty ring
@@ -94,14 +86,15 @@ def test_ring_pushes_in_flight(mdx, ctx, oracle):
     ctx.ring_reset()
     for f in frames[:5]:
         ctx.ring_push(f, 5)
-    _compare(ctx.ring_trajectory(w, h, 5), oracle.flow_trajectory(frames[:5], pixel_step=10, nthreads=8),
-             "five pushes in flight")
+    assert_traj_equals_oracle(ctx.ring_trajectory(w, h, 5),
+                              oracle.flow_trajectory(frames[:5], pixel_step=10, nthreads=8), "five pushes in flight")
     buf = mdx.host_empty(frames[0].shape)
     for k in (5, 6):
         buf[...] = frames[k]
         ctx.ring_push(buf, 5)
-        _compare(ctx.ring_trajectory(w, h, 5),
-                 oracle.flow_trajectory(frames[k - 4:k + 1], pixel_step=10, nthreads=8), f"pinned push {k}")
+        assert_traj_equals_oracle(ctx.ring_trajectory(w, h, 5),
+                                  oracle.flow_trajectory(frames[k - 4:k + 1], pixel_step=10, nthreads=8),
+                                  f"pinned push {k}")
 
 
 @pytest.mark.gpu
@@ -138,4 +131,4 @@ def test_mapped_outputs_equal_copied_outputs(mdx, ctx, oracle, nimg):
         assert a.tobytes() == b.tobytes()
     for i in range(len(mapped.traj_len)):
         assert not mapped.traj[i, int(mapped.traj_len[i]):].any()
-    _compare(mapped, oracle.flow_trajectory(frames, pixel_step=10, nthreads=8), "mapped")
+    assert_traj_equals_oracle(mapped, oracle.flow_trajectory(frames, pixel_step=10, nthreads=8), "mapped")

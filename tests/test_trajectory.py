@@ -13,6 +13,7 @@ trajectories (float32 bits), their lengths, the last pass's start points and Vec
 import numpy as np
 import pytest
 
+from oracle_check import assert_traj_equals_oracle
 from traj_seq import sequence
 
 
@@ -117,17 +118,6 @@ GPU_CASES = [
 ]
 
 
-def _compare(res, ref, label):
-    assert res.num_vectors == ref["num_vectors"], label
-    np.testing.assert_array_equal(res.traj_len, ref["traj_len"], err_msg=label)
-    for i in range(len(res.traj_len)):
-        k = int(ref["traj_len"][i])
-        a, b = res.traj[i, :k].view(np.uint32), ref["traj"][i, :k].view(np.uint32)
-        assert np.array_equal(a, b), f"{label}: point {i}: {res.traj[i, :k]} vs {ref['traj'][i, :k]}"
-    np.testing.assert_array_equal(res.start_pts.view(np.uint32), ref["start_pts"].view(np.uint32), err_msg=label)
-    np.testing.assert_array_equal(res.vectors.view(np.uint64), ref["vectors"].view(np.uint64), err_msg=label)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,n,ps,ch,seed", GPU_CASES)
 def test_trajectory_gpu_bit_exact(mdx, ctx, oracle, w, h, n, ps, ch, seed):
@@ -138,7 +128,7 @@ def test_trajectory_gpu_bit_exact(mdx, ctx, oracle, w, h, n, ps, ch, seed):
     finally:
         ctx.set_params(pixel_step=10)
     ref = oracle.flow_trajectory(frames, pixel_step=ps, nthreads=8)
-    _compare(res, ref, f"{w}x{h}x{n} ps{ps} ch{ch}")
+    assert_traj_equals_oracle(res, ref, f"{w}x{h}x{n} ps{ps} ch{ch}")
     assert len(res.trajectories) == len(ref["trajectories"])
 
 
@@ -172,8 +162,15 @@ def test_trajectory_flat_and_two_frames(mdx, ctx, oracle):
     frames = [np.full((120, 160), 50, np.uint8), np.full((120, 160), 50, np.uint8)]
     res = ctx.flow_trajectory(frames)
     ref = oracle.flow_trajectory(frames, pixel_step=10)
-    _compare(res, ref, "flat")
+    assert_traj_equals_oracle(res, ref, "flat")
     assert res.num_vectors == 0
+
+
+def _same_results(a, b, label):
+    """Two TrajectoryResults hold the same bits, entries past traj_len included."""
+    assert a.num_vectors == b.num_vectors, label
+    for x, y in ((a.traj_len, b.traj_len), (a.traj, b.traj), (a.start_pts, b.start_pts), (a.vectors, b.vectors)):
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), label
 
 
 @pytest.mark.gpu
@@ -190,12 +187,7 @@ def test_trajectory_chain_equals_per_pass_launches(mdx, oracle, monkeypatch):
             out[mode] = c.flow_trajectory(frames)
         finally:
             c.close()
-    a, b = out["1"], out["0"]
-    assert a.num_vectors == b.num_vectors
-    np.testing.assert_array_equal(a.traj_len, b.traj_len)
-    np.testing.assert_array_equal(a.traj.view(np.uint32), b.traj.view(np.uint32))
-    np.testing.assert_array_equal(a.start_pts.view(np.uint32), b.start_pts.view(np.uint32))
-    np.testing.assert_array_equal(a.vectors.view(np.uint64), b.vectors.view(np.uint64))
+    _same_results(out["1"], out["0"], "chained vs per pass")
 
 
 _PPW_SHAPE = (330, 250, 4, 10)   # three pyramid levels (330x250, 165x125, 83x63); 33 x 25 = 825 points
@@ -221,11 +213,7 @@ def test_trajectory_points_per_wave(mdx, oracle, monkeypatch, ppw):
         res = c.flow_trajectory(_ppw_shared["frames"])
     finally:
         c.close()
-    _compare(res, _ppw_shared["ref"], f"ppw {ppw}")
+    assert_traj_equals_oracle(res, _ppw_shared["ref"], f"ppw {ppw}")
     for other, b in _ppw_shared["res"].items():
-        assert res.num_vectors == b.num_vectors, (ppw, other)
-        np.testing.assert_array_equal(res.traj_len, b.traj_len)
-        np.testing.assert_array_equal(res.traj.view(np.uint32), b.traj.view(np.uint32))
-        np.testing.assert_array_equal(res.start_pts.view(np.uint32), b.start_pts.view(np.uint32))
-        np.testing.assert_array_equal(res.vectors.view(np.uint64), b.vectors.view(np.uint64))
+        _same_results(res, b, f"ppw {ppw} vs {other}")
     _ppw_shared["res"][ppw] = res
