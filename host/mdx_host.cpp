@@ -200,6 +200,32 @@ void MotionDetectionNode::stage_regions(FrameResult* r)
     r->regions.assign((size_t)8 * cap, 0);
     const int flags = p_.region_open ? MDX_REGIONS_OPEN3 : 0;
     mdx_region* recs = reinterpret_cast<mdx_region*>(r->regions.data());
+    if (p_.region_external) {
+        // the records, their parents and (region_contours) the hulls of the external ones in one call
+        const int maxv = p_.region_contours ? (int)std::min<long long>((long long)w * h, 2ll * std::min(w, h) * cap) : 0;
+        int total = 0, next = 0;
+        r->region_parent.assign((size_t)cap, 0);
+        r->region_external_index.assign((size_t)cap, 0);
+        if (p_.region_contours) {
+            r->region_contour_offsets.assign((size_t)cap + 1, 0);
+            r->region_contours.resize((size_t)2 * maxv);
+        }
+        const int rc = mdx_mask_regions_tree(ctx_, r->mask.data(), w, h, w, flags, p_.region_min_area, recs, cap,
+                                             &r->num_regions_all, &nkept, r->region_parent.data(),
+                                             r->region_external_index.data(), &next,
+                                             p_.region_contours ? r->region_contour_offsets.data() : nullptr,
+                                             r->region_contours.data(), maxv, &total);
+        if (rc < 0) throw std::runtime_error(std::string("mdx_mask_regions_tree: ") + mdx_last_error(ctx_));
+        const int n = std::min(nkept, cap);
+        r->regions.resize((size_t)8 * n);
+        r->region_parent.resize((size_t)n);
+        r->region_external_index.resize((size_t)next);
+        if (p_.region_contours) {
+            r->region_contour_offsets.resize((size_t)next + 1);
+            r->region_contours.resize((size_t)2 * std::min(total, maxv));
+        }
+        return;
+    }
     if (!p_.region_contours) {
         const int rc = mdx_mask_regions(ctx_, r->mask.data(), w, h, w, flags, p_.region_min_area, recs, cap,
                                         &r->num_regions_all, &nkept, nullptr, nullptr);

@@ -84,6 +84,10 @@ struct Params {
     // the convex hull of every kept mask region (regions_on(); mdx_mask_region_hulls): the
     // records and the hulls in one call, the label image staying on the device.  Off by default
     bool region_contours = false;
+    // findContours' RETR_EXTERNAL (regions_on(); mdx_mask_regions_tree): `regions` keeps every kept
+    // record and gains each one's parent blob and the external ones' indices; with region_contours the hulls are
+    // those of the external records.  Off by default
+    bool region_external = false;
 
     // Whether each optional stage runs on a processed frame (the conditions documented above, written
     // once: the node's stages and mdx_node's output files both ask here)
@@ -108,8 +112,13 @@ struct StageOutputs {
     std::vector<int32_t> regions;              // x, y, width, height, area, seed_x, seed_y, id of each kept one
     // region_contours: region i's convex hull is region_contours[2 * region_contour_offsets[i] ..
     // 2 * region_contour_offsets[i + 1]), (x, y) pairs in mdx_region_hulls_dev's order (include/mdx.h)
-    std::vector<int32_t> region_contour_offsets;    // regions.size() / 8 + 1 entries
+    // (region_external: hull i belongs to regions[region_external_index[i]])
+    std::vector<int32_t> region_contour_offsets;    // regions.size() / 8 + 1 entries (region_external: one per external + 1)
     std::vector<int32_t> region_contours;
+    // region_external: each kept region's parent (a component id, MDX_REGION_NO_PARENT, MDX_REGION_PARENT_UNKNOWN)
+    // and the positions in `regions` of the external ones
+    std::vector<int32_t> region_parent;
+    std::vector<int32_t> region_external_index;
     // detect_outliers: the grid vectors' flags (bit 0 angle, bit 1 magnitude; image rows outer) and their
     // statistics; the clusters of the outlier vectors fill num_clusters, cluster_labels (per grid vector,
     // -1 for a vector that is no outlier or has no flow), kept_clusters, rectangles and

@@ -22,6 +22,8 @@
 //            [cluster_contours=0]     (the convex hull of every kept cluster, showClusterContours' (:393, :510),
 //                                      behind each clustering stage that ran)
 //            [region_contours=0]      (pair path with region_min_area > 0: the convex hull of every kept region)
+//            [region_external=0]      (pair path with region_min_area > 0: findContours' RETR_EXTERNAL -- each kept
+//                                      region's parent blob; rectangles and hulls of the external regions only)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -58,7 +60,14 @@
 //                                 offsets[k + 1]; i32 xy[offsets[k]][2] -- record i's convex hull is
 //                                 xy[offsets[i] .. offsets[i + 1]), in mdx_region_hulls_dev's order (include/mdx.h);
 //                                 with log_contours=1 each hull goes to motion.log too (writeContour), behind
-//                                 the frame's region rectangles
+//                                 the frame's region rectangles.  With region_external=1 the hulls (and k)
+//                                 are those of the external records, hull i belonging to record
+//                                 external_index[i] of region_parents_<k>.bin, and so are the rectangles and
+//                                 hulls that go to motion.log, numbered among the external records
+//   region_parents_<k>.bin        the same with region_external=1: i32 k (the records of regions_<k>.bin); i32
+//                                 parent[k] (a component id, -1: external, -2: unknown; include/mdx.h
+//                                 mdx_region_parents_dev); i32 num_external; i32 external_index[num_external]
+//                                 (positions in the records of the external ones)
 //   motion.log                   log_contours=1: created at start; MotionLogger::writeBoundingBox of
 //                                 every kept cluster's rectangle (node.cpp:431-434), "frame, id, tl.x,
 //                                 tl.y, br.x, br.y" with frame = the node's global_frame_count_ during
@@ -165,6 +174,7 @@ int main(int argc, char** argv)
         p.residual_threshold = getd("residual_threshold", 0.2);
         p.cluster_contours = geti("cluster_contours", 0) != 0;
         p.region_contours = geti("region_contours", 0) != 0;
+        p.region_external = geti("region_external", 0) != 0;
         const bool polling = !p.use_all_frames;
         const int device = geti("device", 0);
         const std::string out = argv[2];
@@ -252,9 +262,22 @@ int main(int argc, char** argv)
                 ByteBuffer b{r.num_regions_all, (int32_t)(r.regions.size() / 8)};
                 b.put(r.regions);
                 b.write(out + "/regions" + sfx);
-                log_rectangles(r.regions.data(), 8, r.regions.size() / 8);
+                if (p.region_external) {
+                    ByteBuffer pb{(int32_t)(r.regions.size() / 8)};
+                    pb.put(r.region_parent);
+                    const int32_t next = (int32_t)r.region_external_index.size();
+                    pb.put(&next, 4);
+                    pb.put(r.region_external_index);
+                    pb.write(out + "/region_parents" + sfx);
+                    std::vector<int32_t> ext;     // the external records, in record order
+                    for (const int32_t i : r.region_external_index)
+                        ext.insert(ext.end(), r.regions.begin() + 8 * i, r.regions.begin() + 8 * (i + 1));
+                    log_rectangles(ext.data(), 8, ext.size() / 8);
+                } else {
+                    log_rectangles(r.regions.data(), 8, r.regions.size() / 8);
+                }
                 if (p.region_contours) {
-                    ByteBuffer hb{(int32_t)(r.regions.size() / 8)};
+                    ByteBuffer hb{(int32_t)(p.region_external ? r.region_external_index.size() : r.regions.size() / 8)};
                     hb.put(r.region_contour_offsets);
                     hb.put(r.region_contours);
                     hb.write(out + "/region_hulls" + sfx);

@@ -43,7 +43,8 @@ extern "C" {
                                    mdx_ring_push_half (new entries; mdx_params is unchanged, 80 bytes).
                                 11: mdx_cluster_hulls (a new entry; mdx_params is unchanged, 80 bytes).
                                    mdx_region_hulls_dev and mdx_mask_region_hulls joined under 11: two
-                                   more entries, nothing existing changes. */
+                                   more entries, nothing existing changes.  mdx_region_parents_dev and
+                                   mdx_mask_regions_tree joined under 11 the same way. */
 
 /* Return codes */
 #define MDX_OK           0
@@ -570,8 +571,8 @@ int mdx_find_outliers(mdx_ctx* ctx, const double* vectors, int batch, int n, int
  *   morphologyDefaultBorderValue, one iteration, centre anchor).  Without the flag D is the
  *   foreground itself.
  *   Components: the 8-connected components of D, ordered by the raster index y*w + x of their first
- *   pixel.  Nested components are all reported: RETR_EXTERNAL would drop a blob that lies inside
- *   another blob's hole; no hierarchy is built.
+ *   pixel.  Nested components are all reported here: findContours' RETR_EXTERNAL drops a blob that
+ *   lies inside another blob's hole, and mdx_region_parents_dev (below) makes that cut on the device.
  *   Record: x, y, width, height = (xmin, ymin, xmax - xmin + 1, ymax - ymin + 1), as
  *   mdx_cluster_euclidean's rects; area = pixel count; seed_x, seed_y = the first pixel; id = the
  *   component's index among ALL components.
@@ -611,8 +612,9 @@ int mdx_mask_regions(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int stride
  *   record's id.  The rectangle is clamped to the frame first: the entry cannot validate device
  *   records and never touches memory outside the frame because of one.  Pixels of other regions inside
  *   the rectangle (nested or interleaved blobs) take no part.  A record whose id matches no pixel
- *   gives 0 vertices.  A nested blob's hull is reported like any other: no hierarchy, no RETR_EXTERNAL
- *   filtering, and no contour polylines -- the hull only.  (A record edited so that its area
+ *   gives 0 vertices.  A nested blob's hull is reported like any other (for the external blobs only,
+ *   pass mdx_region_parents_dev's d_external and d_num_external), and no contour polylines -- the
+ *   hull only.  (A record edited so that its area
  *   understates its members may have its hull cut short at min(area, 2*width, 2*height) vertices.)
  *   Vertices, order, start: mdx_cluster_hulls' contract, minus the conversion (members are integers
  *   already).  Extreme points only: collinear boundary points are excluded, one pixel gives 1 vertex,
@@ -657,6 +659,78 @@ int mdx_mask_region_hulls(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int s
                           mdx_region* regions, int max_regions, int* num_all, int* num_kept,
                           int32_t* offsets /* [max_regions + 1] */, int32_t* xy, int max_vertices, int* num_vertices);
 
+/*
+ * The parent blob of each mask region, and findContours' RETR_EXTERNAL filter: the
+ * reference's getMotionContours asks for CV_RETR_EXTERNAL (background_subtractor.cpp:31-35), which
+ * keeps the blobs that lie in no other blob's hole.  Which blob encloses which follows from the label
+ * image alone; integer and exact.  Restated, and unpinned against a real build like the rest of the
+ * recipe (OpenCV 2.4's findContours is also said to clear the frame's outermost ring of pixels before
+ * it traces; neither mdx_mask_regions_dev nor this entry does that).
+ *   Inputs: what mdx_mask_regions_dev wrote -- d_labels, d_regions and d_num_kept; the mask is not
+ *   needed.  Per image b the first r = min(max(num_kept[b], 0), max_regions) records take part.
+ *   Background: the pixels with a label < 0, together with everything outside the frame.  Its
+ *   components are 4-connected (the dual of the 8-connected foreground).  The component that holds
+ *   the outside of the frame is the frame background: any background pixel of the frame's first or
+ *   last row or column belongs to it.  Every other background component is a hole; a hole never
+ *   touches the frame's edge.
+ *   Enclosing background of a blob C: the background component of the pixel directly above C's seed,
+ *   (seed_x, seed_y - 1); the frame background when seed_y == 0.  (That pixel is background because
+ *   the seed is C's first pixel in raster order, and it lies in none of C's own holes: those are closed
+ *   in by pixels of C and so lie below C's top row.)
+ *   Parent: MDX_REGION_NO_PARENT (-1, C is external) when the enclosing background is the frame
+ *   background; otherwise the id, among ALL components, of the pixel directly above the hole's first
+ *   pixel in raster order.  (That pixel exists, is foreground, and belongs to the blob whose hole this
+ *   is: an island inside the hole lies strictly below the hole's top row.)  The parent may be a
+ *   component that min_area or max_regions left out of the records.
+ *   Records the entry cannot trust (d_regions is device memory a caller may have edited): a record
+ *   gets MDX_REGION_PARENT_UNKNOWN (-2) and is not external when its seed lies outside the frame, its
+ *   seed pixel does not carry the record's id, or the pixel above its seed is not background.  No
+ *   access outside the frame ever results from a record.
+ * Outputs (each may be NULL):
+ *   d_parent       [batch][max_regions] the parent of each participating record
+ *   d_external     [batch][max_regions] the records with parent -1, in record order: what RETR_EXTERNAL
+ *                  keeps.  Only the first num_external[b] entries of image b are written.
+ *   d_num_external [batch] how many those are
+ * Entries of d_parent and d_external past the r participating records are not touched.
+ * mdx_region_parents_dev is asynchronous on the context stream and never synchronises with the host:
+ * it chains behind mdx_mask_regions_dev with no round trip, mdx_region_hulls_dev chains behind it on
+ * d_external / d_num_external in place of d_regions / d_num_kept (the hulls of the external blobs only),
+ * and it honours mdx_input_ready like the other device entries.  Every pointer is a device pointer.
+ * Five launches per call for any batch up to 65,535 images (the background labelled per 64 x 32 tile,
+ * the tiles joined straight across their borders, the tile roots flattened, then every pixel; one
+ * workgroup per image resolves the records); no workgroup waits for another.  max_regions == 0 is
+ * MDX_OK with num_external[b] = 0.
+ * Scratch belongs to the context, is a function of (batch, w, h) alone and only grows:
+ *   batch * 5 * w * h bytes (+ 510 of alignment)
+ * -- per pixel the background's 4-byte parent word and a mark byte; nothing is cleared between calls.
+ * No allocation after the first call at a given (batch, w, h).
+ * MDX_EINVAL: a null context; batch < 1; w or h < 1; w*h > 2^30; max_regions < 0; d_labels NULL;
+ * d_regions or d_num_kept NULL with max_regions > 0; d_external overlapping d_regions.
+ */
+#define MDX_REGION_NO_PARENT (-1)
+#define MDX_REGION_PARENT_UNKNOWN (-2)
+int mdx_region_parents_dev(mdx_ctx* ctx, int batch, const int32_t* d_labels /* [batch][h][w] */, int w, int h,
+                           const mdx_region* d_regions /* [batch][max_regions] */, int max_regions,
+                           const int32_t* d_num_kept /* [batch] */,
+                           int32_t* d_parent /* [batch][max_regions] or NULL */,
+                           mdx_region* d_external /* [batch][max_regions] or NULL; must not overlap d_regions */,
+                           int32_t* d_num_external /* [batch] or NULL */);
+/* mdx_mask_regions, the parents of its records and, when offsets is given, the hulls of its EXTERNAL
+ * records for one mask in host memory, synchronous: the label image stays on the device and never
+ * crosses PCIe.  regions, num_all, num_kept as mdx_mask_regions (every kept record, nested or not);
+ * parent [max_regions]: the first min(num_kept, max_regions) entries are written; external_index
+ * [max_regions]: external_index[i] is the position in `regions` of the i-th external record, the first
+ * num_external entries are written (either array may be NULL).  offsets (NULL: no hulls; xy,
+ * max_vertices and num_vertices are then ignored), xy, num_vertices: mdx_mask_region_hulls' contract with
+ * the external records in place of the kept ones, hull i belonging to regions[external_index[i]].
+ * Errors: mdx_mask_regions', plus with offsets given mdx_mask_region_hulls'. */
+int mdx_mask_regions_tree(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                          mdx_region* regions, int max_regions, int* num_all, int* num_kept,
+                          int32_t* parent /* [max_regions] */, int32_t* external_index /* [max_regions] */,
+                          int* num_external,
+                          int32_t* offsets /* [max_regions + 1] or NULL */, int32_t* xy, int max_vertices,
+                          int* num_vertices);
+
 /* Page-locked host memory for frames and outputs (e.g. the node's rgb8 staging buffer and its
  * trajectory outputs): copies between it and the device run as DMA at full link rate, while a
  * pageable buffer is staged by the runtime through bounce buffers.  Any entry taking host pointers
@@ -678,7 +752,9 @@ int mdx_memcpy_d2h(mdx_ctx* ctx, void* dst, const void* src, size_t bytes);
  * 5 warp+diff, 6 whole call; mdx_timing_calls returns how many calls were recorded.
  * mdx_cluster_hulls records a set too: stage 0 its upload, 3 k_hull, 4 its readback, 6 the three
  * together (1, 2 and 5 are empty); mdx_region_hulls_dev too: stage 2 its scan of the records' bounds, 3
- * k_region_hull, 4 the scan that packs xy, 6 the three together (0, 1 and 5 are empty). */
+ * k_region_hull, 4 the scan that packs xy, 6 the three together (0, 1 and 5 are empty);
+ * mdx_region_parents_dev too: stages 0 .. 4 its tile, merge, roots, flatten and resolve kernels, 6 the
+ * five together (5 is empty). */
 int mdx_enable_timing(mdx_ctx* ctx, int on);
 int mdx_timing_calls(const mdx_ctx* ctx);
 int mdx_stage_ms(mdx_ctx* ctx, int stage, float* ms);

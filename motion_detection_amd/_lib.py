@@ -33,6 +33,8 @@ VCLUSTER_MAX_POINTS = 131072  # include/mdx.h MDX_VCLUSTER_MAX_POINTS
 OUTLIERS_INCLUDE_ZEROS = 1    # include/mdx.h MDX_OUTLIERS_INCLUDE_ZEROS
 OUTLIERS_MAX_POINTS = 131072  # include/mdx.h MDX_OUTLIERS_MAX_POINTS
 HULL_MAX_SPAN = 8192          # include/mdx.h MDX_HULL_MAX_SPAN
+REGION_NO_PARENT = -1         # include/mdx.h MDX_REGION_NO_PARENT
+REGION_PARENT_UNKNOWN = -2    # include/mdx.h MDX_REGION_PARENT_UNKNOWN
 
 # every symbol include/mdx.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -49,6 +51,7 @@ EXPORTED = [
     "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions", "mdx_cluster_vectors",
     "mdx_find_outliers", "mdx_half_size", "mdx_resize_half_dev", "mdx_resize_half", "mdx_ring_push_half",
     "mdx_cluster_hulls", "mdx_region_hulls_dev", "mdx_mask_region_hulls",
+    "mdx_region_parents_dev", "mdx_mask_regions_tree",
 ]
 ABI_VERSION = 11  # include/mdx.h MDX_ABI_VERSION
 
@@ -275,6 +278,12 @@ def lib() -> C.CDLL:
     L.mdx_mask_region_hulls.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.mdx_mask_region_hulls.restype = C.c_int
+    L.mdx_region_parents_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.mdx_region_parents_dev.restype = C.c_int
+    L.mdx_mask_regions_tree.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), vp, vp,
+                                        C.c_int, C.POINTER(C.c_int)]
+    L.mdx_mask_regions_tree.restype = C.c_int
     _lib = L
     return L
 

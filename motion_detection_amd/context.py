@@ -171,6 +171,20 @@ class RegionResult:
         return [tuple(int(v) for v in r[:4]) for r in self.regions]
 
 
+@dataclass
+class RegionTreeResult(RegionResult):
+    """RegionResult with each record's parent blob (include/mdx.h mdx_mask_regions_tree).
+    `regions` holds every kept record, nested or not; `hulls` (want_hulls) holds the hulls of the external
+    records only, hulls[i] belonging to regions[external[i]]."""
+    parent: np.ndarray | None = None    # (len(regions),) int32: a component id, -1 external, -2 unknown
+    external: np.ndarray | None = None  # (num_external,) int32: positions in `regions` of the external records
+
+    @property
+    def external_rectangles(self) -> list:
+        """(x, y, width, height) of each external region: what findContours' RETR_EXTERNAL keeps."""
+        return [tuple(int(v) for v in self.regions[i, :4]) for i in self.external]
+
+
 class Context:
     """One device context (mdx_ctx): workspace sized at creation, one HIP stream."""
 
@@ -409,10 +423,13 @@ class Context:
 
     # -- the motion mask labelled into regions (getMotionContours' recipe: opening, 8-connected blobs, boundingRect)
     def mask_regions(self, mask: np.ndarray, open3: bool = True, min_area: int = 1, max_regions: int | None = None,
-                     want_labels: bool = False, want_mask: bool = False, want_hulls: bool = False) -> "RegionResult":
+                     want_labels: bool = False, want_mask: bool = False, want_hulls: bool = False,
+                     want_parents: bool = False) -> "RegionResult":
         """max_regions (default: every component the frame can hold) caps how many records are returned.
         want_hulls: the records and each one's convex hull in one call (mdx_mask_region_hulls: the label
-        image stays on the device); labels or the mask asked for next to the hulls cost a second call."""
+        image stays on the device); labels or the mask asked for next to the hulls cost a second call.
+        want_parents: a RegionTreeResult -- every record's parent blob and the external records
+        (mdx_mask_regions_tree); with want_hulls the hulls are those of the external records."""
         mask = np.asarray(mask, dtype=np.uint8)
         if mask.ndim != 2 or mask.strides[1] != 1 or mask.strides[0] < mask.shape[1]:
             mask = np.ascontiguousarray(mask)
@@ -427,7 +444,7 @@ class Context:
         mout = np.empty((h, w), np.uint8) if want_mask else None
         nall, nkept = C.c_int(0), C.c_int(0)
         flags = _lib.REGIONS_OPEN3 if open3 else 0
-        if not want_hulls or want_labels or want_mask:
+        if not (want_hulls or want_parents) or want_labels or want_mask:
             self._check(lib().mdx_mask_regions(self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area),
                                                _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
                                                _ptr(labels), _ptr(mout)))
@@ -437,6 +454,21 @@ class Context:
             offsets = np.zeros(max(cap, 0) + 1, np.int32)
             xy = np.empty((maxv, 2), np.int32)
             nv = C.c_int(0)
+        if want_parents:
+            parent = np.zeros(max(cap, 0), np.int32)
+            ext = np.zeros(max(cap, 0), np.int32)
+            next_ = C.c_int(0)
+            self._check(lib().mdx_mask_regions_tree(
+                self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area), _ptr(regs) if cap > 0 else None, cap,
+                C.byref(nall), C.byref(nkept), _ptr(parent), _ptr(ext), C.byref(next_),
+                _ptr(offsets) if want_hulls else None, _ptr(xy) if want_hulls and maxv > 0 else None,
+                maxv if want_hulls else 0, C.byref(nv) if want_hulls else None))
+            n = min(nkept.value, max(cap, 0))
+            if want_hulls:
+                hulls = [xy[offsets[j]:offsets[j + 1]].copy() for j in range(next_.value)]
+            return RegionTreeResult(regs[:n].copy(), nall.value, nkept.value, labels, mout, hulls, parent[:n].copy(),
+                                    ext[:next_.value].copy())
+        if want_hulls:
             self._check(lib().mdx_mask_region_hulls(self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area),
                                                     _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
                                                     _ptr(offsets), _ptr(xy) if maxv > 0 else None, maxv, C.byref(nv)))
@@ -451,6 +483,15 @@ class Context:
         return self._check(lib().mdx_region_hulls_dev(
             self._h, batch, _v(d_labels), w, h, _v(d_regions), max_regions, _v(d_num_kept), _v(d_offsets), _v(d_xy),
             max_vertices, _v(d_num_vertices)))
+
+    def region_parents_dev(self, batch: int, d_labels: int, w: int, h: int, d_regions: int, max_regions: int,
+                           d_num_kept: int, d_parent: int = 0, d_external: int = 0, d_num_external: int = 0) -> int:
+        """Asynchronous on the context stream (include/mdx.h mdx_region_parents_dev); pointers are ints.
+        Takes what mask_regions_dev wrote; region_hulls_dev takes d_external / d_num_external in place of
+        d_regions / d_num_kept for the hulls of the external records only."""
+        return self._check(lib().mdx_region_parents_dev(
+            self._h, batch, _v(d_labels), w, h, _v(d_regions), max_regions, _v(d_num_kept), _v(d_parent), _v(d_external),
+            _v(d_num_external)))
 
     def mask_regions_dev(self, batch: int, d_mask: int, w: int, h: int, stride: int, frame_stride: int,
                          open3: bool = True, min_area: int = 1, d_regions: int = 0, max_regions: int = 0,

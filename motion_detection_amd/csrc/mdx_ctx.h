@@ -129,6 +129,8 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf rgin, rgout;                      // mdx_mask_regions (host entry): the mask, every output
     DevBuf rhscr;                            // mdx_region_hulls_dev: staging slices, vertex counts, staged hulls
     DevBuf rhout;                            // mdx_mask_region_hulls (host entry): counts, records, labels, offsets, xy
+    DevBuf rtscr;                            // mdx_region_parents_dev: the background's parent words and mark bytes
+    DevBuf rtout;                            // mdx_mask_regions_tree (host entry): counts, records, parents, labels, offsets, xy
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
     DevBuf rfull;                            // mdx_ring_push_half: the full-size frame, halved into rin
     DevBuf hsrc, hdst;                       // mdx_resize_half (host entry): the frame and its half

@@ -333,6 +333,19 @@ size_t regions_scratch_bytes(int batch, int w, int h, RegionsScratch* lay = null
 hipError_t launch_mask_regions(hipStream_t s, int batch, const uint8_t* mask, int w, int h, int stride,
                                size_t frame_stride, int open3, int min_area, mdx_region* regions, int max_regions,
                                int32_t* num_all, int32_t* num_kept, int32_t* labels, uint8_t* mask_out, void* scratch);
+// mdx_regions.hip: the parent blob of each region record and the external records.
+// Five launches on s (one when max_regions is 0), no host synchronisation, every pointer a device
+// pointer.  scratch: region_parents_scratch_bytes(batch, w, h) of device memory, a function of those
+// three alone (5 B per pixel: the background's 4-B parent word and a mark byte); nothing in it has
+// to be cleared between calls.  ev, when given, holds seven events: ev[1 .. 5] are recorded behind
+// the tile, merge, roots, flatten and resolve kernels.
+struct RegionTreeScratch {
+    size_t bg, mark;   // byte offsets: the background's parent words, the mark bytes
+};
+size_t region_parents_scratch_bytes(int batch, int w, int h, RegionTreeScratch* lay = nullptr);
+hipError_t launch_region_parents(hipStream_t s, int batch, const int32_t* labels, int w, int h,
+                                 const mdx_region* regions, int max_regions, const int32_t* num_kept, int32_t* parent,
+                                 mdx_region* external, int32_t* num_external, void* scratch, hipEvent_t* ev = nullptr);
 
 // cv::Mat(vector<Point2f>).copyTo(vector<cv::Point>): saturate_cast<int>(float) = cvRound, half to even.
 // The rectangles (mdx_post.cpp clusters_from_roots) and the hulls (host and k_hull) convert with this.

@@ -2,7 +2,8 @@
 // fit (OutlierDetector::fitSubspace), Euclidean clustering (FlowClusterer::clusterEuclidean), flow
 // vectors clustered by distance and angle (getClusters), the kept clusters' convex hulls
 // (showClusterContours), the flow vectors' median / MAD outliers (findOutliers), the pair path's mask labelled
-// into regions (BackgroundSubtractor::getMotionContours' recipe) and those regions' convex hulls.
+// into regions (BackgroundSubtractor::getMotionContours' recipe), those regions' convex hulls and which of
+// them lies inside which (its RETR_EXTERNAL).
 #include "mdx_ctx.h"
 
 #include <cfloat>
@@ -627,5 +628,120 @@ extern "C" int mdx_mask_region_hulls(mdx_ctx* c, const uint8_t* mask, int w, int
     if (num_all) *num_all = cnt[0];
     if (num_kept) *num_kept = cnt[1];
     if (num_vertices) *num_vertices = cnt[2];
+    return MDX_OK;
+}
+
+// Which blob lies inside which: the parent of each region record and the records that
+// findContours' RETR_EXTERNAL keeps.  All of it runs on the device (mdx_regions.hip, the k_tree_* kernels);
+// the call only queues five launches on the context's stream.
+extern "C" int mdx_region_parents_dev(mdx_ctx* c, int batch, const int32_t* d_labels, int w, int h,
+                                      const mdx_region* d_regions, int max_regions, const int32_t* d_num_kept,
+                                      int32_t* d_parent, mdx_region* d_external, int32_t* d_num_external)
+{
+    if (!c) return MDX_EINVAL;
+    const char* who = "mdx_region_parents_dev";
+    if (batch < 1 || w < 1 || h < 1) return set_err(c, MDX_EINVAL, "%s: bad batch or size", who);
+    if ((long long)w * h > (1ll << 30)) return set_err(c, MDX_EINVAL, "%s: more than 2^30 pixels", who);
+    if (max_regions < 0) return set_err(c, MDX_EINVAL, "%s: negative max_regions", who);
+    if (!d_labels || (max_regions > 0 && (!d_regions || !d_num_kept)))
+        return set_err(c, MDX_EINVAL, "%s: a needed pointer is NULL", who);
+    if (d_external && d_regions && max_regions > 0) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_regions), b = reinterpret_cast<uintptr_t>(d_external);
+        const size_t bytes = (size_t)batch * max_regions * sizeof(mdx_region);
+        if (a < b + bytes && b < a + bytes) return set_err(c, MDX_EINVAL, "%s: d_external overlaps d_regions", who);
+    }
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const int chunk = std::min(batch, kRegionsMaxBatch);
+    if (const int rc = ensure(c, c->rtscr, region_parents_scratch_bytes(chunk, w, h)); rc != MDX_OK) return rc;
+    hipStream_t s = c->stream;
+    if (c->input_ev) {      // mdx_input_ready: one-shot
+        hipEvent_t e = c->input_ev;
+        c->input_ev = nullptr;
+        HIP_OR_RETURN(c, hipStreamWaitEvent(s, e, 0));
+    }
+    const size_t N = (size_t)w * h, M = (size_t)max_regions;
+    // (mdx_enable_timing: stages 0 .. 4 the tile, merge, roots, flatten and resolve kernels, 6 the five together)
+    mark(c, 0);
+    hipEvent_t* ev = c->timing && c->cur >= 0 ? c->ev.data() + c->cur * 7 : nullptr;
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+        const int nb = std::min(chunk, batch - b0);
+        HIP_OR_RETURN(c, launch_region_parents(s, nb, d_labels + b0 * N, w, h, d_regions ? d_regions + b0 * M : nullptr,
+                                               max_regions, d_num_kept ? d_num_kept + b0 : nullptr,
+                                               d_parent ? d_parent + b0 * M : nullptr,
+                                               d_external ? d_external + b0 * M : nullptr,
+                                               d_num_external ? d_num_external + b0 : nullptr, c->rtscr.p, ev));
+    }
+    mark(c, 6);
+    return MDX_OK;
+}
+
+extern "C" int mdx_mask_regions_tree(mdx_ctx* c, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                                     mdx_region* regions, int max_regions, int* num_all, int* num_kept, int32_t* parent,
+                                     int32_t* external_index, int* num_external, int32_t* offsets, int32_t* xy,
+                                     int max_vertices, int* num_vertices)
+{
+    if (!c) return MDX_EINVAL;
+    const char* who = "mdx_mask_regions_tree";
+    const size_t fs = (size_t)std::max(h, 0) * (size_t)std::max(stride, 0);
+    if (const int rc = check_regions(c, who, 1, mask, w, h, stride, fs, flags, regions, max_regions, nullptr); rc != MDX_OK)
+        return rc;
+    if (offsets) {
+        if (const int rc = check_region_hulls(c, who, w, offsets, xy, max_vertices); rc != MDX_OK) return rc;
+    } else {
+        max_vertices = 0;
+    }
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    // one output block: counts (num_all, num_kept, num_external, num_vertices), records, external records,
+    // parents, offsets, labels, xy; the labels stay on the device
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t N = (size_t)w * h, M = (size_t)max_regions, o_rec = 256, o_ext = o_rec + up(M * sizeof(mdx_region)),
+                 o_par = o_ext + up(M * sizeof(mdx_region)), o_off = o_par + up(M * 4), o_lab = o_off + up((M + 1) * 4),
+                 o_xy = o_lab + up(N * 4);
+    const size_t in_bytes = (size_t)(h - 1) * stride + w;     // the caller's last row holds w bytes, not stride
+    if (const int rc = ensure_all(c, {{&c->rgin, fs}, {&c->rtout, o_xy + (size_t)max_vertices * 8}}); rc != MDX_OK)
+        return rc;
+    hipStream_t s = c->stream;
+    char* out = c->rtout.as<char>();
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->rgin.p, mask, in_bytes, hipMemcpyHostToDevice, s));
+    int32_t* d_cnt = reinterpret_cast<int32_t*>(out);
+    mdx_region* d_rec = max_regions ? reinterpret_cast<mdx_region*>(out + o_rec) : nullptr;
+    mdx_region* d_ext = max_regions ? reinterpret_cast<mdx_region*>(out + o_ext) : nullptr;
+    int32_t* d_lab = reinterpret_cast<int32_t*>(out + o_lab);
+    if (const int rc = mdx_mask_regions_dev(c, 1, c->rgin.as<uint8_t>(), w, h, stride, fs, flags, min_area, d_rec,
+                                            max_regions, d_cnt, d_cnt + 1, d_lab, nullptr);
+        rc != MDX_OK)
+        return rc;
+    if (const int rc = mdx_region_parents_dev(c, 1, d_lab, w, h, d_rec, max_regions, d_cnt + 1,
+                                              reinterpret_cast<int32_t*>(out + o_par), d_ext, d_cnt + 2);
+        rc != MDX_OK)
+        return rc;
+    if (offsets)
+        if (const int rc = mdx_region_hulls_dev(c, 1, d_lab, w, h, d_ext, max_regions, d_cnt + 2,
+                                                reinterpret_cast<int32_t*>(out + o_off),
+                                                max_vertices ? reinterpret_cast<int32_t*>(out + o_xy) : nullptr,
+                                                max_vertices, d_cnt + 3);
+            rc != MDX_OK)
+            return rc;
+    int32_t cnt[4] = {0, 0, 0, 0};
+    HIP_OR_RETURN(c, hipMemcpyAsync(cnt, d_cnt, offsets ? 16 : 12, hipMemcpyDeviceToHost, s));
+    if (offsets) HIP_OR_RETURN(c, hipMemcpyAsync(offsets, out + o_off, (M + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    const int nrec = std::min(cnt[1], max_regions);
+    if (nrec > 0) {
+        HIP_OR_RETURN(c, hipMemcpy(regions, out + o_rec, (size_t)nrec * sizeof(mdx_region), hipMemcpyDeviceToHost));
+        std::vector<int32_t> par;     // external_index follows from the parents
+        if (!parent) par.resize((size_t)nrec);
+        int32_t* p = parent ? parent : par.data();
+        HIP_OR_RETURN(c, hipMemcpy(p, out + o_par, (size_t)nrec * 4, hipMemcpyDeviceToHost));
+        if (external_index)
+            for (int j = 0, k = 0; j < nrec; j++)
+                if (p[j] == MDX_REGION_NO_PARENT) external_index[k++] = j;
+    }
+    const int nxy = std::min(cnt[3], max_vertices);           // only the vertices that exist come back
+    if (nxy > 0) HIP_OR_RETURN(c, hipMemcpy(xy, out + o_xy, (size_t)nxy * 8, hipMemcpyDeviceToHost));
+    if (num_all) *num_all = cnt[0];
+    if (num_kept) *num_kept = cnt[1];
+    if (num_external) *num_external = cnt[2];
+    if (offsets && num_vertices) *num_vertices = cnt[3];
     return MDX_OK;
 }

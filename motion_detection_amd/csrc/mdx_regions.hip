@@ -30,6 +30,8 @@
 // Reads of L inside a launch that also lowers it (merge, flatten) are agent-scope atomic loads or
 // the value an atomic min returned; a stale value is an older parent, still an ancestor.  Integer
 // atomics only: every output is bit-reproducible.
+// The second half of the file labels the background of the label image the same way and answers which
+// blob lies inside which (the k_tree_* kernels).
 #include "mdx_internal.h"
 
 namespace mdx {
@@ -475,6 +477,229 @@ hipError_t launch_mask_regions(hipStream_t s, int batch, const uint8_t* mask, in
                        stats, maxc, labels);
     hipLaunchKernelGGL(k_regions_out, dim3(batch), dim3(256), 0, s, stats, maxc, nall, w, min_area, regions,
                        max_regions, num_kept);
+    return hipGetLastError();
+}
+
+// ---- which blob lies inside which: the background of the label image, labelled with
+// 4-connectivity by the same scheme -- a parent image B with B[i] <= i for a background pixel
+// (labels[i] < 0) and -1 for a foreground one -- so that the root of a finished background component
+// is its first pixel in raster order.  The component that holds a background pixel of the frame's
+// first or last row or column is the frame background; every other one is a hole, and the pixel
+// above a hole's first pixel belongs to the blob whose hole it is.  A call is five launches on one
+// stream, ordered by the launch boundaries alone, with the same loop discipline as above.
+//   k_tree_tile      one workgroup per 64 x 32 tile: background rows as bit words, the runs of adjacent
+//                    rows joined where a bit sits directly above a bit, union-find in LDS; B (the
+//                    tile's own root per pixel) and the mark byte (2: a tile root, else 0)
+//   k_tree_merge     one thread per pixel on a tile's top row or left column: union straight across
+//                    the border, once per stretch of contact inside one tile edge
+//   k_tree_roots     every tile root walks to its root and stores it.  On a frame-wide background the
+//                    chains run tile root to tile root across the frame; only the tile roots walk them
+//   k_tree_flatten   every other background pixel takes its tile root's root: two loads.  A background
+//                    pixel on the frame edge sets bit 0 of its root's mark (every writer stores 3)
+//   k_tree_resolve   per image, one thread per participating record: its parent, and the external
+//                    records compacted in record order by ballot prefix
+
+// grid (tiles_x * tiles_y, batch), 256 threads
+__global__ __launch_bounds__(256) void k_tree_tile(const int32_t* __restrict__ labels, int w, int h, int tiles_x,
+                                                    int32_t* __restrict__ bg, uint8_t* __restrict__ mark)
+{
+    __shared__ u64 sB[kRgTH + 1];               // background; [0] is the row above the tile: empty
+    __shared__ int sL[kRgTH * kRgTW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * kRgTW, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * kRgTH;
+    const size_t base = (size_t)blockIdx.y * ((size_t)w * h);
+    const int x = x0 + lane;
+    for (int j = 0; j < kRgTH / 4; j++) {
+        const int r = wave + 4 * j, y = y0 + r;
+        const bool b = x < w && y < h && labels[base + (size_t)y * w + x] < 0;
+        const u64 W = __ballot(b);
+        if (lane == 0) sB[r + 1] = W;
+    }
+    if (tid == 0) sB[0] = 0;
+    __syncthreads();
+    // every pixel starts at the first pixel of its row run
+    for (int j = 0; j < kRgTH / 4; j++) {
+        const int r = wave + 4 * j;
+        const u64 W = sB[r + 1];
+        int l = -1;
+        if ((W >> lane) & 1) {
+            const u64 z = ~W & ((1ull << lane) - 1);
+            l = r * kRgTW + (z ? 64 - __clzll((long long)z) : 0);
+        }
+        sL[r * kRgTW + lane] = l;
+    }
+    __syncthreads();
+    // a bit directly above a bit: one union per stretch of contact (the pixel to the left makes the
+    // same union when it and the one above it are background too)
+    for (int j = 0; j < kRgTH / 4; j++) {
+        const int r = wave + 4 * j, p = r * kRgTW + lane;
+        const u64 C = sB[r + 1] & sB[r];
+        if (((C >> lane) & 1) && !(lane > 0 && ((C >> (lane - 1)) & 1))) lds_union(sL, p, p - kRgTW);
+    }
+    __syncthreads();
+    for (int j = 0; j < kRgTH / 4; j++) {
+        const int r = wave + 4 * j, p = r * kRgTW + lane, y = y0 + r;
+        if (x >= w || y >= h) continue;
+        int l = sL[p];
+        uint8_t m = 0;
+        if (l >= 0) {
+            l = lds_find(sL, l);
+            m = l == p ? 2 : 0;
+            l = (y0 + (l >> 6)) * w + x0 + (l & 63);
+        }
+        bg[base + (size_t)y * w + x] = l;
+        mark[base + (size_t)y * w + x] = m;
+    }
+}
+
+// grid (ceil(((tiles_y - 1) * w + (tiles_x - 1) * h) / 256), batch)
+__global__ __launch_bounds__(256) void k_tree_merge(int32_t* __restrict__ bg, int w, int h, int tiles_x, int tiles_y)
+{
+    int32_t* B = bg + (size_t)blockIdx.y * ((size_t)w * h);
+    int t = (int)(blockIdx.x * 256u + threadIdx.x);
+    const int nrow = (tiles_y - 1) * w, ncol = (tiles_x - 1) * h;
+    int x, y, dx, dy, along;   // the pixel, the direction along the border, its place inside the tile edge
+    if (t < nrow) {
+        y = (t / w + 1) * kRgTH, x = t % w;
+        dx = 1, dy = 0, along = x % kRgTW;
+    } else if ((t -= nrow) < ncol) {
+        x = (t / h + 1) * kRgTW, y = t % h;
+        dx = 0, dy = 1, along = y % kRgTH;
+    } else {
+        return;
+    }
+    const int32_t i = y * w + x, j = (y - dx) * w + (x - dy);     // straight across: above, or to the left
+    if (g_load(B + i) < 0 || g_load(B + j) < 0) return;
+    // the pair before this one along the same tile edge makes the same union: each side's two pixels
+    // are neighbours inside one tile
+    if (along > 0 && g_load(B + i - dx - dy * w) >= 0 && g_load(B + j - dx - dy * w) >= 0) return;
+    g_union(B, i, j);
+}
+
+// grid (ceil(N / 256), batch)
+__global__ __launch_bounds__(256) void k_tree_roots(int32_t* __restrict__ bg, int N, const uint8_t* __restrict__ mark)
+{
+    int32_t* B = bg + (size_t)blockIdx.y * (size_t)N;
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= N || !mark[(size_t)blockIdx.y * (size_t)N + i]) return;
+    const int32_t l = g_load(B + i), r = g_find(B, l);
+    if (r != l) __hip_atomic_store(B + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid (ceil(N / 256), batch).  Only the words of pixels that are no tile root are written, and only
+// the words of tile roots are read a second time: they are final since k_tree_roots.
+__global__ __launch_bounds__(256) void k_tree_flatten(int32_t* __restrict__ bg, int w, int h, uint8_t* __restrict__ mark)
+{
+    const int N = w * h;
+    int32_t* B = bg + (size_t)blockIdx.y * (size_t)N;
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= N) return;
+    const int32_t l = B[i];
+    if (l < 0) return;
+    const int32_t r = B[l];
+    if (r != l) B[i] = r;
+    const int x = i % w, y = i / w;
+    if (x == 0 || y == 0 || x == w - 1 || y == h - 1) mark[(size_t)blockIdx.y * (size_t)N + r] = 3;
+}
+
+// The parent of one record (include/mdx.h): MDX_REGION_NO_PARENT, MDX_REGION_PARENT_UNKNOWN or an id.
+// No access outside the frame results from a record.
+__device__ __forceinline__ int32_t tree_parent(const mdx_region& rec, const int32_t* __restrict__ lab,
+                                               const int32_t* __restrict__ B, const uint8_t* __restrict__ mark, int w, int h)
+{
+    const int sx = rec.seed_x, sy = rec.seed_y;
+    if (sx < 0 || sx >= w || sy < 0 || sy >= h || rec.id < 0) return MDX_REGION_PARENT_UNKNOWN;
+    if (lab[sy * w + sx] != rec.id) return MDX_REGION_PARENT_UNKNOWN;
+    if (sy == 0) return MDX_REGION_NO_PARENT;
+    const int32_t above = (sy - 1) * w + sx;
+    if (lab[above] >= 0) return MDX_REGION_PARENT_UNKNOWN;
+    const int32_t root = B[above];                    // the enclosing background's first pixel
+    if (root < 0) return MDX_REGION_PARENT_UNKNOWN;   // cannot happen: B is built from these labels
+    if (mark[root] & 1) return MDX_REGION_NO_PARENT;
+    if (root < w) return MDX_REGION_PARENT_UNKNOWN;   // cannot happen: a hole never touches row 0
+    const int32_t p = lab[root - w];
+    return p >= 0 ? p : MDX_REGION_PARENT_UNKNOWN;
+}
+
+constexpr int kTreeResolveThreads = 1024;
+
+// grid (batch), 1,024 threads
+__global__ __launch_bounds__(kTreeResolveThreads) void k_tree_resolve(
+    const int32_t* __restrict__ labels, const int32_t* __restrict__ bg, const uint8_t* __restrict__ mark, int w, int h,
+    const mdx_region* __restrict__ regions, int max_regions, const int32_t* __restrict__ num_kept,
+    int32_t* __restrict__ parent, mdx_region* __restrict__ external, int32_t* __restrict__ num_external)
+{
+    constexpr int kWaves = kTreeResolveThreads / 64;
+    __shared__ int wc[kWaves];
+    const size_t N = (size_t)w * h, img = blockIdx.x;
+    const int r = max_regions > 0 ? min(max(num_kept[img], 0), max_regions) : 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int c0 = 0; c0 < r; c0 += kTreeResolveThreads) {
+        const int j = c0 + (int)threadIdx.x;
+        mdx_region rec{};
+        bool ext = false;
+        if (j < r) {
+            rec = regions[img * max_regions + j];
+            const int32_t p = tree_parent(rec, labels + img * N, bg + img * N, mark + img * N, w, h);
+            if (parent) parent[img * max_regions + j] = p;
+            ext = p == MDX_REGION_NO_PARENT;
+        }
+        const u64 b = __ballot(ext);
+        __syncthreads();     // the previous round's wc has been read
+        if (lane == 0) wc[wave] = __popcll(b);
+        __syncthreads();
+        int pos = base + __popcll(b & ((1ull << lane) - 1)), total = 0;
+        for (int q = 0; q < kWaves; q++) {
+            if (q < wave) pos += wc[q];
+            total += wc[q];
+        }
+        if (ext && external) external[img * max_regions + pos] = rec;
+        base += total;
+    }
+    if (threadIdx.x == 0 && num_external) num_external[img] = base;
+}
+
+size_t region_parents_scratch_bytes(int batch, int w, int h, RegionTreeScratch* lay)
+{
+    const size_t N = (size_t)w * h;
+    RegionTreeScratch s{};
+    s.bg = 0;
+    s.mark = (N * 4 * batch + 255) / 256 * 256;
+    if (lay) *lay = s;
+    return s.mark + (N * batch + 255) / 256 * 256;
+}
+
+hipError_t launch_region_parents(hipStream_t s, int batch, const int32_t* labels, int w, int h,
+                                 const mdx_region* regions, int max_regions, const int32_t* num_kept, int32_t* parent,
+                                 mdx_region* external, int32_t* num_external, void* scratch, hipEvent_t* ev)
+{
+    if (batch < 1 || batch > kRegionsMaxBatch || w < 1 || h < 1 || (long long)w * h > (1ll << 30))
+        return hipErrorInvalidValue;
+    RegionTreeScratch lay;
+    (void)region_parents_scratch_bytes(batch, w, h, &lay);
+    int32_t* bg = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + lay.bg);
+    uint8_t* mark = reinterpret_cast<uint8_t*>(static_cast<char*>(scratch) + lay.mark);
+    const int N = w * h, nblk = (N + 255) / 256;
+    const int tx = (w + kRgTW - 1) / kRgTW, ty = (h + kRgTH - 1) / kRgTH;
+    const int nborder = (ty - 1) * w + (tx - 1) * h;
+    auto stamp = [&](int i) { return ev ? hipEventRecord(ev[i], s) : hipSuccess; };   // behind kernel i of the five
+    if (max_regions > 0) {    // no record, no question: only num_external is written
+        hipLaunchKernelGGL(k_tree_tile, dim3(tx * ty, batch), dim3(256), 0, s, labels, w, h, tx, bg, mark);
+        (void)stamp(1);
+        if (nborder > 0)
+            hipLaunchKernelGGL(k_tree_merge, dim3((nborder + 255) / 256, batch), dim3(256), 0, s, bg, w, h, tx, ty);
+        (void)stamp(2);
+        hipLaunchKernelGGL(k_tree_roots, dim3(nblk, batch), dim3(256), 0, s, bg, N, mark);
+        (void)stamp(3);
+        hipLaunchKernelGGL(k_tree_flatten, dim3(nblk, batch), dim3(256), 0, s, bg, w, h, mark);
+        (void)stamp(4);
+    } else {
+        for (int i = 1; i <= 4; i++) (void)stamp(i);
+    }
+    hipLaunchKernelGGL(k_tree_resolve, dim3(batch), dim3(kTreeResolveThreads), 0, s, labels, bg, mark, w, h, regions,
+                       max_regions, num_kept, parent, external, num_external);
+    (void)stamp(5);
     return hipGetLastError();
 }
 

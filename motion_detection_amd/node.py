@@ -45,7 +45,11 @@ lines (the reference's loop at :426-429 is commented out, hence the opt-in).  Dr
 (drawContours, the published cluster_image) is out of scope.  With ``region_contours`` (off by default)
 and ``region_min_area`` set, the regions come with the convex hull of each (mdx_mask_region_hulls,
 DESIGN.md §7k: the label image stays on the device) as ``regions.hulls``, logged the same way behind
-the frame's region rectangles.
+the frame's region rectangles.  With ``region_external`` (off by default) and ``region_min_area`` set,
+``regions`` is a RegionTreeResult: every kept record still, plus each one's ``parent`` blob and the
+``external`` ones' indices (findContours' RETR_EXTERNAL, mdx_mask_regions_tree); the logged
+rectangles and, with ``region_contours``, ``regions.hulls`` and the logged contours cover the external
+records only.
 
 With ``use_all_frames=False`` the callback only fills the ring (:262) and the reference's polling caller
 run() (:457-553) does the work: ``run_once()`` is one pass of its body (:464-529) and ``run()`` the loop.
@@ -146,7 +150,10 @@ class MotionDetectionNode:
                        "cluster_contours": False,
                        # the convex hull of every kept mask region (region_min_area set): off by
                        # default; logged with writeContour behind the frame's region rectangles
-                       "region_contours": False}
+                       "region_contours": False,
+                       # findContours' RETR_EXTERNAL (region_min_area set): regions keeps every
+                       # kept record and gains parent / external; what is logged covers the external records only
+                       "region_external": False}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -375,10 +382,12 @@ class MotionDetectionNode:
         if min_area is not None and res.mask is not None:
             # the mask is labelled on the device; what comes back is the records
             # (region_contours: and each record's convex hull; the labels stay on the device)
-            want_hulls = bool(self.params.get("region_contours"))
+            # (region_external: and each record's parent blob; rectangles and hulls of the external ones)
+            want_hulls, external = bool(self.params.get("region_contours")), bool(self.params.get("region_external"))
             res.regions = self.ofc.context.mask_regions(res.mask, open3=bool(self.params.get("region_open", True)),
-                                                        min_area=int(min_area), want_hulls=want_hulls)
-            self._log_rectangles(res.regions.rectangles)
+                                                        min_area=int(min_area), want_hulls=want_hulls,
+                                                        **({"want_parents": True} if external else {}))
+            self._log_rectangles(res.regions.external_rectangles if external else res.regions.rectangles)
             if want_hulls:
                 self._log_contours(res.regions.hulls)
         thr, athr = self.params.get("distance_threshold"), self.params.get("angular_threshold")
