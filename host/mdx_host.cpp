@@ -192,6 +192,12 @@ void MotionDetectionNode::stage_detect_outliers(FrameResult* r)
 void MotionDetectionNode::stage_regions(FrameResult* r)
 {
     if (!p_.regions_on()) return;
+    stage_region_records(r);
+    if (p_.region_outlines) stage_region_outlines(r);
+}
+
+void MotionDetectionNode::stage_region_records(FrameResult* r)
+{
     const int w = r->w, h = r->h;
     // a kept region has at least region_min_area pixels
     static_assert(sizeof(mdx_region) == 8 * sizeof(int32_t), "mdx_region is eight int32");
@@ -246,6 +252,36 @@ void MotionDetectionNode::stage_regions(FrameResult* r)
     r->regions.resize((size_t)8 * n);
     r->region_contour_offsets.resize((size_t)n + 1);
     r->region_contours.resize((size_t)2 * std::min(total, maxv));
+}
+
+// region_outlines: the outer border polyline of every kept (region_external: external) record, a call of its
+// own behind the records'; the points' number is the image's, so a first guess may need a second call
+void MotionDetectionNode::stage_region_outlines(FrameResult* r)
+{
+    const int w = r->w, h = r->h;
+    const int cap = (int)std::min<long long>((long long)w * h / p_.region_min_area, (long long)((w + 1) / 2) * ((h + 1) / 2));
+    const int flags = p_.region_open ? MDX_REGIONS_OPEN3 : 0;
+    std::vector<int32_t> recs((size_t)8 * cap), parent, index;
+    if (p_.region_external) {
+        parent.assign((size_t)cap, 0);
+        index.assign((size_t)cap, 0);
+    }
+    int maxp = std::max(4096, w * h / 4), total = 0, nall = 0, nkept = 0, next = 0;
+    for (;;) {
+        r->region_outline_offsets.assign((size_t)cap + 1, 0);
+        r->region_outlines.resize((size_t)2 * maxp);
+        const int rc = mdx_mask_region_outlines(ctx_, r->mask.data(), w, h, w, flags, p_.region_min_area,
+                                                reinterpret_cast<mdx_region*>(recs.data()), cap, &nall, &nkept,
+                                                p_.region_external ? parent.data() : nullptr,
+                                                p_.region_external ? index.data() : nullptr,
+                                                p_.region_external ? &next : nullptr, r->region_outline_offsets.data(),
+                                                r->region_outlines.data(), maxp, &total);
+        if (rc < 0) throw std::runtime_error(std::string("mdx_mask_region_outlines: ") + mdx_last_error(ctx_));
+        if (total <= maxp) break;
+        maxp = total;
+    }
+    r->region_outline_offsets.resize((size_t)(p_.region_external ? next : std::min(nkept, cap)) + 1);
+    r->region_outlines.resize((size_t)2 * total);
 }
 
 // One clustering entry's call and trim: the result vectors sized for n members and max_kept = n / 6 clusters (a

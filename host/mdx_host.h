@@ -88,6 +88,10 @@ struct Params {
     // record and gains each one's parent blob and the external ones' indices; with region_contours the hulls are
     // those of the external records.  Off by default
     bool region_external = false;
+    // the outer border polyline of every kept mask region, the point list findContours itself returns
+    // (regions_on(); mdx_mask_region_outlines), the label image staying on the device; with
+    // region_external those of the external records, as region_contours.  Off by default
+    bool region_outlines = false;
 
     // Whether each optional stage runs on a processed frame (the conditions documented above, written
     // once: the node's stages and mdx_node's output files both ask here)
@@ -115,6 +119,11 @@ struct StageOutputs {
     // (region_external: hull i belongs to regions[region_external_index[i]])
     std::vector<int32_t> region_contour_offsets;    // regions.size() / 8 + 1 entries (region_external: one per external + 1)
     std::vector<int32_t> region_contours;
+    // region_outlines: region i's outer border is region_outlines[2 * region_outline_offsets[i] ..
+    // 2 * region_outline_offsets[i + 1]), (x, y) pairs in mdx_region_outlines_dev's order (include/mdx.h)
+    // (region_external: outline i belongs to regions[region_external_index[i]])
+    std::vector<int32_t> region_outline_offsets;    // as region_contour_offsets
+    std::vector<int32_t> region_outlines;
     // region_external: each kept region's parent (a component id, MDX_REGION_NO_PARENT, MDX_REGION_PARENT_UNKNOWN)
     // and the positions in `regions` of the external ones
     std::vector<int32_t> region_parent;
@@ -209,6 +218,8 @@ private:
     // the optional stages behind the flow; each returns at once unless its Params::*_on() holds
     void stage_detect_outliers(FrameResult* r);
     void stage_regions(FrameResult* r);
+    void stage_region_records(FrameResult* r);     // the records, (region_external) parents, (region_contours) hulls
+    void stage_region_outlines(FrameResult* r);    // region_outlines
     void stage_vector_clusters(FrameResult* r);
     void stage_subspace(int nimg, FrameResult* r);
     void stage_point_clusters(FrameResult* r);

@@ -24,6 +24,8 @@
 //            [region_contours=0]      (pair path with region_min_area > 0: the convex hull of every kept region)
 //            [region_external=0]      (pair path with region_min_area > 0: findContours' RETR_EXTERNAL -- each kept
 //                                      region's parent blob; rectangles and hulls of the external regions only)
+//            [region_outlines=0]      (pair path with region_min_area > 0: the outer border polyline of every kept
+//                                      region, findContours' own point list; with region_external=1 of the external ones)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -64,6 +66,12 @@
 //                                 are those of the external records, hull i belonging to record
 //                                 external_index[i] of region_parents_<k>.bin, and so are the rectangles and
 //                                 hulls that go to motion.log, numbered among the external records
+//   region_outlines_<k>.bin       the same with region_outlines=1, in region_hulls_<k>.bin's layout: i32 k; i32
+//                                 offsets[k + 1]; i32 xy[offsets[k]][2] -- record i's outer border is
+//                                 xy[offsets[i] .. offsets[i + 1]), in mdx_region_outlines_dev's order
+//                                 (include/mdx.h); with log_contours=1 each outline goes to motion.log too
+//                                 (writeContour), behind the frame's hull lines.  With region_external=1 they
+//                                 are those of the external records, as the hulls
 //   region_parents_<k>.bin        the same with region_external=1: i32 k (the records of regions_<k>.bin); i32
 //                                 parent[k] (a component id, -1: external, -2: unknown; include/mdx.h
 //                                 mdx_region_parents_dev); i32 num_external; i32 external_index[num_external]
@@ -175,6 +183,7 @@ int main(int argc, char** argv)
         p.cluster_contours = geti("cluster_contours", 0) != 0;
         p.region_contours = geti("region_contours", 0) != 0;
         p.region_external = geti("region_external", 0) != 0;
+        p.region_outlines = geti("region_outlines", 0) != 0;
         const bool polling = !p.use_all_frames;
         const int device = geti("device", 0);
         const std::string out = argv[2];
@@ -282,6 +291,13 @@ int main(int argc, char** argv)
                     hb.put(r.region_contours);
                     hb.write(out + "/region_hulls" + sfx);
                     log_hulls(r.region_contour_offsets, r.region_contours);
+                }
+                if (p.region_outlines) {
+                    ByteBuffer ob{(int32_t)(p.region_external ? r.region_external_index.size() : r.regions.size() / 8)};
+                    ob.put(r.region_outline_offsets);
+                    ob.put(r.region_outlines);
+                    ob.write(out + "/region_outlines" + sfx);
+                    log_hulls(r.region_outline_offsets, r.region_outlines);
                 }
             }
             if (!polling && p.detect_outliers_on()) {

@@ -44,7 +44,8 @@ extern "C" {
                                 11: mdx_cluster_hulls (a new entry; mdx_params is unchanged, 80 bytes).
                                    mdx_region_hulls_dev and mdx_mask_region_hulls joined under 11: two
                                    more entries, nothing existing changes.  mdx_region_parents_dev and
-                                   mdx_mask_regions_tree joined under 11 the same way. */
+                                   mdx_mask_regions_tree joined under 11 the same way, and so did
+                                   mdx_region_outlines_dev and mdx_mask_region_outlines. */
 
 /* Return codes */
 #define MDX_OK           0
@@ -613,8 +614,8 @@ int mdx_mask_regions(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int stride
  *   records and never touches memory outside the frame because of one.  Pixels of other regions inside
  *   the rectangle (nested or interleaved blobs) take no part.  A record whose id matches no pixel
  *   gives 0 vertices.  A nested blob's hull is reported like any other (for the external blobs only,
- *   pass mdx_region_parents_dev's d_external and d_num_external), and no contour polylines -- the
- *   hull only.  (A record edited so that its area
+ *   pass mdx_region_parents_dev's d_external and d_num_external).  This entry gives the hull only; the
+ *   contour polyline itself is mdx_region_outlines_dev's (below).  (A record edited so that its area
  *   understates its members may have its hull cut short at min(area, 2*width, 2*height) vertices.)
  *   Vertices, order, start: mdx_cluster_hulls' contract, minus the conversion (members are integers
  *   already).  Extreme points only: collinear boundary points are excluded, one pixel gives 1 vertex,
@@ -731,6 +732,92 @@ int mdx_mask_regions_tree(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int s
                           int32_t* offsets /* [max_regions + 1] or NULL */, int32_t* xy, int max_vertices,
                           int* num_vertices);
 
+/*
+ * Outer border polylines of the mask regions: what getMotionContours' cv::findContours(mask,
+ * contours, CV_RETR_EXTERNAL, CV_CHAIN_APPROX_NONE) itself returns for a blob -- the ordered list of its
+ * border pixels -- for the regions of mdx_mask_regions_dev, on the device.  Restated from the published
+ * border-following algorithm and OpenCV 2.4's behaviour; unpinned against a real build, like the rest of
+ * the recipe.  Like the other region entries it does not clear the frame's outermost ring of pixels.
+ *   Inputs: what mdx_mask_regions_dev wrote -- d_labels, d_regions and d_num_kept.  Per image b the first
+ *   r = min(max(num_kept[b], 0), max_regions) records take part.
+ *   Directions: d = 0..7 are E, NE, N, NW, W, SW, S, SE.  In that order D[d] = (1,0), (1,-1), (0,-1),
+ *   (-1,-1), (-1,0), (-1,1), (0,1), (1,1), with x to the right and y down.  Increasing d runs
+ *   counter-clockwise on the screen.
+ *   Members of record j: the in-frame pixels whose label equals the record's id.  Everything else counts
+ *   as background: other regions, label < 0, and the outside of the frame.
+ *   The tracing rule.
+ *     Start: p0 = (seed_x, seed_y).  Look at p0's neighbours in the order d = 3, 2, 1, 0, 7, 6, 5, 4, which
+ *     runs clockwise from just past W.  The first member found is i1, in direction b0.
+ *     No neighbour: if p0 has no member neighbour, the outline is the single point p0.
+ *     Step: a state is (p, b).  p is a member, and b is the direction from p back to the pixel it was
+ *     entered from.  For the first step, p = p0 and b = b0.  The next pixel is q = p + D[t], where t is the
+ *     first of b+1, b+2, .., b+8 (mod 8) with p + D[t] a member.  The next state is (q, t xor 4).
+ *     Outline: the p of every state from (p0, b0) onward, in order.  It ends with the state whose
+ *     successor is (p0, b0) again.  That state is the step from i1 back to p0, and it is included.
+ *     Shape of the result: p0 comes first and is not repeated at the end.  A pixel on a one-pixel-wide
+ *     strand appears once per pass: a 3 x 1 line gives (0,0), (1,0), (2,0), (1,0).  A 2 x 2 square gives
+ *     (0,0), (0,1), (1,1), (1,0): from the seed it runs down the blob's left side, counter-clockwise on
+ *     the screen.
+ *     Scope: only the outer border is traced.  Holes are never traced, which is RETR_EXTERNAL with
+ *     CHAIN_APPROX_NONE.  A nested blob's outline is reported like any other record's; for the external
+ *     blobs only, pass mdx_region_parents_dev's d_external / d_num_external, as with the hulls.
+ *   Records the entry cannot trust (d_regions is device memory a caller may have edited): a record gives 0
+ *   points if its seed lies outside the frame or its seed pixel does not carry its id (a negative id is
+ *   carried by no pixel: label < 0 is background).  A record's seed may be a member but not the
+ *   component's first pixel; it then gives the cycle of the rule from that seed.  That cycle is well
+ *   defined and finite, though it has no meaning.  (Such a record, and records that share a start or a
+ *   cycle, are traced by one device lane each: exact, but slow.)  No access outside the frame ever
+ *   results from a record.
+ * Outputs:
+ *   d_offsets    [batch][max_regions + 1] outline j's points are xy[b][offsets[b][j] .. offsets[b][j+1]);
+ *                always complete and monotone, entries past r repeat the total
+ *   d_xy         [batch][max_points][2] int32 x, y: the first max_points points of image b, packed in
+ *                record order; nothing past them is written, and nothing at all when max_points is 0
+ *                (d_xy may then be NULL)
+ *   d_num_points [batch] (may be NULL) offsets[b][r]; may exceed max_points
+ * mdx_region_outlines_dev is asynchronous on the context stream and never synchronises with the host: it
+ * chains behind mdx_mask_regions_dev / mdx_region_parents_dev with no round trip, and it honours
+ * mdx_input_ready like the other device entries.  Every pointer is a device pointer.  No workgroup waits
+ * for another.  max_regions == 0 is MDX_OK with offsets[b][0] = 0 and num_points[b] = 0 (one launch).
+ * How: the rule is a bijection on the states (p, b) with p and p + D[b] members, so an outline is one
+ * cycle of a permutation, and list ranking -- pointer jumping over each state's predecessor -- finds every
+ * state's position in it.  Only pixels with a non-member 4-neighbour carry states, at most 7 each.  No
+ * state occurs twice in an outline, so a position is below 7*w*h, the proven bound used here: the call
+ * queues 7 + R launches, R = ceil(log2(7*w*h)) rounds of jumping (24 at 1080p, 26 at 4K), for any batch up
+ * to 65,535 images; a round that follows one in which no state of an image reached its start returns at
+ * once for that image.
+ * Scratch belongs to the context, is a function of (batch, w, h) alone (max_regions takes no part) and
+ * only grows; nothing in it is cleared between calls:
+ *   batch * (61 * w*h + 4 * ceil(w*h / 256) + 260) bytes (+ 765 of alignment)
+ * -- per pixel 7 state words of 8 bytes (the worst case: the ranking runs where the states are, but the
+ * room for them cannot depend on the image), the 4-byte index of its first state and its neighbour mask
+ * byte.  That is 4.0 GB for 32 x 1080p and for 8 x 4K; allocation failure is MDX_ENOMEM.  No allocation
+ * after the first call at a given (batch, w, h).
+ * MDX_EINVAL: a null context; batch < 1; w or h < 1; w*h > 2^28 (state indices are 31-bit: this design's
+ * limit, in place of the hulls' MDX_HULL_MAX_SPAN, which does not apply); max_regions < 0 or
+ * max_points < 0; d_labels or d_offsets NULL; d_regions or d_num_kept NULL with max_regions > 0; d_xy NULL
+ * with max_points > 0.
+ */
+int mdx_region_outlines_dev(mdx_ctx* ctx, int batch, const int32_t* d_labels /* [batch][h][w] */, int w, int h,
+                            const mdx_region* d_regions /* [batch][max_regions] */, int max_regions,
+                            const int32_t* d_num_kept /* [batch] */,
+                            int32_t* d_offsets /* [batch][max_regions + 1] */,
+                            int32_t* d_xy /* [batch][max_points][2] or NULL */, int max_points,
+                            int32_t* d_num_points /* [batch] or NULL */);
+/* mdx_mask_regions and the outlines of its records for one mask in host memory, synchronous: the label
+ * image stays on the device and never crosses PCIe; of xy only the min(offsets[r], max_points) points that
+ * exist are copied back.  regions, num_all, num_kept as mdx_mask_regions.  With parent, external_index and
+ * num_external all NULL every kept record is outlined, outline j belonging to regions[j].  With any of
+ * the three given, they are filled as by mdx_mask_regions_tree and the EXTERNAL records are outlined,
+ * outline i belonging to regions[external_index[i]].  offsets, xy, num_points as above for one image.
+ * Errors: mdx_mask_regions', plus w*h > 2^28, negative max_points, NULL offsets, NULL xy with
+ * max_points > 0. */
+int mdx_mask_region_outlines(mdx_ctx* ctx, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                             mdx_region* regions, int max_regions, int* num_all, int* num_kept,
+                             int32_t* parent /* [max_regions] */, int32_t* external_index /* [max_regions] */,
+                             int* num_external,   /* all three NULL: every kept record */
+                             int32_t* offsets /* [max_regions + 1] */, int32_t* xy, int max_points, int* num_points);
+
 /* Page-locked host memory for frames and outputs (e.g. the node's rgb8 staging buffer and its
  * trajectory outputs): copies between it and the device run as DMA at full link rate, while a
  * pageable buffer is staged by the runtime through bounce buffers.  Any entry taking host pointers
@@ -754,7 +841,8 @@ int mdx_memcpy_d2h(mdx_ctx* ctx, void* dst, const void* src, size_t bytes);
  * together (1, 2 and 5 are empty); mdx_region_hulls_dev too: stage 2 its scan of the records' bounds, 3
  * k_region_hull, 4 the scan that packs xy, 6 the three together (0, 1 and 5 are empty);
  * mdx_region_parents_dev too: stages 0 .. 4 its tile, merge, roots, flatten and resolve kernels, 6 the
- * five together (5 is empty). */
+ * five together (5 is empty); mdx_region_outlines_dev too: stage 0 its set-up kernels, 1 the rounds, 2 the
+ * offsets, 3 the scatter, 6 all of them (4 and 5 are empty). */
 int mdx_enable_timing(mdx_ctx* ctx, int on);
 int mdx_timing_calls(const mdx_ctx* ctx);
 int mdx_stage_ms(mdx_ctx* ctx, int stage, float* ms);

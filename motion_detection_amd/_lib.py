@@ -51,14 +51,14 @@ EXPORTED = [
     "mdx_cluster_euclidean", "mdx_mask_regions_dev", "mdx_mask_regions", "mdx_cluster_vectors",
     "mdx_find_outliers", "mdx_half_size", "mdx_resize_half_dev", "mdx_resize_half", "mdx_ring_push_half",
     "mdx_cluster_hulls", "mdx_region_hulls_dev", "mdx_mask_region_hulls",
-    "mdx_region_parents_dev", "mdx_mask_regions_tree",
+    "mdx_region_parents_dev", "mdx_mask_regions_tree", "mdx_region_outlines_dev", "mdx_mask_region_outlines",
 ]
 ABI_VERSION = 11  # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_plan.h", "mdx_internal.h", "mdx_ctx.h", "mdx_dev.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp",
            "mdx_post.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "mdx_resize.hip", "mdx_hull.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "mdx_resize.hip", "mdx_hull.hip", "mdx_outline.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -284,6 +284,12 @@ def lib() -> C.CDLL:
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), vp, vp,
                                         C.c_int, C.POINTER(C.c_int)]
     L.mdx_mask_regions_tree.restype = C.c_int
+    L.mdx_region_outlines_dev.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.mdx_region_outlines_dev.restype = C.c_int
+    L.mdx_mask_region_outlines.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), vp, vp,
+                                           C.c_int, C.POINTER(C.c_int)]
+    L.mdx_mask_region_outlines.restype = C.c_int
     _lib = L
     return L
 

@@ -163,6 +163,7 @@ class RegionResult:
     num_kept: int               # those with area >= min_area, also when max_regions cut `regions` short
     labels: np.ndarray | None = None    # (h, w) int32: id among all components, -1 background (want_labels)
     mask_out: np.ndarray | None = None  # (h, w) uint8: the opened mask as 0 / 255 (want_mask)
+    outlines: list | None = None        # one (n_j, 2) int32 array per returned record: its outer border (want_outlines, §7m)
     hulls: list | None = None           # one (v_j, 2) int32 array per returned record: its convex hull (want_hulls, §7k)
 
     @property
@@ -174,8 +175,8 @@ class RegionResult:
 @dataclass
 class RegionTreeResult(RegionResult):
     """RegionResult with each record's parent blob (include/mdx.h mdx_mask_regions_tree).
-    `regions` holds every kept record, nested or not; `hulls` (want_hulls) holds the hulls of the external
-    records only, hulls[i] belonging to regions[external[i]]."""
+    `regions` holds every kept record, nested or not; `hulls` (want_hulls) and `outlines` (want_outlines) hold
+    those of the external records only, hulls[i] and outlines[i] belonging to regions[external[i]]."""
     parent: np.ndarray | None = None    # (len(regions),) int32: a component id, -1 external, -2 unknown
     external: np.ndarray | None = None  # (num_external,) int32: positions in `regions` of the external records
 
@@ -424,12 +425,15 @@ class Context:
     # -- the motion mask labelled into regions (getMotionContours' recipe: opening, 8-connected blobs, boundingRect)
     def mask_regions(self, mask: np.ndarray, open3: bool = True, min_area: int = 1, max_regions: int | None = None,
                      want_labels: bool = False, want_mask: bool = False, want_hulls: bool = False,
-                     want_parents: bool = False) -> "RegionResult":
+                     want_parents: bool = False, want_outlines: bool = False) -> "RegionResult":
         """max_regions (default: every component the frame can hold) caps how many records are returned.
         want_hulls: the records and each one's convex hull in one call (mdx_mask_region_hulls: the label
         image stays on the device); labels or the mask asked for next to the hulls cost a second call.
         want_parents: a RegionTreeResult -- every record's parent blob and the external records
-        (mdx_mask_regions_tree); with want_hulls the hulls are those of the external records."""
+        (mdx_mask_regions_tree); with want_hulls the hulls are those of the external records.
+        want_outlines: each record's outer border polyline, findContours' point list (mdx_mask_region_outlines:
+        the label image stays on the device); with want_parents those of the external records.  It is a call
+        of its own next to any of the others, and a second one when the points outgrow the first guess."""
         mask = np.asarray(mask, dtype=np.uint8)
         if mask.ndim != 2 or mask.strides[1] != 1 or mask.strides[0] < mask.shape[1]:
             mask = np.ascontiguousarray(mask)
@@ -444,7 +448,24 @@ class Context:
         mout = np.empty((h, w), np.uint8) if want_mask else None
         nall, nkept = C.c_int(0), C.c_int(0)
         flags = _lib.REGIONS_OPEN3 if open3 else 0
-        if not (want_hulls or want_parents) or want_labels or want_mask:
+        outlines = None
+        if want_outlines:
+            maxp = max(4096, (w * h) // 4)                    # a guess: num_points tells when it was short
+            ooff = np.zeros(max(cap, 0) + 1, np.int32)
+            opar, oext, onext, npts = np.zeros(max(cap, 0), np.int32), np.zeros(max(cap, 0), np.int32), C.c_int(0), C.c_int(0)
+            while True:
+                oxy = np.empty((maxp, 2), np.int32)
+                self._check(lib().mdx_mask_region_outlines(
+                    self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area), _ptr(regs) if cap > 0 else None, cap,
+                    C.byref(nall), C.byref(nkept), _ptr(opar) if want_parents else None,
+                    _ptr(oext) if want_parents else None, C.byref(onext) if want_parents else None, _ptr(ooff), _ptr(oxy),
+                    maxp, C.byref(npts)))
+                if npts.value <= maxp:
+                    break
+                maxp = npts.value
+            nout = onext.value if want_parents else min(nkept.value, max(cap, 0))
+            outlines = [oxy[ooff[j]:ooff[j + 1]].copy() for j in range(nout)]
+        if not (want_hulls or want_parents or want_outlines) or want_labels or want_mask:
             self._check(lib().mdx_mask_regions(self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area),
                                                _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
                                                _ptr(labels), _ptr(mout)))
@@ -466,14 +487,25 @@ class Context:
             n = min(nkept.value, max(cap, 0))
             if want_hulls:
                 hulls = [xy[offsets[j]:offsets[j + 1]].copy() for j in range(next_.value)]
-            return RegionTreeResult(regs[:n].copy(), nall.value, nkept.value, labels, mout, hulls, parent[:n].copy(),
-                                    ext[:next_.value].copy())
+            return RegionTreeResult(regs[:n].copy(), nall.value, nkept.value, labels, mout, outlines, hulls,
+                                    parent[:n].copy(), ext[:next_.value].copy())
         if want_hulls:
             self._check(lib().mdx_mask_region_hulls(self._h, _ptr(mask), w, h, mask.strides[0], flags, int(min_area),
                                                     _ptr(regs) if cap > 0 else None, cap, C.byref(nall), C.byref(nkept),
                                                     _ptr(offsets), _ptr(xy) if maxv > 0 else None, maxv, C.byref(nv)))
             hulls = [xy[offsets[j]:offsets[j + 1]].copy() for j in range(min(nkept.value, max(cap, 0)))]
-        return RegionResult(regs[:min(nkept.value, max(cap, 0))].copy(), nall.value, nkept.value, labels, mout, hulls)
+        return RegionResult(regs[:min(nkept.value, max(cap, 0))].copy(), nall.value, nkept.value, labels, mout,
+                            outlines, hulls)
+
+    def region_outlines_dev(self, batch: int, d_labels: int, w: int, h: int, d_regions: int, max_regions: int,
+                            d_num_kept: int, d_offsets: int, d_xy: int = 0, max_points: int = 0,
+                            d_num_points: int = 0) -> int:
+        """Asynchronous on the context stream (include/mdx.h mdx_region_outlines_dev); pointers are ints.
+        Takes what mask_regions_dev wrote: d_labels, d_regions, d_num_kept -- or region_parents_dev's
+        d_external / d_num_external for the outlines of the external records only."""
+        return self._check(lib().mdx_region_outlines_dev(
+            self._h, batch, _v(d_labels), w, h, _v(d_regions), max_regions, _v(d_num_kept), _v(d_offsets), _v(d_xy),
+            max_points, _v(d_num_points)))
 
     def region_hulls_dev(self, batch: int, d_labels: int, w: int, h: int, d_regions: int, max_regions: int,
                          d_num_kept: int, d_offsets: int, d_xy: int = 0, max_vertices: int = 0,

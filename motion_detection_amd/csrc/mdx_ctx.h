@@ -131,6 +131,8 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf rhout;                            // mdx_mask_region_hulls (host entry): counts, records, labels, offsets, xy
     DevBuf rtscr;                            // mdx_region_parents_dev: the background's parent words and mark bytes
     DevBuf rtout;                            // mdx_mask_regions_tree (host entry): counts, records, parents, labels, offsets, xy
+    DevBuf roscr;                            // mdx_region_outlines_dev: neighbour masks, state indices, state words
+    DevBuf roout;                            // mdx_mask_region_outlines (host entry): counts, records, parents, labels, offsets, xy
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
     DevBuf rfull;                            // mdx_ring_push_half: the full-size frame, halved into rin
     DevBuf hsrc, hdst;                       // mdx_resize_half (host entry): the frame and its half

@@ -1,5 +1,5 @@
 // mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
-// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip, mdx_resize.hip, mdx_hull.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip, mdx_resize.hip, mdx_hull.hip, mdx_outline.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
 // mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
 #pragma once
 
@@ -380,6 +380,23 @@ hipError_t launch_region_hulls(hipStream_t s, int batch, const int32_t* labels, 
                                int max_regions, const int32_t* num_kept, int32_t* offsets, int32_t* xy,
                                int max_vertices, int32_t* num_vertices, void* scratch,
                                hipEvent_t hull_begin = nullptr, hipEvent_t hull_end = nullptr);   // around k_region_hull
+
+// Outer border polylines of the mask regions (mdx_outline.hip): region_outlines_launches
+// launches on s (7 + outline_rounds(w, h) with records and room for points, 1 when max_regions is 0), no
+// host synchronisation, every pointer a device pointer, w * h <= 2^28.  scratch:
+// region_outlines_scratch_bytes(batch, w, h, max_regions) of device memory, a function of (batch, w, h)
+// alone: per pixel 7 state words of 8 B, the 4-B index of its first state and its 1-B neighbour mask, per
+// 256 pixels a 4-B state count, per image the state total and 64 round flags; nothing in it has to be
+// cleared between calls.  ev, when given, holds seven events: ev[1 .. 4] are recorded behind the set-up
+// kernels (mask, blocks, base, pred, starts), the rounds, the offsets and the scatter.
+struct RegionOutlineScratch {
+    size_t words, base, blk, nstates, flags, nbr;   // byte offsets
+};
+size_t region_outlines_scratch_bytes(int batch, int w, int h, int max_regions, RegionOutlineScratch* lay = nullptr);
+int region_outlines_launches(int w, int h, int max_regions, int max_points);
+hipError_t launch_region_outlines(hipStream_t s, int batch, const int32_t* labels, int w, int h, const mdx_region* regions,
+                                  int max_regions, const int32_t* num_kept, int32_t* offsets, int32_t* xy, int max_points,
+                                  int32_t* num_points, void* scratch, hipEvent_t* ev = nullptr);
 
 // Half-size ingest (mdx_resize.hip k_half): `batch` frames of w x h pixels of `channels`
 // (1 or 3) interleaved bytes halved to mdx_half_size(w, h), one launch on s (per kHalfMaxBatch frames).

@@ -437,4 +437,39 @@ inline RowSpan band_built_rows(const RowSpan* rows, int h)
     return RowSpan{std::max(0, 2 * lo1), std::min(h, 2 * hi1)};
 }
 
+// ---- the border-following rule of the region outlines (mdx_outline.hip), written once for
+// the kernels, the host and the CPU test (tests/outline_check.cpp).  Directions d = 0..7 are E, NE, N, NW,
+// W, SW, S, SE (x right, y down; increasing d runs counter-clockwise on the screen); bit d of a pixel's
+// 8-bit mask is set iff its neighbour in direction d is a member.
+MDX_HD inline int outline_dx(int d) { return (d <= 1 || d == 7) - (d >= 3 && d <= 5); }
+MDX_HD inline int outline_dy(int d) { return (d >= 5) - (d >= 1 && d <= 3); }
+// The step: from state (p, b) -- b the direction from p back to the pixel it was entered from -- the next
+// pixel lies in the first direction of b+1, b+2, .., b+8 (mod 8) that holds a member.  -1: no neighbour.
+MDX_HD inline int outline_next_dir(unsigned mask, int b)
+{
+    for (int i = 1; i <= 8; i++)
+        if (mask >> ((b + i) & 7) & 1u) return (b + i) & 7;
+    return -1;
+}
+// Its inverse: the state (p, b) whose step leaves p in direction t has b = the first direction of t-1, t-2,
+// .., t-8 (mod 8) that holds a member (bit t of mask is set, so there is one).  The start rule is the same
+// scan from 3: outline_prev_dir(mask, 4) looks at 3, 2, 1, 0, 7, 6, 5, 4.
+MDX_HD inline int outline_prev_dir(unsigned mask, int t)
+{
+    for (int i = 1; i <= 8; i++)
+        if (mask >> ((t - i) & 7) & 1u) return (t - i) & 7;
+    return -1;
+}
+// Rounds of pointer jumping that rank any outline of a w x h image (w * h <= 2^28): ceil(log2) of the bound
+// on a position in an outline.  A state is a (pixel, direction) pair and the rule is a bijection on the
+// states, so no state occurs twice in an outline; only pixels with a non-member 4-neighbour carry states,
+// at most 7 each: fewer than 7 * w * h positions.
+inline int outline_rounds(int w, int h)
+{
+    const long long bound = 7ll * w * h;
+    int r = 0;
+    while ((1ll << r) < bound) r++;
+    return r;
+}
+
 }  // namespace mdx

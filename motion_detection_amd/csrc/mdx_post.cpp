@@ -745,3 +745,123 @@ extern "C" int mdx_mask_regions_tree(mdx_ctx* c, const uint8_t* mask, int w, int
     if (offsets && num_vertices) *num_vertices = cnt[3];
     return MDX_OK;
 }
+
+// The outer border polyline of each region record: what findContours itself returns for a
+// blob.  All of it runs on the device (mdx_outline.hip); the call only queues launches on the context's
+// stream, their number fixed by (w, h).
+static int check_region_outlines(mdx_ctx* c, const char* who, int w, int h, const void* offsets, const void* xy,
+                                 int max_points)
+{
+    if ((long long)w * h > (1ll << 28)) return set_err(c, MDX_EINVAL, "%s: more than 2^28 pixels", who);
+    if (max_points < 0) return set_err(c, MDX_EINVAL, "%s: negative max_points", who);
+    if (!offsets || (max_points > 0 && !xy)) return set_err(c, MDX_EINVAL, "%s: a needed pointer is NULL", who);
+    return MDX_OK;
+}
+
+extern "C" int mdx_region_outlines_dev(mdx_ctx* c, int batch, const int32_t* d_labels, int w, int h,
+                                       const mdx_region* d_regions, int max_regions, const int32_t* d_num_kept,
+                                       int32_t* d_offsets, int32_t* d_xy, int max_points, int32_t* d_num_points)
+{
+    if (!c) return MDX_EINVAL;
+    const char* who = "mdx_region_outlines_dev";
+    if (batch < 1 || w < 1 || h < 1) return set_err(c, MDX_EINVAL, "%s: bad batch or size", who);
+    if (max_regions < 0) return set_err(c, MDX_EINVAL, "%s: negative max_regions", who);
+    if (const int rc = check_region_outlines(c, who, w, h, d_offsets, d_xy, max_points); rc != MDX_OK) return rc;
+    if (!d_labels || (max_regions > 0 && (!d_regions || !d_num_kept)))
+        return set_err(c, MDX_EINVAL, "%s: a needed pointer is NULL", who);
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    const int chunk = std::min(batch, kRegionsMaxBatch);
+    if (max_regions > 0)                             // without records the one launch touches no scratch
+        if (const int rc = ensure(c, c->roscr, region_outlines_scratch_bytes(chunk, w, h, max_regions)); rc != MDX_OK)
+            return rc;
+    hipStream_t s = c->stream;
+    if (c->input_ev) {      // mdx_input_ready: one-shot
+        hipEvent_t e = c->input_ev;
+        c->input_ev = nullptr;
+        HIP_OR_RETURN(c, hipStreamWaitEvent(s, e, 0));
+    }
+    const size_t N = (size_t)w * h, M = (size_t)max_regions;
+    // (mdx_enable_timing: stage 0 the set-up kernels, 1 the rounds, 2 the offsets, 3 the scatter, 6 all of them)
+    mark(c, 0);
+    hipEvent_t* ev = c->timing && c->cur >= 0 ? c->ev.data() + c->cur * 7 : nullptr;
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+        const int nb = std::min(chunk, batch - b0);
+        HIP_OR_RETURN(c, launch_region_outlines(s, nb, d_labels + b0 * N, w, h, d_regions ? d_regions + b0 * M : nullptr,
+                                                max_regions, d_num_kept ? d_num_kept + b0 : nullptr,
+                                                d_offsets + b0 * (M + 1),
+                                                d_xy ? d_xy + (size_t)b0 * max_points * 2 : nullptr, max_points,
+                                                d_num_points ? d_num_points + b0 : nullptr, c->roscr.p, ev));
+    }
+    for (int i = 5; i <= 6; i++) mark(c, i);
+    return MDX_OK;
+}
+
+extern "C" int mdx_mask_region_outlines(mdx_ctx* c, const uint8_t* mask, int w, int h, int stride, int flags, int min_area,
+                                        mdx_region* regions, int max_regions, int* num_all, int* num_kept,
+                                        int32_t* parent, int32_t* external_index, int* num_external, int32_t* offsets,
+                                        int32_t* xy, int max_points, int* num_points)
+{
+    if (!c) return MDX_EINVAL;
+    const char* who = "mdx_mask_region_outlines";
+    const size_t fs = (size_t)std::max(h, 0) * (size_t)std::max(stride, 0);
+    if (const int rc = check_regions(c, who, 1, mask, w, h, stride, fs, flags, regions, max_regions, nullptr); rc != MDX_OK)
+        return rc;
+    if (const int rc = check_region_outlines(c, who, w, h, offsets, xy, max_points); rc != MDX_OK) return rc;
+    const bool tree = parent || external_index || num_external;    // outline the external records only
+    HIP_OR_RETURN(c, hipSetDevice(c->device));
+    // one output block: counts (num_all, num_kept, num_external, num_points), records, external records,
+    // parents, offsets, labels, xy; the labels stay on the device
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t N = (size_t)w * h, M = (size_t)max_regions, o_rec = 256, o_ext = o_rec + up(M * sizeof(mdx_region)),
+                 o_par = o_ext + up(M * sizeof(mdx_region)), o_off = o_par + up(M * 4), o_lab = o_off + up((M + 1) * 4),
+                 o_xy = o_lab + up(N * 4);
+    const size_t in_bytes = (size_t)(h - 1) * stride + w;     // the caller's last row holds w bytes, not stride
+    if (const int rc = ensure_all(c, {{&c->rgin, fs}, {&c->roout, o_xy + (size_t)max_points * 8}}); rc != MDX_OK)
+        return rc;
+    hipStream_t s = c->stream;
+    char* out = c->roout.as<char>();
+    HIP_OR_RETURN(c, hipMemcpyAsync(c->rgin.p, mask, in_bytes, hipMemcpyHostToDevice, s));
+    int32_t* d_cnt = reinterpret_cast<int32_t*>(out);
+    mdx_region* d_rec = max_regions ? reinterpret_cast<mdx_region*>(out + o_rec) : nullptr;
+    mdx_region* d_ext = max_regions ? reinterpret_cast<mdx_region*>(out + o_ext) : nullptr;
+    int32_t* d_lab = reinterpret_cast<int32_t*>(out + o_lab);
+    if (const int rc = mdx_mask_regions_dev(c, 1, c->rgin.as<uint8_t>(), w, h, stride, fs, flags, min_area, d_rec,
+                                            max_regions, d_cnt, d_cnt + 1, d_lab, nullptr);
+        rc != MDX_OK)
+        return rc;
+    if (tree)
+        if (const int rc = mdx_region_parents_dev(c, 1, d_lab, w, h, d_rec, max_regions, d_cnt + 1,
+                                                  reinterpret_cast<int32_t*>(out + o_par), d_ext, d_cnt + 2);
+            rc != MDX_OK)
+            return rc;
+    if (const int rc = mdx_region_outlines_dev(c, 1, d_lab, w, h, tree ? d_ext : d_rec, max_regions,
+                                               tree ? d_cnt + 2 : d_cnt + 1, reinterpret_cast<int32_t*>(out + o_off),
+                                               max_points ? reinterpret_cast<int32_t*>(out + o_xy) : nullptr, max_points,
+                                               d_cnt + 3);
+        rc != MDX_OK)
+        return rc;
+    int32_t cnt[4] = {0, 0, 0, 0};
+    HIP_OR_RETURN(c, hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipMemcpyAsync(offsets, out + o_off, (M + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_RETURN(c, hipStreamSynchronize(s));
+    const int nrec = std::min(cnt[1], max_regions);
+    if (nrec > 0) {
+        HIP_OR_RETURN(c, hipMemcpy(regions, out + o_rec, (size_t)nrec * sizeof(mdx_region), hipMemcpyDeviceToHost));
+        if (tree) {
+            std::vector<int32_t> par;     // external_index follows from the parents
+            if (!parent) par.resize((size_t)nrec);
+            int32_t* p = parent ? parent : par.data();
+            HIP_OR_RETURN(c, hipMemcpy(p, out + o_par, (size_t)nrec * 4, hipMemcpyDeviceToHost));
+            if (external_index)
+                for (int j = 0, k = 0; j < nrec; j++)
+                    if (p[j] == MDX_REGION_NO_PARENT) external_index[k++] = j;
+        }
+    }
+    const int nxy = std::min(cnt[3], max_points);             // only the points that exist come back
+    if (nxy > 0) HIP_OR_RETURN(c, hipMemcpy(xy, out + o_xy, (size_t)nxy * 8, hipMemcpyDeviceToHost));
+    if (num_all) *num_all = cnt[0];
+    if (num_kept) *num_kept = cnt[1];
+    if (tree && num_external) *num_external = cnt[2];
+    if (num_points) *num_points = cnt[3];
+    return MDX_OK;
+}

@@ -49,7 +49,10 @@ the frame's region rectangles.  With ``region_external`` (off by default) and ``
 ``regions`` is a RegionTreeResult: every kept record still, plus each one's ``parent`` blob and the
 ``external`` ones' indices (findContours' RETR_EXTERNAL, mdx_mask_regions_tree); the logged
 rectangles and, with ``region_contours``, ``regions.hulls`` and the logged contours cover the external
-records only.
+records only.  With ``region_outlines`` (off by default) and ``region_min_area`` set, the regions come with the
+outer border polyline of each -- the point list findContours itself returns (mdx_mask_region_outlines,
+DESIGN.md §7m) -- as ``regions.outlines``, each logged with writeContour behind the frame's hull lines; it
+combines with ``region_external`` as ``region_contours`` does.
 
 With ``use_all_frames=False`` the callback only fills the ring (:262) and the reference's polling caller
 run() (:457-553) does the work: ``run_once()`` is one pass of its body (:464-529) and ``run()`` the loop.
@@ -153,7 +156,10 @@ class MotionDetectionNode:
                        "region_contours": False,
                        # findContours' RETR_EXTERNAL (region_min_area set): regions keeps every
                        # kept record and gains parent / external; what is logged covers the external records only
-                       "region_external": False}
+                       "region_external": False,
+                       # the outer border polyline of every kept mask region, findContours' own point list
+                       # (region_min_area set): off by default; logged with writeContour behind the hulls
+                       "region_outlines": False}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -383,13 +389,18 @@ class MotionDetectionNode:
             # the mask is labelled on the device; what comes back is the records
             # (region_contours: and each record's convex hull; the labels stay on the device)
             # (region_external: and each record's parent blob; rectangles and hulls of the external ones)
+            # (region_outlines: and each record's outer border polyline; of the external ones likewise)
             want_hulls, external = bool(self.params.get("region_contours")), bool(self.params.get("region_external"))
+            want_outlines = bool(self.params.get("region_outlines"))
             res.regions = self.ofc.context.mask_regions(res.mask, open3=bool(self.params.get("region_open", True)),
                                                         min_area=int(min_area), want_hulls=want_hulls,
-                                                        **({"want_parents": True} if external else {}))
+                                                        **({"want_parents": True} if external else {}),
+                                                        **({"want_outlines": True} if want_outlines else {}))
             self._log_rectangles(res.regions.external_rectangles if external else res.regions.rectangles)
             if want_hulls:
                 self._log_contours(res.regions.hulls)
+            if want_outlines:
+                self._log_contours(res.regions.outlines)
         thr, athr = self.params.get("distance_threshold"), self.params.get("angular_threshold")
         if self.params.get("detect_outliers") and thr is not None and athr is not None:
             self.detect_outliers(image1.shape[0], image1.shape[1], res, float(thr), float(athr))
