@@ -101,6 +101,7 @@ bool MotionDetectionNode::image_callback(const Image& msg, FrameResult* out)
                                                                    MDX_FMT_RGB8, (int)raw_images_.size());
         if (rc < 0) throw std::runtime_error(std::string("mdx_ring_push: ") + mdx_last_error(ctx_));
     }
+    if (p_.background_subtraction) update_background(p_.ring_on() ? last_rgb_ : to_rgb8(msg));
     bool done = false;
     if (p_.use_all_frames && image_received_) {                  // :262
         set_flow_params();
@@ -116,6 +117,64 @@ bool MotionDetectionNode::image_callback(const Image& msg, FrameResult* out)
     }
     global_frame_count_++;
     return done;
+}
+
+// background_subtraction: the frame updates the mixture model (BackgroundSubtractor::getMotionContours,
+// background_subtractor.cpp:27); with region_min_area > 0 its mask is opened and labelled and the external
+// records picked (:31-35), all on the device: the frame goes up, the records come back.
+void MotionDetectionNode::update_background(const Image& rgb)
+{
+    const int w = (int)rgb.width, h = (int)rgb.height;
+    auto check = [&](int rc, const char* what) {
+        if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mdx_last_error(ctx_));
+    };
+    const size_t n = (size_t)w * h, cap = (size_t)((w + 1) / 2) * ((h + 1) / 2);
+    if (!bg_ || w != bg_w_ || h != bg_h_) {          // a new frame size starts a new model
+        check(mdx_sync(ctx_), "mdx_sync");
+        if (bg_) check(mdx_bg_destroy(ctx_, bg_), "mdx_bg_destroy");
+        bg_ = nullptr;
+        for (void*& d : bg_dev_) {
+            if (d) mdx_dev_free(ctx_, d);
+            d = nullptr;
+        }
+        check(mdx_bg_create(ctx_, 1, w, h, 3, nullptr, &bg_), "mdx_bg_create");
+        const size_t bytes[6] = {n * 3, n, n * 4, cap * sizeof(mdx_region), cap * sizeof(mdx_region), 16};
+        for (int i = 0; i < 6; i++)
+            if (!(bg_dev_[i] = mdx_dev_alloc(ctx_, bytes[i]))) throw std::runtime_error("mdx_dev_alloc failed");
+        bg_w_ = w, bg_h_ = h;
+    }
+    uint8_t* d_frame = static_cast<uint8_t*>(bg_dev_[0]);
+    uint8_t* d_mask = static_cast<uint8_t*>(bg_dev_[1]);
+    if (rgb.step == 3u * rgb.width) {
+        check(mdx_memcpy_h2d(ctx_, d_frame, rgb.data.data(), n * 3), "mdx_memcpy_h2d");
+    } else {
+        for (int y = 0; y < h; y++)
+            check(mdx_memcpy_h2d(ctx_, d_frame + (size_t)y * w * 3, rgb.data.data() + (size_t)y * rgb.step, (size_t)w * 3),
+                  "mdx_memcpy_h2d");
+    }
+    check(mdx_bg_apply_dev(ctx_, bg_, 1, d_frame, w * 3, n * 3, 0, -1.0, d_mask), "mdx_bg_apply_dev");
+    bg_frame_ = global_frame_count_;
+    bg_rects_.clear();
+    if (p_.region_min_area <= 0) return;
+    int32_t* d_labels = static_cast<int32_t*>(bg_dev_[2]);
+    mdx_region* d_rec = static_cast<mdx_region*>(bg_dev_[3]);
+    mdx_region* d_ext = static_cast<mdx_region*>(bg_dev_[4]);
+    int32_t* d_cnt = static_cast<int32_t*>(bg_dev_[5]);     // num_all, num_kept, num_external
+    check(mdx_mask_regions_dev(ctx_, 1, d_mask, w, h, w, n, MDX_REGIONS_OPEN3, p_.region_min_area, d_rec, (int)cap, d_cnt,
+                               d_cnt + 1, d_labels, nullptr),
+          "mdx_mask_regions_dev");
+    check(mdx_region_parents_dev(ctx_, 1, d_labels, w, h, d_rec, (int)cap, d_cnt + 1, nullptr, d_ext, d_cnt + 2),
+          "mdx_region_parents_dev");
+    int32_t cnt[3] = {0, 0, 0};
+    check(mdx_memcpy_d2h(ctx_, cnt, d_cnt, sizeof cnt), "mdx_memcpy_d2h");
+    check(mdx_sync(ctx_), "mdx_sync");
+    const size_t next = std::min((size_t)std::max(cnt[2], 0), cap);
+    std::vector<mdx_region> ext(next);
+    if (next) {
+        check(mdx_memcpy_d2h(ctx_, ext.data(), d_ext, next * sizeof(mdx_region)), "mdx_memcpy_d2h");
+        check(mdx_sync(ctx_), "mdx_sync");
+    }
+    for (const mdx_region& e : ext) bg_rects_.insert(bg_rects_.end(), {e.x, e.y, e.width, e.height});
 }
 
 // pixel_step and min_vector_size are re-read on every frame (:264) and every pass of run()

@@ -92,6 +92,11 @@ struct Params {
     // (regions_on(); mdx_mask_region_outlines), the label image staying on the device; with
     // region_external those of the external records, as region_contours.  Off by default
     bool region_outlines = false;
+    // background subtraction (the reference's BackgroundSubtractor bs_, motion_detection_node.h:93; mdx_bg_*,
+    // DESIGN.md §7n): every frame that enters the ring also updates a mixture model of its size on the device;
+    // with region_min_area > 0 the frame's external regions of the model's opened mask are kept
+    // (background_regions(); mdx_node: motion_bg.log).  Whichever path runs.  Off by default
+    bool background_subtraction = false;
 
     // Whether each optional stage runs on a processed frame (the conditions documented above, written
     // once: the node's stages and mdx_node's output files both ask here)
@@ -204,6 +209,11 @@ public:
     // the reference's spinning loop does.
     bool run_once(FrameResult* out);
 
+    // background_subtraction: the frame (global_frame_count() at its callback) the model last took, -1 before
+    // the first; with region_min_area > 0 that frame's external regions, x, y, width, height each
+    long background_frame() const { return bg_frame_; }
+    const std::vector<int32_t>& background_regions() const { return bg_rects_; }
+
     Params& params() { return p_; }
     long global_frame_count() const { return global_frame_count_; }
     int trajectory_size() const { return p_.egomotion ? 2 * p_.num_motions + 1 : 2; }   // :241-245
@@ -227,6 +237,7 @@ private:
     void cluster_hulls(const std::vector<float>& points, FrameResult* r);
     template <class Entry> void cluster_and_trim(const char* name, int n, FrameResult* r, Entry entry);
     void publish(const std::string& topic, const Image& img) const;
+    void update_background(const Image& rgb);
 
     Params p_;
     Publisher pub_;
@@ -237,6 +248,12 @@ private:
     int ring_w_ = 0, ring_h_ = 0;             // the size the newest frame has in the device ring (halved or not)
     bool image_received_ = false;
     long global_frame_count_ = 0;
+    // background_subtraction: the model, its frame size, and the device buffers of its chain (freed with ctx_)
+    mdx_bg* bg_ = nullptr;
+    int bg_w_ = 0, bg_h_ = 0;
+    void* bg_dev_[6] = {};                    // frame, mask, labels, records, external records, counts
+    long bg_frame_ = -1;
+    std::vector<int32_t> bg_rects_;
 };
 
 // RGB8 renderings the node publishes, both under topic names of this build's own (kTopicMask,

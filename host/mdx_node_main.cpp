@@ -26,6 +26,9 @@
 //                                      region's parent blob; rectangles and hulls of the external regions only)
 //            [region_outlines=0]      (pair path with region_min_area > 0: the outer border polyline of every kept
 //                                      region, findContours' own point list; with region_external=1 of the external ones)
+//            [background_subtraction=0] (every frame that enters the ring also updates a MOG2 background model on the
+//                                      device; with region_min_area > 0 the external regions of its opened mask go to
+//                                      motion_bg.log, one MotionLogger::writeBoundingBox line each)
 //
 // frames.bin: "MDXF", u32 count, then per frame u32 height, u32 width, u32 step, u32 len, the
 // encoding (len bytes) and step * height data bytes (a sensor_msgs/Image each).
@@ -184,6 +187,7 @@ int main(int argc, char** argv)
         p.region_contours = geti("region_contours", 0) != 0;
         p.region_external = geti("region_external", 0) != 0;
         p.region_outlines = geti("region_outlines", 0) != 0;
+        p.background_subtraction = geti("background_subtraction", 0) != 0;
         const bool polling = !p.use_all_frames;
         const int device = geti("device", 0);
         const std::string out = argv[2];
@@ -215,13 +219,26 @@ int main(int argc, char** argv)
                 ml->write_contour(std::vector<int>(xy.begin() + 2 * offsets[i], xy.begin() + 2 * offsets[i + 1]),
                                   (int)node.global_frame_count() - 1, (int)i);
         };
+        // background_subtraction=1 with region_min_area > 0: every frame that entered the ring, processed or not
+        std::unique_ptr<MotionLogger> bgl;
+        if (p.background_subtraction && p.region_min_area > 0) bgl.reset(new MotionLogger(out + "/motion_bg.log"));
+        auto log_background = [&]() {
+            const long frame = node.global_frame_count() - 1;
+            if (!bgl || node.background_frame() != frame) return;
+            const std::vector<int32_t>& q = node.background_regions();
+            for (size_t i = 0; i + 3 < q.size(); i += 4)
+                bgl->write_bounding_box(q[i], q[i + 1], q[i + 2], q[i + 3], (int)frame, (int)(i / 4));
+        };
         for (size_t fi = 0; fi < frames.size(); fi++) {
             FrameResult r;
             if (polling) {
                 node.image_callback(frames[fi], nullptr);
+                log_background();
                 if (!node.run_once(&r)) continue;
-            } else if (!node.image_callback(frames[fi], &r)) {
-                continue;
+            } else {
+                const bool done = node.image_callback(frames[fi], &r);
+                log_background();
+                if (!done) continue;
             }
             const bool live = p.live_path || polling;
             const std::string sfx = "_" + std::to_string(k) + ".bin";

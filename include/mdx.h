@@ -818,6 +818,120 @@ int mdx_mask_region_outlines(mdx_ctx* ctx, const uint8_t* mask, int w, int h, in
                              int* num_external,   /* all three NULL: every kept record */
                              int32_t* offsets /* [max_regions + 1] */, int32_t* xy, int max_points, int* num_points);
 
+/*
+ * Background subtraction (ABI 11): the head of the reference's
+ * BackgroundSubtractor::getMotionContours (common/src/background_subtractor.cpp:27-28) --
+ * cv::BackgroundSubtractorMOG2::operator() and getBackgroundImage as OpenCV 2.4's bgfg_gaussmix2.cpp
+ * (MOG2Invoker, detectShadowGMM) computes them.  Restated from the published source, unpinned against a
+ * real build.  A model is a per-pixel mixture of up to nmixtures Gaussians, kept on the device; the mask
+ * it writes (0 background, shadow_value shadow, 255 foreground) is a valid d_mask for mdx_mask_regions_dev,
+ * which treats any non-zero byte as foreground, so frame -> mask -> opening -> external outlines runs with
+ * no round trip.
+ *
+ * Arithmetic: IEEE binary32, no contraction, operations in the order written, division correctly rounded.
+ * Per call: nframes++; learning_rate < 0: alphaT = (float)(1.0 / min(2 * nframes, history)) (in double);
+ * learning_rate >= 0 and nframes > 1: alphaT = (float)learning_rate; on frame 1 alphaT =
+ * (float)(1.0 / min(2, history)) whatever the rate.  alpha1 = 1.f - alphaT; prune = -alphaT * ct.
+ * Per pixel, data[c] = (float)byte, state modes and per mode m weight[m], variance[m], mean[m][c]:
+ *   1  n = n0 = modes, fits = background = false, total = 0.f
+ *   2  for (m = 0; m < n; m++)                 -- n is re-read and may shrink inside the loop
+ *        w = alpha1 * weight[m] + prune; swaps = 0
+ *        if (!fits)  var = variance[m]; d[c] = mean[m][c] - data[c]; dist2 = d0*d0 + d1*d1 + d2*d2 (left to
+ *                    right; one channel: d0*d0)
+ *                    if (total < TB && dist2 < Tb * var) background = true
+ *                    if (dist2 < Tg * var)  fits = true; w += alphaT; k = alphaT / w; mean[m][c] -= k * d[c];
+ *                        vn = var + k * (dist2 - var); vn = vn > var_min ? vn : var_min;
+ *                        vn = vn < var_max ? vn : var_max; variance[m] = vn;
+ *                        for (i = m; i > 0; i--) { if (w < weight[i-1]) break; swaps++; swap modes i, i-1 }
+ *        if (w < -prune) { w = 0.f; n--; }
+ *        weight[m - swaps] = w; total += w
+ *   3  total = 1.f / total; for (m < n) weight[m] *= total; n = n0 (a pruned mode stays, with weight 0)
+ *   4  if (!fits)  m = (n == nmixtures) ? nmixtures - 1 : n++
+ *                  n == 1: weight[m] = 1.f; else weight[m] = alphaT and weight[i] *= alpha1 for i < n - 1
+ *                  mean[m][c] = data[c]; variance[m] = var_init
+ *                  for (i = n - 1; i > 0; i--) { if (alphaT < weight[i-1]) break; swap modes i, i-1 }
+ *   5  modes = n; mask = background ? 0 : (detect_shadows && shadow()) ? shadow_value : 255
+ * shadow(), on the updated state, tw = 0.f, for (m < n):
+ *        num = sum_c data[c] * mean[m][c], den = sum_c mean[m][c]^2 (both from 0.f, in channel order)
+ *        if (den == 0) return false
+ *        if (num <= den && num >= tau * den)  a = num / den; s = sum_c (a * mean[m][c] - data[c])^2 from 0.f;
+ *                                             if (s < Tb * variance[m] * a * a) return true   (left to right)
+ *        tw += weight[m]; if (tw > TB) return false
+ *      return false
+ * Background image, per pixel: for (m < modes) { acc[c] += weight[m] * mean[m][c] (from 0.f); tot += weight[m];
+ * if (tot > TB) break; }  acc[c] *= (1.f / tot); the byte is acc[c] clamped to [0, 255] (a NaN gives 0) and
+ * rounded half to even; modes == 0 gives 0.  (2.4 asserts three channels there; one channel follows the same
+ * rule and is an extension.)
+ * A NaN in the state (learning_rate 1 makes them: step 3 multiplies a weight 0 by 1 / 0) is held as
+ * 0x7fc00000: IEEE leaves a generated NaN's sign and payload open.  Nothing else depends on either.
+ */
+#define MDX_BG_MAX_MIXTURES 8
+#define MDX_BG_MAX_FRAMES_PER_LAUNCH 32   /* mdx_bg_apply_dev splits a longer run of frames into launches */
+typedef struct mdx_bg_params {   /* 48 bytes */
+    int32_t history;             /* 500 */
+    int32_t nmixtures;           /* 5; 1 .. MDX_BG_MAX_MIXTURES */
+    float var_threshold;         /* Tb 16 */
+    float var_threshold_gen;     /* Tg 9 */
+    float background_ratio;      /* TB 0.9f; (0, 1] */
+    float var_init;              /* 15 */
+    float var_min;               /* 4 */
+    float var_max;               /* 75 */
+    float ct;                    /* 0.05f */
+    int32_t detect_shadows;      /* 1 */
+    int32_t shadow_value;        /* 127; 0 .. 255 */
+    float tau;                   /* 0.5f; [0, 1] */
+} mdx_bg_params;
+typedef struct mdx_bg mdx_bg;
+/* OpenCV 2.4's default constructor, which the reference uses (background_subtractor.h:23). */
+void mdx_bg_default_params(mdx_bg_params* p);
+size_t mdx_bg_params_size(void);
+/* `streams` independent models of w x h pixels of `channels` (1 or 3) interleaved bytes; params NULL: the
+ * defaults.  The model belongs to the context: mdx_bg_destroy frees it, and mdx_destroy frees the models
+ * that never were.  Device memory: streams * w * h * (1 + 4 * nmixtures * (2 + channels)) bytes (101 B per
+ * pixel at the defaults and 3 channels); MDX_ENOMEM when it does not fit.  A fresh model has no modes and has
+ * seen no frame.
+ * MDX_EINVAL (and *out untouched): a null context, params-with-null out; streams < 1 (or > 65,535); w or h < 1;
+ * channels not 1 or 3; nmixtures outside [1, 8]; history < 1; a threshold, variance or ct that is negative or
+ * not finite; var_min > var_max; background_ratio outside (0, 1]; tau outside [0, 1]; shadow_value outside
+ * [0, 255]. */
+int mdx_bg_create(mdx_ctx* ctx, int streams, int w, int h, int channels, const mdx_bg_params* params, mdx_bg** out);
+int mdx_bg_destroy(mdx_ctx* ctx, mdx_bg* bg);
+/* modes = 0 everywhere and nframes = 0 (queued on the context's stream). */
+int mdx_bg_reset(mdx_ctx* ctx, mdx_bg* bg);
+/* Frames the model has seen (every stream of a model sees the same number); negative on error. */
+int mdx_bg_frames(mdx_ctx* ctx, mdx_bg* bg);
+/* T consecutive frames of every stream, in one launch per 32 frames: a pixel's mixture is loaded once, carried
+ * in registers through the launch's frames, and stored once, so replaying a recording pays the state's traffic
+ * once per launch; T = 1 is the live case.  The outcome equals T calls with one frame each, bit for bit.
+ * d_frames: stream s, frame t, row y at d_frames + s * stream_stride + t * frame_stride + y * stride, w *
+ * channels bytes each, any alignment.  d_fgmask (may be NULL) [streams][T][h][w], packed; with T = 1 it is a
+ * d_mask for mdx_mask_regions_dev with batch = streams, stride = w, frame_stride = w * h.
+ * Asynchronous on the context's stream, never synchronises with the host, honours mdx_input_ready.
+ * MDX_EHIP (a launch failed): with T > 32 the launches queued before the failing one stand -- the model and
+ * mdx_bg_frames have advanced by a multiple of 32 frames, which mdx_bg_frames tells.
+ * MDX_EINVAL (mask and model untouched): a null context, model or d_frames; a model of another context; T < 1;
+ * stride < w * channels; with T > 1 a frame_stride below (h - 1) * stride + w * channels; with streams > 1 a
+ * stream_stride below (T - 1) * frame_stride + (h - 1) * stride + w * channels; a learning_rate that is not
+ * finite. */
+int mdx_bg_apply_dev(mdx_ctx* ctx, mdx_bg* bg, int T, const uint8_t* d_frames, int stride, size_t frame_stride,
+                     size_t stream_stride, double learning_rate, uint8_t* d_fgmask);
+/* The background image of every stream, d_out [streams][h][w][channels]; asynchronous like the above. */
+int mdx_bg_image_dev(mdx_ctx* ctx, mdx_bg* bg, uint8_t* d_out);
+/* Synchronous conveniences for a model of one stream and frames in host memory (MDX_EINVAL for more
+ * streams); fgmask [h][w] may be NULL, out is [h][w][channels]. */
+int mdx_bg_apply(mdx_ctx* ctx, mdx_bg* bg, const uint8_t* frame, int stride, double learning_rate, uint8_t* fgmask);
+int mdx_bg_image(mdx_ctx* ctx, mdx_bg* bg, uint8_t* out);
+/* One stream's model in a canonical host layout, to checkpoint it or to start from a crafted state;
+ * synchronous.  weight [h][w][nmixtures], variance [h][w][nmixtures], mean [h][w][nmixtures][channels] floats,
+ * modes [h][w] bytes, nframes the model's frame count (one per model: set_state of any stream sets it).  Any
+ * output of get_state may be NULL; entries of modes at or above a pixel's count read 0.  set_state needs all
+ * four arrays, ignores entries at or above a pixel's count, and is MDX_EINVAL (model untouched) for a count
+ * above nmixtures, a negative nframes or a stream outside [0, streams). */
+int mdx_bg_get_state(mdx_ctx* ctx, mdx_bg* bg, int stream, float* weight, float* variance, float* mean,
+                     uint8_t* modes, int* nframes);
+int mdx_bg_set_state(mdx_ctx* ctx, mdx_bg* bg, int stream, const float* weight, const float* variance,
+                     const float* mean, const uint8_t* modes, int nframes);
+
 /* Page-locked host memory for frames and outputs (e.g. the node's rgb8 staging buffer and its
  * trajectory outputs): copies between it and the device run as DMA at full link rate, while a
  * pageable buffer is staged by the runtime through bounce buffers.  Any entry taking host pointers

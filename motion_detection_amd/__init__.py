@@ -11,7 +11,8 @@ from .context import (ClusterResult, Context, FlowResult, OutlierResult, RegionR
 from .optical_flow_calculator import OpticalFlowCalculator
 from .flow_clusterer import FlowClusterer, bounding_rects, hulls_of
 from .outlier_detector import OutlierDetector
+from .background_subtractor import BackgroundSubtractor
 
-__all__ = ["build", "lib", "Context", "FlowResult", "OpticalFlowCalculator", "OutlierDetector", "MdxError", "MdxParams",
+__all__ = ["build", "lib", "Context", "BackgroundSubtractor", "FlowResult", "OpticalFlowCalculator", "OutlierDetector", "MdxError", "MdxParams",
            "FlowClusterer", "bounding_rects", "hulls_of", "ClusterResult", "OutlierResult", "RegionResult", "RegionTreeResult", "VectorClusterResult", "default_params", "grid_count", "grid_points", "half_size", "host_empty", "synth_pair", "LIB_PATH", "FMT_GRAY8", "FMT_RGB8",
            "FMT_BGR8", "FIT_FIRST4", "FIT_EXTERNAL", "FIT_RANSAC", "SUBSPACE_F64", "SUBSPACE_F32", "MDX_OK", "MDX_EDEGENERATE"]

@@ -35,6 +35,8 @@ OUTLIERS_MAX_POINTS = 131072  # include/mdx.h MDX_OUTLIERS_MAX_POINTS
 HULL_MAX_SPAN = 8192          # include/mdx.h MDX_HULL_MAX_SPAN
 REGION_NO_PARENT = -1         # include/mdx.h MDX_REGION_NO_PARENT
 REGION_PARENT_UNKNOWN = -2    # include/mdx.h MDX_REGION_PARENT_UNKNOWN
+BG_MAX_MIXTURES = 8           # include/mdx.h MDX_BG_MAX_MIXTURES
+BG_MAX_FRAMES_PER_LAUNCH = 32  # include/mdx.h MDX_BG_MAX_FRAMES_PER_LAUNCH
 
 # every symbol include/mdx.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -52,13 +54,15 @@ EXPORTED = [
     "mdx_find_outliers", "mdx_half_size", "mdx_resize_half_dev", "mdx_resize_half", "mdx_ring_push_half",
     "mdx_cluster_hulls", "mdx_region_hulls_dev", "mdx_mask_region_hulls",
     "mdx_region_parents_dev", "mdx_mask_regions_tree", "mdx_region_outlines_dev", "mdx_mask_region_outlines",
+    "mdx_bg_default_params", "mdx_bg_params_size", "mdx_bg_create", "mdx_bg_destroy", "mdx_bg_reset", "mdx_bg_frames",
+    "mdx_bg_apply_dev", "mdx_bg_image_dev", "mdx_bg_apply", "mdx_bg_image", "mdx_bg_get_state", "mdx_bg_set_state",
 ]
 ABI_VERSION = 11  # include/mdx.h MDX_ABI_VERSION
 
 # csrc/Makefile STAMPED: the files whose bytes the library's provenance stamp hashes, in order
 STAMPED = ["Makefile", "mdx_plan.h", "mdx_internal.h", "mdx_ctx.h", "mdx_dev.h", "mdx_api.cpp", "mdx_pair.cpp", "mdx_traj.cpp",
-           "mdx_post.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
-           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "mdx_resize.hip", "mdx_hull.hip", "mdx_outline.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
+           "mdx_post.cpp", "mdx_bg_api.cpp", "mdx_front.hip", "mdx_lk_point.hip", "mdx_fit.hip", "mdx_lk.hip", "mdx_warp.hip",
+           "mdx_subspace.hip", "mdx_cluster.hip", "mdx_vcluster.hip", "mdx_outliers.hip", "mdx_regions.hip", "mdx_resize.hip", "mdx_hull.hip", "mdx_outline.hip", "mdx_bg.hip", "synth.cpp", os.path.join("..", "..", "include", "mdx.h")]
 
 
 class MdxBandCand(C.Structure):
@@ -84,7 +88,16 @@ class MdxOutlierStats(C.Structure):
                 ("median_magnitude", C.c_double), ("mad_magnitude", C.c_double)]
 
 
+class MdxBgParams(C.Structure):
+    """mdx_bg_params (include/mdx.h): the mixture model's parameters, OpenCV 2.4's names."""
+    _fields_ = [("history", C.c_int32), ("nmixtures", C.c_int32), ("var_threshold", C.c_float),
+                ("var_threshold_gen", C.c_float), ("background_ratio", C.c_float), ("var_init", C.c_float),
+                ("var_min", C.c_float), ("var_max", C.c_float), ("ct", C.c_float), ("detect_shadows", C.c_int32),
+                ("shadow_value", C.c_int32), ("tau", C.c_float)]
+
+
 BAND_CAND_BYTES = 96
+assert C.sizeof(MdxBgParams) == 48
 assert C.sizeof(MdxOutlierStats) == 48
 assert C.sizeof(MdxRegion) == 32
 assert C.sizeof(MdxBandCand) == BAND_CAND_BYTES
@@ -290,6 +303,27 @@ def lib() -> C.CDLL:
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), vp, vp,
                                            C.c_int, C.POINTER(C.c_int)]
     L.mdx_mask_region_outlines.restype = C.c_int
+    L.mdx_bg_default_params.argtypes = [C.POINTER(MdxBgParams)]
+    L.mdx_bg_default_params.restype = None
+    L.mdx_bg_params_size.argtypes = []
+    L.mdx_bg_params_size.restype = C.c_size_t
+    L.mdx_bg_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MdxBgParams), C.POINTER(vp)]
+    L.mdx_bg_create.restype = C.c_int
+    for name in ("mdx_bg_destroy", "mdx_bg_reset", "mdx_bg_frames"):
+        getattr(L, name).argtypes = [vp, vp]
+        getattr(L, name).restype = C.c_int
+    L.mdx_bg_apply_dev.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_size_t, C.c_size_t, C.c_double, vp]
+    L.mdx_bg_apply_dev.restype = C.c_int
+    L.mdx_bg_image_dev.argtypes = [vp, vp, vp]
+    L.mdx_bg_image_dev.restype = C.c_int
+    L.mdx_bg_apply.argtypes = [vp, vp, u8p, C.c_int, C.c_double, u8p]
+    L.mdx_bg_apply.restype = C.c_int
+    L.mdx_bg_image.argtypes = [vp, vp, u8p]
+    L.mdx_bg_image.restype = C.c_int
+    L.mdx_bg_get_state.argtypes = [vp, vp, C.c_int, f32p, f32p, f32p, u8p, C.POINTER(C.c_int)]
+    L.mdx_bg_get_state.restype = C.c_int
+    L.mdx_bg_set_state.argtypes = [vp, vp, C.c_int, f32p, f32p, f32p, u8p, C.c_int]
+    L.mdx_bg_set_state.restype = C.c_int
     _lib = L
     return L
 
@@ -297,6 +331,16 @@ def lib() -> C.CDLL:
 def default_params(**overrides) -> MdxParams:
     p = MdxParams()
     lib().mdx_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def bg_default_params(**overrides) -> MdxBgParams:
+    p = MdxBgParams()
+    lib().mdx_bg_default_params(C.byref(p))
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise TypeError(f"unknown parameter {k!r}")

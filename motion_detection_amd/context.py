@@ -533,6 +533,61 @@ class Context:
             self._h, batch, _v(d_mask), w, h, stride, frame_stride, _lib.REGIONS_OPEN3 if open3 else 0, int(min_area),
             _v(d_regions), max_regions, _v(d_num_all), _v(d_num_kept), _v(d_labels), _v(d_mask_out)))
 
+    # -- background subtraction (include/mdx.h mdx_bg_*); a model is an int handle
+    def bg_create(self, streams: int, w: int, h: int, channels: int, **params) -> int:
+        """A background model of `streams` independent w x h streams; params: mdx_bg_params fields."""
+        p = _lib.bg_default_params(**params)
+        out = C.c_void_p(0)
+        self._check(lib().mdx_bg_create(self._h, streams, w, h, channels, C.byref(p), C.byref(out)))
+        return out.value
+
+    def bg_destroy(self, bg: int):
+        self._check(lib().mdx_bg_destroy(self._h, _v(bg)))
+
+    def bg_reset(self, bg: int):
+        self._check(lib().mdx_bg_reset(self._h, _v(bg)))
+
+    def bg_frames(self, bg: int) -> int:
+        return self._check(lib().mdx_bg_frames(self._h, _v(bg)))
+
+    def bg_apply_dev(self, bg: int, T: int, d_frames: int, stride: int, frame_stride: int, stream_stride: int = 0,
+                     learning_rate: float = -1.0, d_fgmask: int = 0) -> int:
+        """Asynchronous on the context stream (include/mdx.h mdx_bg_apply_dev); pointers are ints."""
+        return self._check(lib().mdx_bg_apply_dev(self._h, _v(bg), T, _v(d_frames), stride, frame_stride, stream_stride,
+                                                  float(learning_rate), _v(d_fgmask)))
+
+    def bg_image_dev(self, bg: int, d_out: int) -> int:
+        """Asynchronous on the context stream (include/mdx.h mdx_bg_image_dev); pointers are ints."""
+        return self._check(lib().mdx_bg_image_dev(self._h, _v(bg), _v(d_out)))
+
+    def bg_apply(self, bg: int, frame: np.ndarray, learning_rate: float = -1.0, want_mask: bool = True):
+        """One frame (h, w) or (h, w, 3) of a one-stream model, synchronous; returns the (h, w) mask."""
+        frame = _frame_view(frame)
+        mask = np.empty(frame.shape[:2], np.uint8) if want_mask else None
+        self._check(lib().mdx_bg_apply(self._h, _v(bg), _ptr(frame), frame.strides[0], float(learning_rate), _ptr(mask)))
+        return mask
+
+    def bg_image(self, bg: int, h: int, w: int, channels: int) -> np.ndarray:
+        out = np.empty((h, w) if channels == 1 else (h, w, channels), np.uint8)
+        self._check(lib().mdx_bg_image(self._h, _v(bg), _ptr(out)))
+        return out
+
+    def bg_get_state(self, bg: int, stream: int, h: int, w: int, channels: int, nmixtures: int) -> dict:
+        """One stream's model in the canonical host layout (include/mdx.h mdx_bg_get_state)."""
+        st = {"weight": np.empty((h, w, nmixtures), np.float32), "variance": np.empty((h, w, nmixtures), np.float32),
+              "mean": np.empty((h, w, nmixtures, channels), np.float32), "modes": np.empty((h, w), np.uint8)}
+        nf = C.c_int(0)
+        self._check(lib().mdx_bg_get_state(self._h, _v(bg), stream, _ptr(st["weight"]), _ptr(st["variance"]),
+                                           _ptr(st["mean"]), _ptr(st["modes"]), C.byref(nf)))
+        st["nframes"] = nf.value
+        return st
+
+    def bg_set_state(self, bg: int, stream: int, state: dict):
+        a = {k: np.ascontiguousarray(state[k], np.uint8 if k == "modes" else np.float32)
+             for k in ("weight", "variance", "mean", "modes")}
+        self._check(lib().mdx_bg_set_state(self._h, _v(bg), stream, _ptr(a["weight"]), _ptr(a["variance"]), _ptr(a["mean"]),
+                                           _ptr(a["modes"]), int(state.get("nframes", 0))))
+
     # -- half-size ingest (the node's cv::resize(img, out, Size(), 0.5, 0.5), node.cpp:470-474; DESIGN.md §7i)
     def resize_half(self, image: np.ndarray) -> np.ndarray:
         """image: (h, w) or (h, w, 3) uint8, a row-pitched view allowed.  Returns a new packed array of

@@ -1,5 +1,5 @@
 // mdx_ctx.h -- the context behind the C-ABI (include/mdx.h) and what every host file (mdx_api.cpp, mdx_pair.cpp,
-// mdx_traj.cpp, mdx_post.cpp) needs of it: owning types, errors, workspace growth, the frame check.
+// mdx_traj.cpp, mdx_post.cpp, mdx_bg_api.cpp) needs of it: owning types, errors, workspace growth, the frame check.
 #pragma once
 
 #include "../../include/mdx.h"
@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -61,6 +62,17 @@ struct LkTuning {
     bool lk_fma = true;
     int spin_max = mdx::kLkSpinDefault;  // MDX_LK_SPIN_MAX (debug: < 0 injects timeouts)
     bool ol_reg = true;       // MDX_OL_REG=0: findOutliers re-reads its values on every pass at every size
+};
+
+// A background model (mdx_bg_create, mdx_bg_api.cpp): owned by its context's `bgs`, freed with it.
+struct mdx_bg {
+    mdx_ctx* owner = nullptr;
+    int streams = 0, w = 0, h = 0, channels = 0;
+    mdx_bg_params prm{};
+    int nframes = 0;
+    DevBuf state, modes;       // mdx_internal.h BgModel
+    DevBuf hin, hout;          // the host conveniences' frame, and mask or image
+    std::vector<float> xfer;   // get_state / set_state: one stream's planes on the host; only ever grows
 };
 
 struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
@@ -133,6 +145,7 @@ struct mdx_ctx : LkTuning {   // the knobs stay plain members (c->lk_cap, ...)
     DevBuf rtout;                            // mdx_mask_regions_tree (host entry): counts, records, parents, labels, offsets, xy
     DevBuf roscr;                            // mdx_region_outlines_dev: neighbour masks, state indices, state words
     DevBuf roout;                            // mdx_mask_region_outlines (host entry): counts, records, parents, labels, offsets, xy
+    std::vector<std::unique_ptr<mdx_bg>> bgs;   // background models not yet destroyed (mdx_bg_create)
     DevBuf ring_pyr, ring_der, rin;          // resident frame ring (mdx_ring_*)
     DevBuf rfull;                            // mdx_ring_push_half: the full-size frame, halved into rin
     DevBuf hsrc, hdst;                       // mdx_resize_half (host entry): the frame and its half
@@ -191,6 +204,15 @@ inline int ensure(mdx_ctx* c, DevBuf& b, size_t need)
     if (b.p) (void)hipStreamSynchronize(c->stream);   // the aux stream's work is always joined by c->stream
     if (!b.alloc(need)) return set_err(c, MDX_ENOMEM, "hipMalloc(%zu) failed", need);
     return MDX_OK;
+}
+
+// mdx_input_ready is one-shot: the next device entry makes stream s wait for the caller's event, once
+inline hipError_t wait_input_ready(mdx_ctx* c, hipStream_t s)
+{
+    if (!c->input_ev) return hipSuccess;
+    hipEvent_t e = c->input_ev;
+    c->input_ev = nullptr;
+    return hipStreamWaitEvent(s, e, 0);
 }
 
 // n page-locked ints, the context's until mdx_destroy; null on failure

@@ -1,6 +1,6 @@
 // mdx_internal.h -- the one interface between the HIP kernel files (mdx_front.hip, mdx_lk_point.hip,
-// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip, mdx_resize.hip, mdx_hull.hip, mdx_outline.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
-// mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp).  Not part of the C-ABI.
+// mdx_fit.hip, mdx_lk.hip, mdx_warp.hip, mdx_subspace.hip, mdx_cluster.hip, mdx_vcluster.hip, mdx_outliers.hip, mdx_regions.hip, mdx_resize.hip, mdx_hull.hip, mdx_outline.hip, mdx_bg.hip) and the host files (mdx_ctx.h, mdx_api.cpp,
+// mdx_pair.cpp, mdx_traj.cpp, mdx_post.cpp, mdx_bg_api.cpp).  Not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -413,5 +413,27 @@ bool half_vector_path(int batch, const void* src, int stride, size_t frame_strid
                       size_t dst_frame_stride);
 hipError_t launch_half(hipStream_t s, int batch, const uint8_t* src, int w, int h, int stride, size_t frame_stride,
                        int channels, uint8_t* dst, int dst_stride, size_t dst_frame_stride);
+
+// Background subtraction (mdx_bg.hip): the per-pixel Gaussian mixture of `streams` independent
+// models of w x h pixels.  state: per stream bg_state_floats floats, one plane of w * h per (mode, field) --
+// plane m the weights of mode m, nmixtures + m its variances, 2 * nmixtures + m * channels + c its means;
+// modes: [streams][h][w] bytes.  One launch each on s, no host synchronisation.
+constexpr int kBgMaxFrames = 32;        // frames one k_bg_apply launch carries a mixture through
+constexpr int kBgMaxStreams = 65535;    // models per launch (grid y)
+struct BgModel {
+    float* state;
+    uint8_t* modes;
+    int streams, w, h, channels;
+    mdx_bg_params prm;
+};
+__host__ __device__ inline size_t bg_state_floats(int w, int h, int channels, int nmixtures)
+{
+    return (size_t)w * h * nmixtures * (2 + channels);
+}
+// frames: stream s, frame t, row y at frames + s * stream_stride + t * frame_stride + y * stride; alphaT [T],
+// T <= kBgMaxFrames; mask (may be null): stream s, frame t at mask + s * mask_stream_stride + t * w * h
+hipError_t launch_bg_apply(hipStream_t s, const BgModel& M, int T, const uint8_t* frames, int stride, size_t frame_stride,
+                           size_t stream_stride, const float* alphaT, uint8_t* mask, size_t mask_stream_stride);
+hipError_t launch_bg_image(hipStream_t s, const BgModel& M, uint8_t* out /* [streams][h][w][channels] */);
 
 }  // namespace mdx

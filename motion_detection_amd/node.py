@@ -65,6 +65,7 @@ further-advanced rand() stream, as the reference's spinning loop does.
 """
 from __future__ import annotations
 
+import os
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable
@@ -72,6 +73,7 @@ from typing import Callable
 import numpy as np
 
 from . import _lib
+from .background_subtractor import BackgroundSubtractor
 from .context import grid_points, half_size
 from .flow_clusterer import FlowClusterer, bounding_rects
 from .formats import MotionLogger
@@ -159,7 +161,12 @@ class MotionDetectionNode:
                        "region_external": False,
                        # the outer border polyline of every kept mask region, findContours' own point list
                        # (region_min_area set): off by default; logged with writeContour behind the hulls
-                       "region_outlines": False}
+                       "region_outlines": False,
+                       # the reference's BackgroundSubtractor bs_ (motion_detection_node.h:93): every
+                       # frame that enters the ring also updates a MOG2 model of its size on the device; with
+                       # region_min_area and a log_path set, the external regions of its opened mask go to
+                       # motion_bg.log beside the log_path.  Off by default
+                       "background_subtraction": False}
         if params:
             self.params.update(params)
         self.on_result = on_result
@@ -173,6 +180,10 @@ class MotionDetectionNode:
         self.logger = None                                # MotionLogger (log_contours with a log_path)
         self._pair_tools = None                           # detect_outliers' (context, detector, clusterer)
         self._device = device
+        self.bs = None                                    # background_subtraction's BackgroundSubtractor
+        self.bg_logger = None                             # its MotionLogger (motion_bg.log)
+        self.bg_rectangles: list = []                     # the newest frame's external regions of its mask
+        self.bg_contours: list = []
         self._ring_msgs: list = []                        # run_once: the messages held by the device ring, oldest
         self._ring_ctx = None                             # first, and the context whose ring it is
 
@@ -225,6 +236,25 @@ class MotionDetectionNode:
         for k, hull in enumerate(hulls):
             self.logger.writeContour(hull, self.global_frame_count, k)
 
+    def _update_background(self, frame: np.ndarray):
+        """BackgroundSubtractor::getMotionContours on the frame that just entered the ring: the model update and,
+        with region_min_area set, the external regions of its opened mask, one writeBoundingBox line each in
+        motion_bg.log (beside log_path) when a log_path is set."""
+        min_area = self.params.get("region_min_area")
+        if self.bs is None:
+            self.bs = BackgroundSubtractor(device=self._device, min_area=int(min_area or 1))
+        if min_area is None:
+            self.bs.apply(frame, want_mask=False)
+            return
+        self.bs.min_area = int(min_area)
+        self.bg_contours, self.bg_rectangles = self.bs.getMotionContours(frame)
+        if not self.params.get("log_path"):
+            return
+        if self.bg_logger is None:
+            self.bg_logger = MotionLogger(os.path.join(os.path.dirname(self.params["log_path"]), "motion_bg.log"))
+        for k, rect in enumerate(self.bg_rectangles):
+            self.bg_logger.writeBoundingBox(rect, self.global_frame_count, k)
+
     @property
     def trajectory_size(self) -> int:
         # node.cpp:241-245
@@ -244,6 +274,8 @@ class MotionDetectionNode:
             self.raw_images.append(msg)
             self.raw_images.popleft()
             self.image_received = True
+        if self.params.get("background_subtraction"):
+            self._update_background(to_rgb8(msg))
         out = None
         if self.params.get("use_all_frames", True) and self.image_received:
             if self.params.get("live_chain", True):
